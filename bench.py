@@ -6,7 +6,10 @@ features per image; one step = ORBextractor on B left + B right images and
 Frame::ComputeStereoMatches on the B pairs, inputs resident in HBM before timing.
 Synthetic frames (no datasets in the image): my_orb_slam2_amd.synth.stereo_pair.
 
-    python bench.py [--gpus N --steps K --warmup W --batch B]
+    python bench.py [--gpus N --steps K --warmup W --batch B]    the timed steps, one result line
+    python bench.py --full ...           also the CPU baselines, the one-stream pass, the roofline
+                                         of every kernel and the verification of the outputs
+    python bench.py --dump-outputs DIR   also DIR/<name>.npy: the last timed step's outputs
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank/GPU)
 
 Multi-GPU: pairs are independent (src/Frame.cc:72-130), so every rank runs its own batch
@@ -68,8 +71,17 @@ def parse():
                     help="synthetic base pairs / frames generated per rank (stereo default: one "
                          "per batch slot, 512 independent scenes; fewer: the batch slots are "
                          "row-rolled copies of them, all distinct; other workloads default 32)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the benchmark measures and "
+                         "checks: the CPU baselines (--cpu-seconds) of every workload, and for "
+                         "stereo the one-stream comparison pass (--serial-steps) with its "
+                         "per-kernel roofline and the slot-by-slot verification of the timed "
+                         "outputs.  Off: set up, warm up, time the steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="stereo: after the timed steps write what the last one computed to "
+                         "DIR/<name>.npy (float32; see dump_outputs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
-                    help="CPU-baseline sample budget (0 disables)")
+                    help="--full: CPU-baseline sample budget (0 disables)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--host-io", action="store_true",
                     help="stereo: time the PCIe-inclusive path (H2D of both views from pinned host "
@@ -88,8 +100,8 @@ def parse():
                          "(orbx_extractor_set_overlap; 0 = every kernel in sequence; default: the "
                          "library's)")
     ap.add_argument("--serial-steps", type=int, default=20,
-                    help="stereo: steps of the one-stream comparison pass after the timed region "
-                         "(0: none)")
+                    help="stereo, --full: steps of the one-stream comparison pass after the timed "
+                         "region (0: none)")
     ap.add_argument("--inflight", type=int, default=2,
                     help="stereo: batches in flight on separate HIP streams (step i uses handle "
                          "and stream i %% inflight; 1: one batch at a time)")
@@ -284,6 +296,11 @@ def main():
     args = parse()
     if args.distinct is None:   # the headline: every slot its own scene
         args.distinct = (args.batch or 512) if args.workload == "stereo" else 32
+    if args.dump_outputs and args.workload != "stereo":
+        sys.exit("bench.py: --dump-outputs covers the stereo workload only")
+    if not args.full:   # a plain run: nothing beside the timed steps
+        args.cpu_seconds = 0.0
+        args.serial_steps = 0
     relaunch_if_needed(args)
     keep_stdout_for_result()
     if args.traffic_csv is None:
@@ -378,9 +395,12 @@ def main():
     # sanity on the produced work (outside the timed region)
     nv = sb.nvalid.cpu().numpy()
     nkp, _, _ = sb.fetch("left")
-    # every in-flight handle's outputs of its last timed step, per slot (outside the timed
-    # region), for the comparison with the one-stream pass below
-    dig_inflight = [stereo_digests(h) for h in sbs] if io is None else None
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the handle of the last timed step (before the one-stream pass reruns handle 0)
+        dump_outputs(args.dump_outputs, sbs[(args.steps - 1) % len(sbs)], B)
+    # --full: every in-flight handle's outputs of its last timed step, per slot (outside the
+    # timed region), for the comparison with the one-stream pass below
+    dig_inflight = [stereo_digests(h) for h in sbs] if args.full and io is None else None
 
     # The same step with every kernel in sequence on one stream and one batch in flight
     # (outside the timed region): the overlap's gain measured in this run, and each kernel's
@@ -527,6 +547,40 @@ def stereo_digests(sb) -> list:
     nv = sb.nvalid[:B].cpu().numpy()
     return [slot_digest(kl[i, :nkl[i]], dl[i, :nkl[i]], kr[i, :nkr[i]], dr[i, :nkr[i]],
                         u[i, :nkl[i]], z[i, :nkl[i]], nv[i]) for i in range(B)]
+
+
+DUMP_SLOTS = 32            # pairs of the batch a dump holds
+DUMP_BYTES = 60 << 20      # and the most it may take (fewer pairs when kp_cap is large)
+
+
+def dump_outputs(path, sb, B) -> None:
+    """--dump-outputs: the outputs of StereoBatch `sb`'s last call as `path`/<name>.npy, all
+    float32 (every value is a float32 or a small integer, so none is rounded).  The counts
+    cover the whole batch: nkp_left, nkp_right, nvalid [B].  The rest covers a fixed sample
+    of S pairs (`slots` [S]: sorted pair indices, numpy default_rng(0)), one row per keypoint
+    slot, rows from the pair's count on zeroed (the library leaves them unwritten):
+    keypoints_left / keypoints_right [S, kp_cap, 7] (x, y, size, angle, response, octave,
+    class_id), descriptors_left / descriptors_right [S, kp_cap, 32] (one byte each), uright and
+    depth [S, kp_cap] of the left keypoints.  The inputs are seeded, so two runs with the
+    same arguments write the same files."""
+    os.makedirs(path, exist_ok=True)
+    nkl, kl, dl = sb.fetch("left")
+    nkr, kr, dr = sb.fetch("right")
+    kc = kl.shape[1]
+    S = max(1, min(B, DUMP_SLOTS, DUMP_BYTES // (4 * kc * (2 * (7 + 32) + 2))))
+    sel = np.sort(np.random.default_rng(0).choice(B, S, replace=False))
+    out = {"nkp_left": nkl[:B], "nkp_right": nkr[:B], "nvalid": sb.nvalid[:B].cpu().numpy(),
+           "slots": sel}
+    for side, n, k, d in (("left", nkl, kl, dl), ("right", nkr, kr, dr)):
+        live = np.arange(kc)[None, :] < n[sel][:, None]
+        kp = np.stack([k[sel][f].astype(np.float32) for f in k.dtype.names], axis=-1)
+        out["keypoints_" + side] = np.where(live[..., None], kp, np.float32(0))
+        out["descriptors_" + side] = np.where(live[..., None], d[sel], 0)
+        if side == "left":
+            for name, t in (("uright", sb.uR), ("depth", sb.depth)):
+                out[name] = np.where(live, t[:B].cpu().numpy()[sel], np.float32(0))
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def verification(dig_inflight, dig_serial, B):

@@ -240,3 +240,68 @@ def test_ta_busy_from_committed_pass():
     t = b.ta_busy_from_csv(b.DEFAULT_TA, "k_orient_desc")
     assert t is not None and 0.5 < t <= 1.0
     assert b.ta_busy_from_csv(b.DEFAULT_TA, "k_no_such_kernel") is None
+
+
+def test_plain_run_options():
+    """--full and --dump-outputs exist and are off by default; --steps is the timed steps."""
+    b = _bench()
+    argv, sys.argv = sys.argv, ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+    try:
+        a = b.parse()
+    finally:
+        sys.argv = argv
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+
+
+def test_dump_outputs_files(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; the counts of every pair, the other arrays for the
+    seeded sample of pairs, bit for bit what the handle holds, unwritten rows zeroed."""
+    import numpy as np
+    import torch
+    from my_orb_slam2_amd._lib import KEYPOINT_DTYPE
+    b = _bench()
+    B, kc = 9, 5
+    rng = np.random.default_rng(3)
+
+    class Handle:   # a StereoBatch after a call: rows past a pair's count hold leftovers
+        def __init__(self):
+            self.n = {s: rng.integers(0, kc + 1, B).astype(np.int32) for s in ("left", "right")}
+            self.k = {s: rng.integers(1, 99, (B, kc, 7)).astype(np.float32) for s in self.n}
+            self.d = {s: rng.integers(0, 256, (B, kc, 32), dtype=np.uint8) for s in self.n}
+            self.uR = torch.from_numpy(rng.random((B, kc), np.float32))
+            self.depth = torch.from_numpy(rng.random((B, kc), np.float32))
+            self.nvalid = torch.from_numpy(rng.integers(0, kc, B).astype(np.int32))
+
+        def fetch(self, side):
+            kp = np.zeros((B, kc), KEYPOINT_DTYPE)
+            for j, f in enumerate(KEYPOINT_DTYPE.names):
+                kp[f] = self.k[side][..., j]
+            return self.n[side], kp, self.d[side]
+
+    h = Handle()
+    monkeypatch.setattr(b, "DUMP_SLOTS", 4)
+    b.dump_outputs(str(tmp_path / "o"), h, B)
+    got = {p.stem: np.load(p) for p in (tmp_path / "o").iterdir()}
+    assert sorted(got) == sorted(["nkp_left", "nkp_right", "nvalid", "slots", "keypoints_left",
+                                  "keypoints_right", "descriptors_left", "descriptors_right",
+                                  "uright", "depth"])
+    assert all(a.dtype == np.float32 for a in got.values())
+    sel = got["slots"].astype(int)
+    assert len(sel) == 4 and (np.diff(sel) > 0).all() and sel.min() >= 0 and sel.max() < B
+    assert np.array_equal(got["nkp_left"], h.n["left"]) and np.array_equal(got["nkp_right"], h.n["right"])
+    assert np.array_equal(got["nvalid"], h.nvalid.numpy())
+    for s, i in enumerate(sel):
+        for side in ("left", "right"):
+            n = h.n[side][i]
+            assert np.array_equal(got["keypoints_" + side][s, :n], h.k[side][i, :n])
+            assert np.array_equal(got["descriptors_" + side][s, :n], h.d[side][i, :n])
+            assert not got["keypoints_" + side][s, n:].any()
+            assert not got["descriptors_" + side][s, n:].any()
+        n = h.n["left"][i]
+        assert np.array_equal(got["uright"][s, :n], h.uR.numpy()[i, :n])
+        assert np.array_equal(got["depth"][s, :n], h.depth.numpy()[i, :n])
+        assert not got["uright"][s, n:].any() and not got["depth"][s, n:].any()
+    # the same handle, the same files
+    b.dump_outputs(str(tmp_path / "p"), h, B)
+    for name, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "p" / (name + ".npy")), a)

@@ -331,3 +331,38 @@ def test_resident_equals_tensor_path(orbx_lib, gpu):
             assert_bytes_equal(kb[2][i, :n], ka[2][i, :n], f"{side} {i} desc")
         # the level-0 slots hold the inputs untouched by the extraction
     assert torch.equal(Lv, Ls) and torch.equal(Rv, Rs)
+
+
+def test_dump_outputs_of_timed_handles(orbx_lib, gpu, tmp_path):
+    """bench.py --dump-outputs on the timed configuration at 6 pairs: both in-flight handles
+    (the same pairs) dump the same files, and a dumped pair is the pair the handle holds."""
+    import torch
+    B, NI = 6, 2
+    Lh, Rh, _, _ = bench.stereo_inputs(0, B, B)
+    Ls, Rs = torch.from_numpy(Lh).to(gpu), torch.from_numpy(Rh).to(gpu)
+    mb = float(np.float32(bench.MBF) / np.float32(bench.FX))
+    import my_orb_slam2_amd as m
+    sbs, sts, run_on, run_step, _ = bench.headline_handles(
+        torch, m, gpu, 0, B, Ls, Rs, NI, None, True, mb)
+    for i in range(4):
+        run_step(i)
+    torch.cuda.synchronize()
+    for k, h in enumerate(sbs):
+        bench.dump_outputs(str(tmp_path / str(k)), h, B)
+    names = sorted(p.name for p in (tmp_path / "0").iterdir())
+    assert len(names) == 10
+    a = {n: np.load(tmp_path / "0" / n) for n in names}
+    for n in names:
+        assert a[n].dtype == np.float32
+        assert np.array_equal(a[n], np.load(tmp_path / "1" / n), equal_nan=True), n
+    nkp, kps, desc = sbs[1].fetch("left")
+    assert np.array_equal(a["nkp_left.npy"], nkp) and nkp.min() > 100
+    assert np.array_equal(a["slots.npy"], np.arange(B))
+    u = sbs[1].uR.cpu().numpy()
+    for i in range(B):
+        n = nkp[i]
+        assert np.array_equal(a["keypoints_left.npy"][i, :n, 0], kps[i, :n]["x"])
+        assert np.array_equal(a["keypoints_left.npy"][i, :n, 5], kps[i, :n]["octave"])
+        assert np.array_equal(a["descriptors_left.npy"][i, :n], desc[i, :n])
+        assert_f32_bits_equal(a["uright.npy"][i, :n], u[i, :n], f"pair {i} uRight")
+        assert not a["keypoints_left.npy"][i, n:].any() and not a["uright.npy"][i, n:].any()

@@ -22,7 +22,7 @@ def main(argv):
     else:
         cfgs, extra = argv, []
     for cfg in cfgs:
-        cmd = [sys.executable, str(ROOT / "bench.py"), "--cpu-seconds", "0", "--overlap", cfg] + extra
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--cpu-seconds", "0", "--overlap", cfg] + extra
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         if r.returncode != 0:
             print(cfg, "FAILED rc", r.returncode, r.stderr[-2000:], flush=True)

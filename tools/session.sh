@@ -29,7 +29,7 @@ for step in "$@"; do
         || { echo "SMOKE FAILED"; tail -20 $OUT/smoke.log; exit 1; }
       tail -1 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err \
+      timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err \
         || { echo "BENCH FAILED"; tail -20 $OUT/bench.err; exit 1; }
       python -c "import json,sys; j=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1]); print('bench', j['value'], j['ms_per_step'], json.dumps(j.get('roofline'))[:400])" ;;
     prof)
@@ -37,7 +37,7 @@ for step in "$@"; do
         || { echo "PROF FAILED"; tail -20 $OUT/prof.log; exit 1; }
       echo prof done ;;
     dropin)
-      timeout -k 10 600 python bench.py --workload dropin --frames 300 > $OUT/dropin.json 2> $OUT/dropin.err \
+      timeout -k 10 600 python bench.py --full --workload dropin --frames 300 > $OUT/dropin.json 2> $OUT/dropin.err \
         || { echo "DROPIN BENCH FAILED"; tail -20 $OUT/dropin.err; exit 1; }
       echo dropin done ;;
     counters)
@@ -63,7 +63,7 @@ for step in "$@"; do
       echo match counters done ;;
     workloads)
       for w in euroc reloc triangulation bf kfdb tum; do
-        timeout -k 10 300 python bench.py --workload $w --cpu-seconds 5 > $OUT/$w.json 2> $OUT/$w.err \
+        timeout -k 10 300 python bench.py --full --workload $w --cpu-seconds 5 > $OUT/$w.json 2> $OUT/$w.err \
           || { echo "WORKLOAD $w FAILED"; tail -20 $OUT/$w.err; exit 1; }
       done
       timeout -k 10 300 python bench.py --host-io --cpu-seconds 0 > $OUT/hostio.json 2> $OUT/hostio.err \

@@ -75,7 +75,7 @@ def run(bench_args):
     for rep in range(rounds):
         for name, v in variants.items():
             env = dict(os.environ, ORBX_LIB=str(ROOT / v["lib"]))
-            cmd = [sys.executable, str(ROOT / "bench.py"), "--cpu-seconds", "0"] + bench_args
+            cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--cpu-seconds", "0"] + bench_args
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
             if r.returncode != 0:
                 print(name, "FAILED rc", r.returncode, r.stderr[-2000:], flush=True)
