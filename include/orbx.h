@@ -84,7 +84,16 @@ orbx_status orbx_extract_view(orbx_extractor* h, const uint8_t* img, int width, 
 
 /* Build the geometry and device workspace for width x height images and up to `batch`
  * images per call (otherwise done lazily by the first call); *kp_cap = keypoint slots per
- * image in the batched outputs. */
+ * image in the batched outputs.
+ * Any call that changes the handle's image size or grows its workspace (this one, or an
+ * extraction at another size or with more images) discards what the handle held: until the
+ * next extraction orbx_pyramid_level, orbx_blur_level, orbx_host_pyramid_view,
+ * orbx_batch_view_get and the stereo calls over the last extraction return ORBX_ERR_STATE
+ * (orbx_batch_fetch: ORBX_ERR_INVALID), also when the new size itself is refused.
+ * ORBX_ERR_UNSUPPORTED sizes: a pyramid level wider or taller than 4128 pixels, and a level of
+ * w x h pixels with more than 512 octree roots, round((w - 32) / (h - 32)) > 512
+ * (src/ORBextractor.cc:543: a strip whose usable area is a pixel or two tall, e.g. 545 x 33;
+ * DistributeOctTree's node arrays, four per root, are kept in LDS). */
 orbx_status orbx_extractor_prepare(orbx_extractor* h, int width, int height, int batch,
                                    int* kp_cap);
 
@@ -102,8 +111,10 @@ orbx_status orbx_pyramid_level(orbx_extractor* h, int index, int level, uint8_t*
  * step[l] bytes apart (the layout of a cv::Mat ROI, like the reference's levels, which are
  * views into a bordered image).  The block stays valid until the next orbx_extract(_view) on
  * the handle or its destruction; no other call writes it.  ORBX_ERR_STATE when the last such
- * call ran with host_pyramid off (the default) or failed.  The drop-in facade
- * (integration/ORBextractor.h) turns it on in its constructor. */
+ * call ran with host_pyramid off (the default) or failed, or when a later call on the handle
+ * (a batched extraction, a stereo frame, orbx_extractor_prepare) changed the image size: the
+ * view describes the block with the handle's geometry, which no longer fits it.  The drop-in
+ * facade (integration/ORBextractor.h) turns it on in its constructor. */
 orbx_status orbx_extractor_host_pyramid(orbx_extractor* h, int on);
 /* A counter that changes whenever the handle's pyramids do (every extraction or stereo frame on
  * it, a workspace regrowth): a caller that keeps (handle, image index) as the source of a view's

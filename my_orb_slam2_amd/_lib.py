@@ -48,6 +48,13 @@ class BatchView(ctypes.Structure):
                 ("level_pitch", ctypes.c_int * 16), ("level_off", ctypes.c_size_t * 16)]
 
 
+class HostPyramid(ctypes.Structure):
+    """orbx_host_pyramid (include/orbx.h)."""
+    _fields_ = [("nlevels", ctypes.c_int), ("data", ctypes.c_void_p * 16),
+                ("width", ctypes.c_int * 16), ("height", ctypes.c_int * 16),
+                ("step", ctypes.c_size_t * 16)]
+
+
 # name -> (restype, argtypes); the exported C ABI (include/orbx.h)
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -62,6 +69,8 @@ SIGNATURES = {
                                ctypes.POINTER(_i)]),
     "orbx_pyramid_level": (_i, [_vp, _i, _i, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "orbx_extractor_keep_pyramid": (_i, [_vp, _i]),
+    "orbx_extractor_host_pyramid": (_i, [_vp, _i]),
+    "orbx_host_pyramid_view": (_i, [_vp, _vp]),
     "orbx_frame_server_get_stats": (_i, [_vp, _vp, _i]),
     "orbx_frame_server_release": (_i, [_vp]),
     "orbx_blur_level": (_i, [_vp, _i, _i, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),

@@ -902,8 +902,18 @@ orbx_status ensure_workspace(orbx_extractor* h, int W, int H, int batch) {
     if (!same) {
         // this handle's earlier calls may still read the old tables (on their streams)
         if (!wait_idle(h)) return ORBX_ERR_DEVICE;
+        // Everything the handle holds was laid out by the old geometry, and every query
+        // describes it with h->hg: the host pyramid copy (orbx_host_pyramid_view), the device
+        // pyramids (orbx_pyramid_level) and the outputs of the last call (orbx_batch_fetch,
+        // orbx_stereo_match) stop being valid here, whether or not the new size is supported
+        // or the uploads below succeed; the next extraction refills them.
+        h->have_geom = false;
+        h->host_pyr_ok = false;
+        h->last_valid = false;
+        h->pyr_images = 0;
+        ++h->serial;
         orbx_status s = build_geometry(h, W, H);
-        if (s != ORBX_OK) { h->have_geom = false; return s; }
+        if (s != ORBX_OK) return s;
         if (!h->d_geom.ensure(sizeof(Geometry))) return ORBX_ERR_DEVICE;
         if (!h->d_cells.ensure(std::max<size_t>(h->cells.size(), 1) * sizeof(CellDesc))) return ORBX_ERR_DEVICE;
         if (!h->d_rtab.ensure(std::max<size_t>(h->rtab.size(), 1) * 2)) return ORBX_ERR_DEVICE;
@@ -930,7 +940,8 @@ orbx_status ensure_workspace(orbx_extractor* h, int W, int H, int batch) {
     if (batch > h->cap_batch) {
         // growing frees the old buffers: the handle's work in flight must be done
         if (!wait_idle(h)) return ORBX_ERR_DEVICE;
-        h->pyr_images = 0;   // the pyramids go with them
+        h->pyr_images = 0;   // the pyramids go with them,
+        h->last_valid = false;   // and the last call's outputs (d_outs is reallocated)
         ++h->serial;
         const Geometry& G = h->hg;
         const size_t B = (size_t)batch;

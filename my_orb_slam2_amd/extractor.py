@@ -10,7 +10,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import BatchView, ExtractorParams, KERNELS, KEYPOINT_DTYPE, check, load, ptr
+from ._lib import (BatchView, ExtractorParams, HostPyramid, KERNELS, KEYPOINT_DTYPE, check, load,
+                   ptr)
 
 
 class _DeviceArray:
@@ -139,6 +140,25 @@ class ORBextractor:
         pyramids (image 0 = left, 1 = right) whether the frame ran alone or in a frame-server
         batch; off (the default) none in either case."""
         check("orbx_extractor_keep_pyramid", self._L.orbx_extractor_keep_pyramid(self._h, int(on)))
+
+    def host_pyramid(self, on: bool = True):
+        """orbx_extractor_host_pyramid: every ``extractor(image)`` call also leaves its pyramid
+        in a pinned host block of the handle (``host_pyramid_view``)."""
+        check("orbx_extractor_host_pyramid", self._L.orbx_extractor_host_pyramid(self._h, int(on)))
+
+    def host_pyramid_view(self):
+        """orbx_host_pyramid_view: the levels of the last ``extractor(image)`` call as copies
+        of the handle's host block.  Raises OrbxError (ORBX_ERR_STATE) when the block holds no
+        valid pyramid: host_pyramid off, or the image size changed since that call."""
+        hp = HostPyramid()
+        check("orbx_host_pyramid_view", self._L.orbx_host_pyramid_view(self._h, ctypes.byref(hp)))
+        levels = []
+        for l in range(hp.nlevels):
+            w, h, step = hp.width[l], hp.height[l], hp.step[l]
+            raw = (ctypes.c_uint8 * (step * (h - 1) + w)).from_address(hp.data[l])
+            rows = np.lib.stride_tricks.as_strided(np.frombuffer(raw, np.uint8), (h, w), (step, 1))
+            levels.append(rows.copy())
+        return levels
 
     def frame_server_stats(self, reset: bool = False) -> dict:
         """Counters of the frame server this handle's ``extract_stereo`` calls go to
