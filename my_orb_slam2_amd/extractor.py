@@ -15,11 +15,11 @@ from ._lib import (BatchView, ExtractorParams, HostPyramid, KERNELS, KEYPOINT_DT
 
 
 class _DeviceArray:
-    """A device uint8 array by address (__cuda_array_interface__, which torch.as_tensor wraps
-    without copying)."""
+    """A device array by address (__cuda_array_interface__, which torch.as_tensor wraps
+    without copying); uint8 unless another typestr is given."""
 
-    def __init__(self, ptr_value: int, shape, strides):
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": "|u1",
+    def __init__(self, ptr_value: int, shape, strides, typestr: str = "|u1"):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr,
                                          "data": (int(ptr_value), False),
                                          "strides": tuple(strides), "version": 2}
 
@@ -263,6 +263,21 @@ class ORBextractor:
         check("orbx_batch_view_get", self._L.orbx_batch_view_get(self._h, ctypes.byref(v)))
         return v
 
+    def batch_tensors(self):
+        """(kps, desc, nkp) of the last batched call as torch tensors over the handle's device
+        buffers (views of ``batch_view()``, no copy): kps [batch, kp_cap, 28] uint8 (the bytes
+        of KEYPOINT_DTYPE: five float32 and two int32 per keypoint), desc [batch, kp_cap, 32]
+        uint8, nkp [batch] int32.  Valid until a call that reallocates the workspace; reads
+        and writes are the caller's to order against the handle's launches."""
+        import torch
+        v = self.batch_view()
+        dev = torch.device("cuda", self.params.device)
+        B, KC = v.batch, v.kp_cap
+        kps = torch.as_tensor(_DeviceArray(v.kps, (B, KC, 28), (KC * 28, 28, 1)), device=dev)
+        desc = torch.as_tensor(_DeviceArray(v.desc, (B, KC, 32), (KC * 32, 32, 1)), device=dev)
+        nkp = torch.as_tensor(_DeviceArray(v.nkp, (B,), (4,), "<i4"), device=dev)
+        return kps, desc, nkp
+
 
 def compute_stereo_matches(left: ORBextractor, right: ORBextractor, mbf: float, mb: float):
     """Frame::ComputeStereoMatches over the last extraction of `left` and `right`.
@@ -277,6 +292,16 @@ def compute_stereo_matches(left: ORBextractor, right: ORBextractor, mbf: float, 
     check("orbx_stereo_match", left._L.orbx_stereo_match(
         left._h, right._h, mbf, mb, ptr(u), ptr(d), n, ctypes.byref(nv)))
     return u[:n], d[:n], nv.value
+
+
+def compute_stereo_matches_batch_device(left: ORBextractor, right: ORBextractor, mbf: float,
+                                        mb: float, uR, depth, nvalid, stream=None):
+    """Frame::ComputeStereoMatches over the last batched extraction of `left` and `right`
+    (orbx_stereo_match_batch_device): image i of `left` against image i of `right`.  uR and
+    depth are [batch, kp_cap] float32 device tensors (slots past a pair's left count are not
+    written), nvalid a [batch] int32 device tensor or None; nothing is copied to the host."""
+    check("orbx_stereo_match_batch_device", left._L.orbx_stereo_match_batch_device(
+        left._h, right._h, mbf, mb, ptr(uR), ptr(depth), ptr(nvalid), ptr(stream)))
 
 
 class FrameServerStats(ctypes.Structure):

@@ -74,6 +74,8 @@ def lib():
         L.oracle_get_level_keypoints.argtypes = [vp, i32, vp, i32]
         L.oracle_get_tables.argtypes = [vp] * 7
         L.oracle_stereo_match.argtypes = [vp, vp, f32, f32, vp, vp]
+        L.oracle_stereo_match_ex.argtypes = [vp, vp, f32, f32, vp, vp, vp]
+        L.oracle_set_features.argtypes = [vp, vp, i32, vp]
         L.oracle_resize.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32]
         L.oracle_gaussian7.argtypes = [vp, i32, i32, i32, vp, i32]
         L.oracle_fast.argtypes = [vp, i32, i32, i32, i32, vp, i32]
@@ -137,6 +139,19 @@ class OracleExtractor:
         lib().oracle_get_level_keypoints(self._h, level, _p(out), n)
         return out
 
+    def set_features(self, kps: np.ndarray, desc):
+        """Feature injection (oracle_set_features): replace the keypoints and descriptors of
+        the last extraction; the pyramid and the tables stay.  The caller keeps the extractor's
+        border invariant (orb_oracle.h): ComputeStereoMatches bounds none of its reads."""
+        kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+        n = len(kps)
+        desc = np.zeros((0, 32), np.uint8) if desc is None else np.ascontiguousarray(desc, np.uint8)
+        if desc.shape != (n, 32):
+            raise ValueError(f"{n} keypoints with descriptors of shape {desc.shape}")
+        if lib().oracle_set_features(self._h, _p(kps) if n else None, n,
+                                     _p(desc) if n else None) != n:
+            raise RuntimeError("oracle_set_features: nothing extracted on this handle yet")
+
     def tables(self):
         L = self.nlevels
         f = [np.zeros(L, np.float32) for _ in range(4)]
@@ -147,13 +162,24 @@ class OracleExtractor:
                     features_per_level=feats, umax=umax)
 
 
+# oracle_stereo_match_ex's code per left keypoint (orb_oracle.h ORACLE_STEREO_*)
+STEREO_REASONS = ("accepted", "clamped", "no_candidate", "filtered", "dist_high", "sad_at_end",
+                  "delta", "disparity", "median_cut", "window_outside")
+
+
 def stereo_match(left: OracleExtractor, right: OracleExtractor, n_left: int, mbf: float,
-                 mb: float):
-    """Frame::ComputeStereoMatches (src/Frame.cc:496-686) over the two last extractions."""
+                 mb: float, reasons: bool = False):
+    """Frame::ComputeStereoMatches (src/Frame.cc:496-686) over the two last extractions (or
+    the features injected since).  reasons=True also returns the exit each left keypoint took
+    (an index into STEREO_REASONS)."""
     u = np.zeros(n_left, np.float32)
     d = np.zeros(n_left, np.float32)
-    nvalid = lib().oracle_stereo_match(left._h, right._h, mbf, mb, _p(u), _p(d))
-    return u, d, nvalid
+    if not reasons:
+        nvalid = lib().oracle_stereo_match(left._h, right._h, mbf, mb, _p(u), _p(d))
+        return u, d, nvalid
+    why = np.full(n_left, -1, np.int32)
+    nvalid = lib().oracle_stereo_match_ex(left._h, right._h, mbf, mb, _p(u), _p(d), _p(why))
+    return u, d, nvalid, why
 
 
 def resize(src: np.ndarray, dw: int, dh: int, simd: int = 1) -> np.ndarray:

@@ -769,11 +769,13 @@ int DescriptorDistance(const uint8_t* a8, const uint8_t* b8) {
     return dist;
 }
 
-// src/Frame.cc:496-686
+// src/Frame.cc:496-686.  `reason` (optional, one int per left keypoint) records the exit each
+// left keypoint took (the ORACLE_STEREO_* codes of orb_oracle.h); it changes nothing else.
 int ComputeStereoMatches(const Extractor& L, const Extractor& R, float mbf, float mb,
-                         float* mvuRight, float* mvDepth) {
+                         float* mvuRight, float* mvDepth, int* reason) {
     const int N = (int)L.keypoints.size();
     for (int i = 0; i < N; ++i) { mvuRight[i] = -1.0f; mvDepth[i] = -1.0f; }
+    auto why = [&](int iL, int code) { if (reason) reason[iL] = code; };
     const int TH_HIGH = 100, TH_LOW = 50;
     const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
     const int nRows = L.pyr[0].h;
@@ -801,6 +803,7 @@ int ComputeStereoMatches(const Extractor& L, const Extractor& R, float mbf, floa
         const float& vL = kpL.y;
         const float& uL = kpL.x;
         const std::vector<size_t>& vCandidates = vRowIndices[(size_t)vL];
+        why(iL, ORACLE_STEREO_NO_CANDIDATE);
         if (vCandidates.empty()) continue;
         const float minU = uL - maxD;
         const float maxU = uL - minD;
@@ -822,6 +825,8 @@ int ComputeStereoMatches(const Extractor& L, const Extractor& R, float mbf, floa
                 }
             }
         }
+        // TH_HIGH is only left by a candidate that passed the octave and [minU, maxU] filters
+        why(iL, bestDist >= TH_HIGH ? ORACLE_STEREO_FILTERED : ORACLE_STEREO_DIST_HIGH);
         if (bestDist < thOrbDist) {
             const float uR0 = R.keypoints[bestIdxR].x;
             const float scaleFactor = mvInvScaleFactors[kpL.octave];
@@ -840,6 +845,11 @@ int ComputeStereoMatches(const Extractor& L, const Extractor& R, float mbf, floa
             vDists.resize(2 * L5 + 1);
             const float iniu = scaleduR0 + L5 - w;
             const float endu = scaleduR0 + L5 + w + 1;
+            // unreachable for features that keep the extractor's border: a keypoint lies at
+            // least 16 pixels inside its own level, which is more than 12 pixels inside the
+            // levels one octave up and down, so scaleduR0 is in [10, cols - 12) (the window
+            // reads below rely on the same border; nothing here bounds them)
+            why(iL, ORACLE_STEREO_WINDOW_OUTSIDE);
             if (iniu < 0 || endu >= PR.w) continue;
             for (int incR = -L5; incR <= +L5; incR++) {
                 const int xr0 = (int)(scaleduR0 + incR - w);
@@ -858,15 +868,22 @@ int ComputeStereoMatches(const Extractor& L, const Extractor& R, float mbf, floa
                 }
                 vDists[L5 + incR] = dist;
             }
+            why(iL, ORACLE_STEREO_SAD_AT_END);
             if (bestincR == -L5 || bestincR == L5) continue;
             const float dist1 = vDists[L5 + bestincR - 1];
             const float dist2 = vDists[L5 + bestincR];
             const float dist3 = vDists[L5 + bestincR + 1];
             const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
+            // dist2 is the minimum, strictly below dist1 and not above dist3 (exact integers), so
+            // deltaR = (a - b) / (2 (a + b)) with a = dist1 - dist2 > 0, b = dist3 - dist2 >= 0 is
+            // in [-0.5, 0.5] and never NaN: this exit exists in the reference but cannot be taken
+            why(iL, ORACLE_STEREO_DELTA);
             if (deltaR < -1 || deltaR > 1) continue;
             float bestuR = mvScaleFactors[kpL.octave] * ((float)scaleduR0 + (float)bestincR + deltaR);
             float disparity = (uL - bestuR);
+            why(iL, ORACLE_STEREO_DISPARITY);   // (a NaN deltaR would pass the test above and end here)
             if (disparity >= minD && disparity < maxD) {
+                why(iL, disparity <= 0 ? ORACLE_STEREO_CLAMPED : ORACLE_STEREO_ACCEPTED);
                 if (disparity <= 0) {
                     disparity = 0.01;
                     bestuR = uL - 0.01;
@@ -886,6 +903,7 @@ int ComputeStereoMatches(const Extractor& L, const Extractor& R, float mbf, floa
         if (vDistIdx[i].first < thDist) break;
         mvuRight[vDistIdx[i].second] = -1;
         mvDepth[vDistIdx[i].second] = -1;
+        why(vDistIdx[i].second, ORACLE_STEREO_MEDIAN_CUT);
         --valid;
     }
     return valid;
@@ -959,8 +977,20 @@ void oracle_get_tables(void* h, float* scale, float* inv_scale, float* sigma2, f
     }
     for (int i = 0; i < 16; ++i) umax16[i] = e->umax[i];
 }
+int oracle_set_features(void* h, const okp_t* kps, int n, const uint8_t* desc) {
+    auto* e = (Extractor*)h;
+    if (n < 0 || (n > 0 && (!kps || !desc)) || e->pyr.empty() || e->pyr[0].d.empty()) return -1;
+    e->keypoints.resize((size_t)n);
+    if (n > 0) memcpy((void*)e->keypoints.data(), kps, sizeof(okp_t) * (size_t)n);
+    e->descriptors.assign(desc, desc + (size_t)n * 32);
+    return n;
+}
+int oracle_stereo_match_ex(void* hL, void* hR, float mbf, float mb, float* uRight, float* depth,
+                           int* reason) {
+    return ComputeStereoMatches(*(Extractor*)hL, *(Extractor*)hR, mbf, mb, uRight, depth, reason);
+}
 int oracle_stereo_match(void* hL, void* hR, float mbf, float mb, float* uRight, float* depth) {
-    return ComputeStereoMatches(*(Extractor*)hL, *(Extractor*)hR, mbf, mb, uRight, depth);
+    return oracle_stereo_match_ex(hL, hR, mbf, mb, uRight, depth, nullptr);
 }
 void oracle_resize(const uint8_t* src, int sw, int sh, int sstride, uint8_t* dst, int dw, int dh,
                    int simd) {

@@ -65,6 +65,33 @@ void oracle_get_tables(void* h, float* scale, float* inv_scale, float* sigma2, f
 // uRight / depth: N_left floats each (-1 = no match).  Returns number of valid matches.
 int oracle_stereo_match(void* hL, void* hR, float mbf, float mb, float* uRight, float* depth);
 
+// Feature injection: replaces the keypoints and descriptors (n x 32 bytes) of the handle's last
+// extraction; its pyramid and tables stay.  ComputeStereoMatches bounds none of its reads, so
+// injected features must keep what the extractor guarantees: octave in [0, nlevels), at least
+// 16 pixels from every edge of the keypoint's own level (in that level's coordinates) and, for
+// a right keypoint, floor(y - 2s) >= 0 and ceil(y + 2s) <= rows - 1 (s = scale of its octave).
+// Returns n, or -1 for bad arguments or a handle that has extracted nothing.
+int oracle_set_features(void* h, const okp_t* kps, int n, const uint8_t* desc);
+
+// The exit each left keypoint took in ComputeStereoMatches.
+enum {
+    ORACLE_STEREO_ACCEPTED = 0,        // accepted, disparity > 0
+    ORACLE_STEREO_CLAMPED = 1,         // accepted through the disparity <= 0 clamp (Frame.cc:659-663)
+    ORACLE_STEREO_NO_CANDIDATE = 2,    // row without candidates, or maxU < 0
+    ORACLE_STEREO_FILTERED = 3,        // candidates, but none passed the octave / [minU, maxU]
+                                       // filters, or best distance >= TH_HIGH
+    ORACLE_STEREO_DIST_HIGH = 4,       // best distance in [75, 100)
+    ORACLE_STEREO_SAD_AT_END = 5,      // SAD minimum at -L or +L
+    ORACLE_STEREO_DELTA = 6,           // deltaR outside [-1, 1] (never taken: |deltaR| <= 0.5 at a minimum)
+    ORACLE_STEREO_DISPARITY = 7,       // disparity outside [minD, maxD) (a NaN deltaR lands here)
+    ORACLE_STEREO_MEDIAN_CUT = 8,      // accepted, then removed by the median cut
+    ORACLE_STEREO_WINDOW_OUTSIDE = 9   // iniu < 0 || endu >= cols: unreachable for features that
+                                       // keep the extractor's border
+};
+// oracle_stereo_match plus reason[N_left] (may be NULL: then it is oracle_stereo_match).
+int oracle_stereo_match_ex(void* hL, void* hR, float mbf, float mb, float* uRight, float* depth,
+                           int* reason);
+
 // Standalone primitives for unit tests.
 void oracle_resize(const uint8_t* src, int sw, int sh, int sstride, uint8_t* dst, int dw, int dh,
                    int simd);

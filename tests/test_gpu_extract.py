@@ -263,11 +263,12 @@ def test_large_batch_equals_single_images(oracle_mod, orbx_lib, gpu):
 
 
 def test_stereo_split_equals_unsplit(orbx_lib, gpu):
-    """k_stereo splits a pair's left keypoints over up to four workgroups (median in
-    k_stereo_cut) when a call has at most 128 pairs (8 pairs: 4 workgroups each), and keeps one
-    workgroup per pair above that: 136 pairs
-    in one call (one workgroup per pair) give bit for bit the uRight / depth / counts of the
-    same pairs in calls of 8 (split; those are checked against the oracle elsewhere)."""
+    """k_stereo splits a pair's left keypoints over several workgroups when a call has at most
+    128 pairs (the pair's last workgroup to finish takes the median) and keeps one workgroup
+    per pair above that: 136 pairs in one call (k_stereo<1>, one workgroup per pair) give bit
+    for bit the uRight / depth / counts of the same pairs in calls of 8 and of 1 (both
+    k_stereo<8>, 16 workgroups per pair; checked against the oracle elsewhere).  The regimes
+    between (8, 4 and 2 workgroups per pair) are test_gpu_stereo_directed.py's."""
     import torch
     import my_orb_slam2_amd as m
     B, C = 136, 8
@@ -279,9 +280,8 @@ def test_stereo_split_equals_unsplit(orbx_lib, gpu):
     big = m.StereoBatch(B, 1000)
     uR, dep, nv = (t.cpu().numpy() for t in big(Ls, Rs, KITTI_MBF, mb))
     nkp = big.fetch("left")[0]
-    # calls of 8 pairs (4 workgroups each) over all 136, and of one pair (the most workgroups
-    # per pair: the last one to arrive takes the median, include the hand-off's ordering) over
-    # 48 of them
+    # calls of 8 pairs over all 136, and of one pair (the fewest keypoints per workgroup: the
+    # last one to arrive takes the median, include the hand-off's ordering) over 48 of them
     for C, upto in ((8, B), (1, 48)):
         small = m.StereoBatch(C, 1000)
         for c0 in range(0, upto, C):
