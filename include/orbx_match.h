@@ -334,6 +334,18 @@ orbx_status orbx_compute_distinctive_descriptors_device(orbx_matcher* m, const u
                                                         const int32_t* d_off, int32_t npoints,
                                                         int32_t* d_best, void* stream);
 
+/* Which kernel variant a call of the given sizes runs (host only: no device, no handle).
+ * kind: ORBX_VK_BOW_KF_FRAME / ORBX_VK_BOW_KF_KF with n_a / n_b = the feature counts of the
+ * first / second featureset (nq unused); ORBX_VK_INIT with n_a / n_b = the feature counts of
+ * F1 / F2; ORBX_VK_PROJ + an orbx_proj_mode with n_b = the target's feature count and nq the
+ * query count (n_a unused).  Returns 0 for the on-chip variant (SearchByBoW: the second set's
+ * descriptors staged in LDS; claim-mode projections: an owner word per target feature in the
+ * greedy replay; also every kind that has a single variant), 1 for the fallback (descriptors
+ * read from global memory; one query per replay round), or the ORBX_ERR_INVALID /
+ * ORBX_ERR_UNSUPPORTED the entry point itself returns for these sizes. */
+enum { ORBX_VK_BOW_KF_FRAME = 0, ORBX_VK_BOW_KF_KF = 1, ORBX_VK_INIT = 2, ORBX_VK_PROJ = 16 };
+int32_t orbx_matcher_variant(int32_t kind, int32_t n_a, int32_t n_b, int32_t nq);
+
 /* ---- per-kernel timing for the matcher handle ------------------------------------------ */
 typedef enum {
     ORBX_MK_BOW = 0, ORBX_MK_TRIANGULATE, ORBX_MK_PROJ_SEARCH, ORBX_MK_PROJ_RESOLVE,

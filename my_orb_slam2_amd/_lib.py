@@ -127,6 +127,7 @@ SIGNATURES = {
     "orbx_matcher_profile_enable": (_i, [_vp, _i]),
     "orbx_matcher_profile_collect": (_i, [_vp, _vp, _vp]),
     "orbx_match_kernel_name": (ctypes.c_char_p, [_i]),
+    "orbx_matcher_variant": (_i, [_i, _i, _i, _i]),
     # include/orbx_vocab.h
     "orbx_vocabulary_load_text": (_i, [ctypes.c_char_p, _i, ctypes.POINTER(_vp)]),
     "orbx_vocabulary_destroy": (_i, [_vp]),

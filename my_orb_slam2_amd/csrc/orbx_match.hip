@@ -1108,6 +1108,8 @@ static bool bow_blds(const BowLaunch& a) { return bow_lds_raw(a, true) <= MATCH_
 
 size_t bow_lds_bytes(const BowLaunch& a) { return bow_lds_raw(a, bow_blds(a)); }
 
+bool bow_b_in_lds(const BowLaunch& a) { return bow_blds(a); }
+
 hipError_t launch_bow(const BowLaunch& a, hipStream_t st) {
     if (a.njobs <= 0) return hipSuccess;
     const size_t lds = bow_lds_bytes(a);
@@ -1158,6 +1160,8 @@ hipError_t launch_triangulate(const TriLaunch& a, hipStream_t st) {
     hipLaunchKernelGGL(k_triangulate, dim3(a.njobs), dim3(256), tri_lds_bytes(a.db.max_feat), st, a);
     return hipGetLastError();
 }
+
+bool proj_resolve_owner_words(int max_t) { return proj_resolve_parallel(max_t); }
 
 size_t proj_resolve_lds_bytes(int mode, int n_target, int nq) {
     if (mode == PROJ_INIT) return 4 * (32 + 2 * (size_t)n_target + (size_t)nq);

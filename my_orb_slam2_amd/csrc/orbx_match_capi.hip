@@ -265,6 +265,15 @@ orbx_status bow_common(orbx_matcher* m, const orbx_featureset* a, const uint8_t*
     return ORBX_OK;
 }
 
+// The size limits of one projection search (any mode, PROJ_INIT included): shared by the entry
+// points and orbx_matcher_variant.
+orbx_status proj_size_status(int mode, int n_target, int nq) {
+    if (nq < 0 || nq > (1 << 22) || n_target < 0 || n_target > MAX_FEAT) return ORBX_ERR_INVALID;
+    if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, n_target, nq) > MATCH_MAX_LDS)
+        return ORBX_ERR_UNSUPPORTED;
+    return ORBX_OK;
+}
+
 orbx_status proj_common(orbx_matcher* m, int mode, const orbx_featureset* T,
                         const uint8_t* claimed, const uint8_t* qdesc, const orbx_proj_query* q,
                         int nq, const float* inv_sigma2, int nlevels, int orb_dist, int32_t* out,
@@ -274,8 +283,8 @@ orbx_status proj_common(orbx_matcher* m, int mode, const orbx_featureset* T,
     if (!valid_feat(T, false, true)) return ORBX_ERR_INVALID;
     if (mode == ORBX_PROJ_FUSE && (!inv_sigma2 || nlevels <= 0)) return ORBX_ERR_INVALID;
     if (nlevels > MATCH_MAX_LEVELS) return ORBX_ERR_UNSUPPORTED;
-    if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, T->n, nq) > MATCH_MAX_LDS)
-        return ORBX_ERR_UNSUPPORTED;
+    const orbx_status sz = proj_size_status(mode, T->n, nq);
+    if (sz != ORBX_OK) return sz;
     std::lock_guard<std::mutex> lk(m->mu);
     if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
     Packer P(m->staging);
@@ -927,6 +936,27 @@ orbx_status orbx_matcher_profile_collect(orbx_matcher* m, double* total_ms, int6
         m->timer.n[k] = 0;
     }
     return ORBX_OK;
+}
+
+int32_t orbx_matcher_variant(int32_t kind, int32_t n_a, int32_t n_b, int32_t nq) {
+    if (kind == ORBX_VK_BOW_KF_FRAME || kind == ORBX_VK_BOW_KF_KF) {
+        if (n_a < 0 || n_a > MAX_FEAT || n_b < 0 || n_b > MAX_FEAT) return ORBX_ERR_INVALID;
+        BowLaunch L{};   // bow_lds_bytes / bow_b_in_lds read the two bounds and the flavour only
+        L.A.max_feat = n_a;
+        L.B.max_feat = n_b;
+        L.kf_kf = kind == ORBX_VK_BOW_KF_KF;
+        if (bow_lds_bytes(L) > MATCH_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
+        return bow_b_in_lds(L) ? 0 : 1;
+    }
+    if (kind == ORBX_VK_INIT) {
+        if (n_a < 0 || n_a > MAX_FEAT) return ORBX_ERR_INVALID;
+        return proj_size_status(PROJ_INIT, n_b, n_a);   // one query per F1 feature
+    }
+    const int mode = kind - ORBX_VK_PROJ;
+    if (mode < 0 || mode >= ORBX_PROJ_MODE_COUNT) return ORBX_ERR_INVALID;
+    const orbx_status s = proj_size_status(mode, n_b, nq);
+    if (s != ORBX_OK) return s;
+    return (!proj_mode_greedy(mode) || proj_resolve_owner_words(n_b)) ? 0 : 1;
 }
 
 const char* orbx_match_kernel_name(int id) {

@@ -82,6 +82,8 @@ struct ProjLaunch {
 bool proj_mode_greedy(int mode);
 hipError_t launch_bow(const BowLaunch& a, hipStream_t st);
 size_t bow_lds_bytes(const BowLaunch& a);
+// launch_bow's choice: k_bow<true> (B descriptors staged in LDS) or k_bow<false> (global reads)
+bool bow_b_in_lds(const BowLaunch& a);
 hipError_t launch_triangulate(const TriLaunch& a, hipStream_t st);
 size_t tri_lds_bytes(int max_feat);
 // Phase A (window search, static top-2), B (sequential greedy claims), C (rotation filter
@@ -89,6 +91,9 @@ size_t tri_lds_bytes(int max_feat);
 struct KernelTimer;
 hipError_t launch_proj(const ProjLaunch& a, hipStream_t st, KernelTimer* timer);
 size_t proj_resolve_lds_bytes(int mode, int n_target, int nq);
+// k_proj_resolve's choice for a largest target of max_t features: owner words (many queries
+// per round) or, when they do not fit in the LDS, one query per round
+bool proj_resolve_owner_words(int max_t);
 hipError_t prepare_match_kernels();
 // Brute-force Hamming top-2 (orbx_bf.hip): q nq x 32, db ndb x 32 (device); part = scratch of
 // bf_partial_bytes(ndb, nq, chunk) bytes.

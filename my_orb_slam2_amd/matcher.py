@@ -35,6 +35,21 @@ def compute_three_maxima(histo_counts) -> tuple[int, int, int]:
     return tuple(o.value for o in out)
 
 
+# orbx_matcher_variant kinds (include/orbx_match.h)
+VK_BOW_KF_FRAME = 0
+VK_BOW_KF_KF = 1
+VK_INIT = 2
+VK_PROJ = 16          # + an orbx_proj_mode
+VARIANT_ON_CHIP = 0   # B descriptors in LDS / owner words in the claim replay
+VARIANT_FALLBACK = 1  # B descriptors from global memory / one query per replay round
+
+
+def matcher_variant(kind: int, n_a: int = 0, n_b: int = 0, nq: int = 0) -> int:
+    """orbx_matcher_variant: the kernel variant a call of these sizes runs (VARIANT_ON_CHIP /
+    VARIANT_FALLBACK), or the negative status the entry point returns for them.  Host only."""
+    return int(load().orbx_matcher_variant(int(kind), int(n_a), int(n_b), int(nq)))
+
+
 class MatcherParams(ctypes.Structure):
     _fields_ = [("nnratio", ctypes.c_float), ("check_orientation", ctypes.c_int32),
                 ("device", ctypes.c_int32)]

@@ -91,11 +91,25 @@ def test_projection(oracle_mod, orbx_lib, gpu, mode, seed, th):
 
 @pytest.mark.parametrize("mode", [PROJ_FRAME_MAPPOINTS, PROJ_KEYFRAME])
 def test_projection_large_target(oracle_mod, orbx_lib, gpu, mode):
-    """A target of 32000 features: the claim replay runs without the per-feature owner
-    words (one query per round), and dense windows overflow the 8-candidate lists."""
+    """A target of 32000 features: dense windows overflow the 8-candidate lists.  The claim
+    replay still keeps its per-feature owner words at this size (they fit in the LDS up to
+    32688 features); test_projection_max_feat_target runs it without them."""
+    _large_target(mode, 32000, 0)
+
+
+@pytest.mark.parametrize("mode", [PROJ_FRAME_MAPPOINTS, PROJ_KEYFRAME])
+def test_projection_max_feat_target(oracle_mod, orbx_lib, gpu, mode):
+    """A target of MAX_FEAT = 32768 features: the owner words no longer fit and the claim
+    replay decides one query per round."""
+    _large_target(mode, 32768, 1)
+
+
+def _large_target(mode, n2, variant):
+    from my_orb_slam2_amd.matcher import VK_PROJ, matcher_variant
     from oracle import matcher as om
-    f1, f2, t = synth.feature_pair(77, n1=3000, n2=32000, dup_frac=0.1)
+    f1, f2, t = synth.feature_pair(77, n1=3000, n2=n2, dup_frac=0.1)
     q, d = synth.projection_queries(5, f1, f2, t, th=6.0)
+    assert matcher_variant(VK_PROJ + mode, 0, f2.n, len(q)) == variant
     claimed = np.random.default_rng(5).random(f2.n) < 0.1
     m = _matcher(0.8, True)
     n_g, m_g = m.search_by_projection(mode, f2, q, d, claimed, orb_dist=64)

@@ -11,9 +11,9 @@ import numpy as np
 import pytest
 
 from my_orb_slam2_amd import synth
-from my_orb_slam2_amd.features import (PROJ_FRAME_MAPPOINTS, PROJ_FUSE, PROJ_KEYFRAME,
-                                       PROJ_KF_SCW, PROJ_LAST_FRAME, assign_features_to_grid,
-                                       feature_vector)
+from my_orb_slam2_amd.features import (PROJ_FRAME_MAPPOINTS, PROJ_FUSE, PROJ_FUSE_SCW,
+                                       PROJ_KEYFRAME, PROJ_KF_SCW, PROJ_LAST_FRAME, PROJ_SIM3,
+                                       assign_features_to_grid, feature_vector)
 from oracle import matcher as om
 
 f32 = np.float32
@@ -106,39 +106,64 @@ def nodes(fs):
             for j in range(len(fs.fvec.node_id))}
 
 
-def bow_kf_frame_py(kf, valid, f, ratio, check_ori):
-    match = [-1] * f.n
+def bow_py(a, va, b, vb, kf_kf, ratio, check_ori):
+    """SearchByBoW, both flavours (:182-319, :563-696) -> (nmatches, matches, codes): matches
+    per B feature (KF-F) or per A feature (KF-KF); codes: the outcome of every A feature
+    (tests/matcher_cases.py lists them; "+rescan": its static best or second was claimed)."""
+    match = [-1] * (a.n if kf_kf else b.n)
+    taken = [False] * b.n
+    codes = ["skipped"] * a.n
     hist = [[] for _ in range(30)]
     n = 0
-    fn = nodes(f)
-    for nid, kfi in sorted(nodes(kf).items()):
-        if nid not in fn:
+    bn = nodes(b)
+    for nid, la in sorted(nodes(a).items()):
+        if nid not in bn:
             continue
-        for ik in kfi:
-            if not valid[ik]:
+        for ia in la:
+            if not va[ia]:
                 continue
             b1, b2, bi = 256, 256, -1
-            for jf in fn[nid]:
-                if match[jf] >= 0:
+            static = []
+            for jb in bn[nid]:
+                if kf_kf and not vb[jb]:
                     continue
-                d = hd(kf.desc[ik], f.desc[jf])
+                d = hd(a.desc[ia], b.desc[jb])
+                static.append((d, jb))
+                if taken[jb]:
+                    continue
                 if d < b1:
-                    b2, b1, bi = b1, d, jf
+                    b2, b1, bi = b1, d, jb
                 elif d < b2:
                     b2 = d
-            if b1 <= 50 and f32(b1) < f32(ratio) * f32(b2):
-                match[bi] = ik
+            static.sort(key=lambda t: t[0])   # stable: the lower position first among equals
+            sfx = "+rescan" if any(taken[j] for _, j in static[:2]) else ""
+            if bi < 0:
+                codes[ia] = "no_candidate" + sfx
+            elif not (b1 < 50 if kf_kf else b1 <= 50):
+                codes[ia] = "over_threshold" + sfx
+            elif not f32(b1) < f32(ratio) * f32(b2):
+                codes[ia] = "ratio_rejected" + sfx
+            else:
+                codes[ia] = "accepted" + sfx
+                taken[bi] = True
+                match[ia if kf_kf else bi] = bi if kf_kf else ia
                 if check_ori:
-                    hist[rot_bin(kf.keys["angle"][ik], f.keys["angle"][bi])].append(bi)
+                    hist[rot_bin(a.keys["angle"][ia], b.keys["angle"][bi])].append(
+                        (ia if kf_kf else bi, ia))
                 n += 1
     if check_ori:
         t = three_maxima_py([len(h) for h in hist])
-        for b in range(30):
-            if b not in t:
-                for j in hist[b]:
+        for k in range(30):
+            if k not in t:
+                for j, ia in hist[k]:
                     match[j] = -1
+                    codes[ia] = "rotation_removed"
                     n -= 1
-    return n, np.array(match, np.int32)
+    return n, np.array(match, np.int32), codes
+
+
+def bow_kf_frame_py(kf, valid, f, ratio, check_ori):
+    return bow_py(kf, valid, f, None, False, ratio, check_ori)[:2]
 
 
 def epi_ok(kp1, kp2, F, sigma2):
@@ -154,9 +179,14 @@ def epi_ok(kp1, kp2, F, sigma2):
     return float(dsqr) < 3.84 * float(sigma2[kp2["octave"]])
 
 
-def triangulation_py(k1, h1, k2, h2, F, ex, ey, sigma2, scale, only_stereo):
+def triangulation_py(k1, h1, k2, h2, F, ex, ey, sigma2, scale, only_stereo, check_ori=False,
+                     codes=None):
+    """`codes` (a list of k1.n entries, filled in place): the outcome of every KF1 feature."""
     F = np.asarray(F, f32).reshape(9)
     out = {}
+    if codes is None:
+        codes = [None] * k1.n
+    codes[:] = ["skipped"] * k1.n
     n2 = nodes(k2)
     for nid, l1 in sorted(nodes(k1).items()):
         if nid not in n2:
@@ -184,26 +214,45 @@ def triangulation_py(k1, h1, k2, h2, F, ex, ey, sigma2, scale, only_stereo):
                         continue
                 if epi_ok(k1.keys[i1], kp2, F, sigma2):
                     best, bi = d, i2
+            codes[i1] = "accepted" if bi >= 0 else "no_candidate"
             if bi >= 0:
                 out[i1] = bi
+    if check_ori:
+        hist = [[] for _ in range(30)]
+        for i1, bi in out.items():
+            hist[rot_bin(k1.keys["angle"][i1], k2.keys["angle"][bi])].append(i1)
+        t = three_maxima_py([len(h) for h in hist])
+        for k in range(30):
+            if k not in t:
+                for i1 in hist[k]:
+                    del out[i1]
+                    codes[i1] = "rotation_removed"
     pairs = np.array(sorted(out.items()), np.int32).reshape(-1, 2)
     return len(pairs), pairs
 
 
 def area_py(fs, x, y, r, minl, maxl):
+    with np.errstate(all="ignore"):   # non-finite queries are part of the directed cases
+        return _area_py(fs, x, y, r, minl, maxl)
+
+
+def _area_py(fs, x, y, r, minl, maxl):
     g = fs.grid
     x, y, r = f32(x), f32(y), f32(r)
-    fl = lambda v: int(np.floor(v)) if np.isfinite(v) else -2**31
+    # (int)floor(v) / (int)ceil(v) as x86-64 converts: INT_MIN for NaN and out-of-range values
+    x86 = lambda v: int(v) if np.isfinite(v) and -2.0**31 <= v < 2.0**31 else -2**31
+    fl = lambda v: x86(np.floor(v))
+    ce = lambda v: x86(np.ceil(v))
     cx0 = max(0, fl(f32(f32(f32(x - f32(g.min_x)) - r) * f32(g.inv_w))))
     if cx0 >= g.cols:
         return []
-    cx1 = min(g.cols - 1, int(np.ceil(f32(f32(f32(x - f32(g.min_x)) + r) * f32(g.inv_w)))))
+    cx1 = min(g.cols - 1, ce(f32(f32(f32(x - f32(g.min_x)) + r) * f32(g.inv_w))))
     if cx1 < 0:
         return []
     cy0 = max(0, fl(f32(f32(f32(y - f32(g.min_y)) - r) * f32(g.inv_h))))
     if cy0 >= g.rows:
         return []
-    cy1 = min(g.rows - 1, int(np.ceil(f32(f32(f32(y - f32(g.min_y)) + r) * f32(g.inv_h)))))
+    cy1 = min(g.rows - 1, ce(f32(f32(f32(y - f32(g.min_y)) + r) * f32(g.inv_h))))
     if cy1 < 0:
         return []
     check = minl > 0 or maxl >= 0
@@ -223,13 +272,28 @@ def area_py(fs, x, y, r, minl, maxl):
     return out
 
 
+CLAIM_MODES = (PROJ_FRAME_MAPPOINTS, PROJ_KF_SCW, PROJ_LAST_FRAME, PROJ_KEYFRAME)
+PROJ_TH = {PROJ_FRAME_MAPPOINTS: 100, PROJ_KF_SCW: 50, PROJ_LAST_FRAME: 100, PROJ_FUSE: 50,
+           PROJ_FUSE_SCW: 50, PROJ_SIM3: 100}
+
+
 def projection_py(mode, T, q, qdesc, claimed, ratio, check_ori, orb_dist=100, inv_sigma2=None,
-                  qflags=None, prefilter=False):
-    cl = [bool(c) for c in claimed] if claimed is not None else [False] * T.n
+                  qflags=None, prefilter=False, info=None):
+    """The seven projection searches.  `info` (a dict, filled in place): "codes" = the outcome
+    of every query ("+rescan": its static best was claimed by an earlier query of this call);
+    "exhausted" = the claim-mode queries whose list of the 8 best static candidates was
+    truncated and had fewer than two unclaimed entries left at their turn (the replay kernel
+    then re-scans the window); "overwritten" = no-claim queries whose feature a later query
+    took."""
+    pre = [bool(c) for c in claimed] if claimed is not None and mode in CLAIM_MODES else [False] * T.n
+    cl = list(pre)
     out = [-1] * len(q)
+    codes = ["skipped"] * len(q)
+    exhausted, overwritten, holder = [], [], {}
     qbin = {}
     hist = [[] for _ in range(30)]
     n = 0
+    init256 = mode not in (PROJ_FUSE_SCW, PROJ_SIM3)
     for iq, qq in enumerate(q):
         if not qq["radius"] >= 0:
             continue
@@ -237,12 +301,11 @@ def projection_py(mode, T, q, qdesc, claimed, ratio, check_ori, orb_dist=100, in
             cand = area_py(T, qq["u"], qq["v"], qq["radius"], qq["min_level"], qq["max_level"])
         else:
             cand = area_py(T, qq["u"], qq["v"], qq["radius"], -1, -1)
-        bd, bl, bd2, bl2, bi = 256, -1, 256, -1, -1
+        bd, bl, bd2, bl2, bi = (256 if init256 else 2**31 - 1), -1, 256, -1, -1
+        static = []
         for i in cand:
-            if mode in (PROJ_FRAME_MAPPOINTS, PROJ_KF_SCW, PROJ_LAST_FRAME, PROJ_KEYFRAME) and cl[i]:
-                continue
             kp = T.keys[i]
-            if mode in (PROJ_KF_SCW, PROJ_FUSE):
+            if mode in (PROJ_KF_SCW, PROJ_FUSE, PROJ_FUSE_SCW, PROJ_SIM3):
                 if kp["octave"] < qq["pred_level"] - 1 or kp["octave"] > qq["pred_level"]:
                     continue
             if mode in (PROJ_FRAME_MAPPOINTS, PROJ_LAST_FRAME) and T.u_right[i] > 0:
@@ -260,18 +323,35 @@ def projection_py(mode, T, q, qdesc, claimed, ratio, check_ori, orb_dist=100, in
                     if float(f32(e2 * inv_sigma2[kp["octave"]])) > 5.99:
                         continue
             d = hd(qdesc[iq], T.desc[i])
+            if not pre[i] and (d < 256 or not init256):
+                static.append((d, i))
+            if cl[i]:
+                continue
             if d < bd:
                 bd2, bl2, bd, bl, bi = bd, bl, d, int(kp["octave"]), i
             elif d < bd2:
                 bd2, bl2 = d, int(kp["octave"])
-        th = {PROJ_FRAME_MAPPOINTS: 100, PROJ_KF_SCW: 50, PROJ_LAST_FRAME: 100,
-              PROJ_KEYFRAME: orb_dist, PROJ_FUSE: 50}[mode]
-        if bd <= th:
-            if mode == PROJ_FRAME_MAPPOINTS and bl == bl2 and f32(bd) > f32(ratio) * f32(bd2):
-                continue
-            no_claim = qflags is not None and mode != PROJ_KEYFRAME and qflags[iq] & 1
-            if mode != PROJ_FUSE and not no_claim:
+        static.sort(key=lambda t: t[0])   # stable: visiting order among equal distances
+        sfx = "+rescan" if static and cl[static[0][1]] else ""
+        if mode in CLAIM_MODES and len(static) > 8 and sum(not cl[i] for _, i in static[:8]) < 2:
+            exhausted.append(iq)
+        th = orb_dist if mode == PROJ_KEYFRAME else PROJ_TH[mode]
+        if bi < 0:
+            codes[iq] = "no_candidate" + sfx
+        elif bd > th:
+            codes[iq] = "over_threshold" + sfx
+        elif mode == PROJ_FRAME_MAPPOINTS and bl == bl2 and f32(bd) > f32(ratio) * f32(bd2):
+            codes[iq] = "ratio_rejected" + sfx
+        else:
+            codes[iq] = "accepted" + sfx
+            no_claim = qflags is not None and mode in (PROJ_FRAME_MAPPOINTS, PROJ_LAST_FRAME) \
+                and qflags[iq] & 1
+            if bi in holder:
+                overwritten.append(holder.pop(bi))
+            if mode in CLAIM_MODES and not no_claim:
                 cl[bi] = True
+            elif no_claim:
+                holder[bi] = iq
             out[iq] = bi
             n += 1
             if check_ori and mode in (PROJ_LAST_FRAME, PROJ_KEYFRAME):
@@ -282,8 +362,80 @@ def projection_py(mode, T, q, qdesc, claimed, ratio, check_ori, orb_dist=100, in
         for iq, b in qbin.items():
             if b not in t:
                 out[iq] = -1
+                codes[iq] = "rotation_removed"
                 n -= 1
+    if info is not None:
+        info.update(codes=codes, exhausted=exhausted, overwritten=overwritten)
     return n, np.array(out, np.int32)
+
+
+def sim3_py(k1, k2, qdesc1, q12, qdesc2, q21):
+    """SearchBySim3 (:1158-1382): the two projection loops and the agreement check."""
+    _, m1 = projection_py(PROJ_SIM3, k2, q12, qdesc1, None, 0.0, False)
+    _, m2 = projection_py(PROJ_SIM3, k1, q21, qdesc2, None, 0.0, False)
+    out = np.full(len(q12), -1, np.int32)
+    for i1, i2 in enumerate(m1):
+        if i2 >= 0 and i2 < len(m2) and m2[i2] == i1:
+            out[i1] = i2
+    return int((out >= 0).sum()), out
+
+
+def initialization_py(f1, f2, prev, window, ratio, check_ori):
+    """SearchForInitialization (:446-561) -> (nmatches, vnMatches12, codes); `prev` [n1, 2] is
+    updated in place for the matched features."""
+    INF = 2**31 - 1
+    m12, m21, mdist = [-1] * f1.n, [-1] * f2.n, [INF] * f2.n
+    codes = ["skipped"] * f1.n
+    hist = [[] for _ in range(30)]
+    n = 0
+    for i1 in range(f1.n):
+        lvl = int(f1.keys["octave"][i1])
+        if lvl > 0:
+            continue
+        cand = area_py(f2, prev[i1][0], prev[i1][1], f32(window), lvl, lvl)
+        bd, bd2, bi = INF, INF, -1
+        static = (INF, -1)
+        for i2 in cand:
+            d = hd(f1.desc[i1], f2.desc[i2])
+            if d < static[0]:
+                static = (d, i2)
+            if mdist[i2] <= d:
+                continue
+            if d < bd:
+                bd2, bd, bi = bd, d, i2
+            elif d < bd2:
+                bd2 = d
+        sfx = "+rescan" if static[1] >= 0 and mdist[static[1]] <= static[0] else ""
+        if bi < 0:
+            codes[i1] = "no_candidate" + sfx
+        elif bd > 50:
+            codes[i1] = "over_threshold" + sfx
+        elif not f32(bd) < f32(f32(bd2) * f32(ratio)):
+            codes[i1] = "ratio_rejected" + sfx
+        else:
+            codes[i1] = "accepted" + sfx
+            if m21[bi] >= 0:
+                m12[m21[bi]] = -1
+                codes[m21[bi]] = "taken_over"
+                n -= 1
+            m12[i1], m21[bi], mdist[bi] = bi, i1, bd
+            n += 1
+            if check_ori:
+                hist[rot_bin(f1.keys["angle"][i1], f2.keys["angle"][bi])].append(i1)
+    if check_ori:
+        t = three_maxima_py([len(h) for h in hist])
+        for k in range(30):
+            if k not in t:
+                for i1 in hist[k]:
+                    if m12[i1] >= 0:
+                        m12[i1] = -1
+                        codes[i1] = "rotation_removed"
+                        n -= 1
+    for i1 in range(f1.n):
+        if m12[i1] >= 0:
+            prev[i1][0] = f2.keys["x"][m12[i1]]
+            prev[i1][1] = f2.keys["y"][m12[i1]]
+    return n, np.array(m12, np.int32), codes
 
 
 # ---- cross-checks ----------------------------------------------------------------------
@@ -388,7 +540,8 @@ def distinctive_py(desc, off):
         if n == 0:
             out.append(-1)
             continue
-        D = [[hd(rows[i], rows[j]) for j in range(n)] for i in range(n)]
+        bits = np.unpackbits(rows, axis=1).astype(np.int32)
+        D = (bits[:, None, :] != bits[None, :, :]).sum(2).tolist()
         best, bi = None, 0
         for i in range(n):
             med = sorted(D[i])[int(0.5 * (n - 1))]
