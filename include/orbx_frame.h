@@ -120,6 +120,89 @@ orbx_status orbx_cvt_color(const uint8_t* src, int32_t width, int32_t height, si
                            int32_t channels, int32_t rgb, uint8_t* dst, size_t dst_stride,
                            int device);
 
+/* ---- RGB-D frames (System::RGBD): depth at the keypoints, unprojection, the close-point pass ----
+ *
+ * The raw depth image as the sensor delivers it; Tracking::GrabImageRGBD scales it to CV_32F
+ * (src/Tracking.cc:244-245) with mDepthMapFactor, here `factor`: the value after
+ * Tracking.cc:159-163, i.e. already inverted (1.0f / 5000 for TUM). */
+typedef enum {
+    ORBX_DEPTH_U16 = 0, /* CV_16U: d = (float)raw * factor (cvtScale_<ushort, float, float>) */
+    ORBX_DEPTH_F32 = 1  /* CV_32F: d = raw * factor when fabs(factor - 1.0f) > 1e-5, else raw */
+} orbx_depth_type;
+
+/* Frame::ComputeStereoFromRGBD (src/Frame.cc:689-710) with the depth scaling in front of it
+ * (Tracking.cc:244-245) applied to the sampled pixels only: for every keypoint slot i < d_n[f] of
+ * frame f (layout of orbx_batch_view), d = the depth image of frame f (at d_depth +
+ * f*image_stride bytes, rows row_stride bytes apart) at row (int)kps[i].y, column (int)kps[i].x
+ * (C++ truncation, x86 cvttss2si for NaN / out of range); d > 0: d_depth_out[i] = d,
+ * d_u_right[i] = kps_un[i].x - mbf / d; otherwise (0, -0.0f, negative, NaN) both are -1.  A
+ * pixel outside [0, width) x [0, height) gives -1 / -1 (the reference reads out of bounds).
+ * Slots past d_n[f] are left untouched.  d_kps_un may equal d_kps.  Depth types other than
+ * orbx_depth_type's: ORBX_ERR_UNSUPPORTED. */
+orbx_status orbx_compute_stereo_from_rgbd_batch_device(
+    const void* d_depth, int32_t depth_type, size_t row_stride, size_t image_stride,
+    int32_t width, int32_t height, float factor, float mbf, const orbx_keypoint* d_kps,
+    const orbx_keypoint* d_kps_un, int32_t kp_stride, const int32_t* d_n, int32_t batch,
+    float* d_u_right, float* d_depth_out, void* stream);
+/* One frame, host arrays (copied to the device for the call). */
+orbx_status orbx_compute_stereo_from_rgbd(const void* depth, int32_t depth_type,
+                                          size_t row_stride, int32_t width, int32_t height,
+                                          float factor, float mbf, const orbx_keypoint* kps,
+                                          const orbx_keypoint* kps_un, int32_t n,
+                                          float* u_right, float* depth_out, int device);
+/* The same fused with Frame::UndistortKeyPoints (Frame.cc:429-459): one launch and one read of
+ * each keypoint; d_kps_un is written too (a copy when dist[0] == 0; in place allowed).  Outputs
+ * are bitwise those of orbx_undistort_keypoints_batch_device followed by the call above. */
+orbx_status orbx_rgbd_frame_geometry_batch_device(
+    const float* K4, const float* dist, int32_t ndist, const void* d_depth, int32_t depth_type,
+    size_t row_stride, size_t image_stride, int32_t width, int32_t height, float factor,
+    float mbf, const orbx_keypoint* d_kps, int32_t kp_stride, const int32_t* d_n, int32_t batch,
+    orbx_keypoint* d_kps_un, float* d_u_right, float* d_depth_out, void* stream);
+
+/* Frame::UnprojectStereo (src/Frame.cc:713-727) / KeyFrame::UnprojectStereo (src/KeyFrame.cc:
+ * 629-645) for every slot i < d_n[f]: z = d_depth[i] > 0: x = ((u - cx) * z) * invfx, y likewise
+ * (invfx = 1.0f / fx), d_x3d[3i..] = Rwc * (x, y, z) + Ow in cv::gemm's small-matrix form (float
+ * products summed left to right, + Ow in double, rounded to float), Rwc the transpose of
+ * d_poses[f].Rcw; d_valid[i] (optional) = 1.  z <= 0: d_valid[i] = 0, the point is untouched.
+ * d_keys: mvKeysUn for a Frame, mvKeys for a KeyFrame. */
+orbx_status orbx_unproject_stereo_batch_device(const orbx_frame_pose* d_poses,
+                                               const orbx_keypoint* d_keys, int32_t kp_stride,
+                                               const float* d_depth, const int32_t* d_n,
+                                               int32_t batch, float* d_x3d, uint8_t* d_valid,
+                                               void* stream);
+orbx_status orbx_unproject_stereo(const orbx_frame_pose* pose, const orbx_keypoint* keys,
+                                  const float* depth, int32_t n, float* x3d, uint8_t* valid,
+                                  int device);
+
+/* The close-point pass Tracking::UpdateLastFrame (src/Tracking.cc:862-912) and
+ * Tracking::CreateNewKeyFrame (:1164-1217) both write, with NeedNewKeyFrame's close counts
+ * (:1076-1092), one workgroup per frame.  d_has_point[i] (optional; absent = none): slot i holds
+ * a MapPoint with Observations() >= 1.  d_tracked[i] (optional; absent = none):
+ * mvpMapPoints[i] && !mvbOutlier[i].  Per frame f (arrays indexed like the keypoints):
+ *   d_order[j], j < M      the slots with z > 0 in ascending (z, index) order: std::sort on
+ *                          vector<pair<float,int>>
+ *   d_counts[4f..]         {M, V, nTrackedClose, nNonTrackedClose}: M = #{z > 0}; V = the sorted
+ *                          entries the loop body runs on before its break (z > th_depth &&
+ *                          nPoints > min_points; the reference's min_points is 100); the close
+ *                          counts take 0 < z < th_depth
+ *   d_create[j], j < V     !has_point[order[j]] (bCreateNew)
+ *   d_x3d[3j..], j < V     UnprojectStereo(order[j])
+ * Entries past M (order) and V (create, x3d) are untouched.  th_depth = +inf gives V = M
+ * (StereoInitialization, Tracking.cc:570-585, takes every z > 0).  kp_stride (n for the host
+ * form) above 8192: ORBX_ERR_UNSUPPORTED. */
+orbx_status orbx_close_points_batch_device(const orbx_frame_pose* d_poses,
+                                           const orbx_keypoint* d_keys, int32_t kp_stride,
+                                           const float* d_depth, const uint8_t* d_has_point,
+                                           const uint8_t* d_tracked, const int32_t* d_n,
+                                           int32_t batch, float th_depth, int32_t min_points,
+                                           int32_t* d_order, int32_t* d_counts,
+                                           uint8_t* d_create, float* d_x3d, void* stream);
+orbx_status orbx_close_points(const orbx_frame_pose* pose, const orbx_keypoint* keys,
+                              const float* depth, const uint8_t* has_point,
+                              const uint8_t* tracked, int32_t n, float th_depth,
+                              int32_t min_points, int32_t* order, int32_t* counts,
+                              uint8_t* create, float* x3d, int device);
+
 #ifdef __cplusplus
 }
 #endif

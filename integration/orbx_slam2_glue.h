@@ -5,6 +5,10 @@
 //   ComputeStereoMatches(F)         replaces Frame::ComputeStereoMatches (src/Frame.cc:496-686)
 //   ExtractStereo(F, imL, imR)      replaces Frame.cc:89-102 (both ExtractORB threads + the
 //                                   stereo match) by one two-image submission
+//   ComputeStereoFromRGBD(F, imDepth, depthFactor)
+//                                   replaces Frame::ComputeStereoFromRGBD (src/Frame.cc:689-710)
+//                                   and the whole-image imDepth.convertTo in front of it
+//                                   (src/Tracking.cc:244-245)
 //   OrbxView / BuildView(f, view)   the orbx_featureset of a Frame / KeyFrame (mFeatVec, mGrid)
 //   SearchByBoW(m, pKF, F, out)     ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (:182-319)
 //
@@ -21,9 +25,17 @@
 #include <opencv2/core/core.hpp>
 
 #include "orbx.h"
+#include "orbx_frame.h"
 #include "orbx_match.h"
 
 namespace orbx_glue {
+
+// CV_16U (core/hal/interface.h: 2), also where a cv header without 16-bit types is in use
+#ifdef CV_16U
+constexpr int kCv16U = CV_16U;
+#else
+constexpr int kCv16U = 2;
+#endif
 
 inline void check(orbx_status s, const char* what) {
     if (s != ORBX_OK) throw std::runtime_error(std::string(what) + ": " + orbx_last_error());
@@ -105,6 +117,39 @@ int ExtractStereo(Frame& F, const cv::Mat& imLeft, const cv::Mat& imRight) {
     F.mvuRight.assign(o.u_right, o.u_right + o.n[0]);
     F.mvDepth.assign(o.depth, o.depth + o.n[0]);
     return o.n_valid;
+}
+
+// Frame.cc:689-710 on the RAW depth image (CV_16U or CV_32F, any row step): mvuRight / mvDepth
+// from mvKeys (the sampled pixel) and mvKeysUn (uRight).  depthFactor is mDepthMapFactor after
+// Tracking.cc:159-163.  The caller drops Tracking.cc:244-245: only the ~N sampled pixels are
+// scaled, with the rounding of convertTo.  A keypoint outside the image gives -1 / -1 (the
+// reference reads out of bounds).  Returns the number of features with depth.
+template <class Frame>
+int ComputeStereoFromRGBD(Frame& F, const void* depth, orbx_depth_type type, size_t step,
+                          int cols, int rows, float depthFactor, int device = 0) {
+    static_assert(sizeof(*F.mvKeys.data()) == sizeof(orbx_keypoint), "cv::KeyPoint layout");
+    if ((int)F.mvKeys.size() != F.N || (int)F.mvKeysUn.size() != F.N)
+        throw std::invalid_argument("ComputeStereoFromRGBD: mvKeys / mvKeysUn do not hold N keypoints");
+    F.mvuRight = std::vector<float>((size_t)F.N, -1.0f);
+    F.mvDepth = std::vector<float>((size_t)F.N, -1.0f);
+    check(orbx_compute_stereo_from_rgbd(depth, type, step, cols, rows, depthFactor, F.mbf,
+                                        reinterpret_cast<const orbx_keypoint*>(F.mvKeys.data()),
+                                        reinterpret_cast<const orbx_keypoint*>(F.mvKeysUn.data()),
+                                        F.N, F.mvuRight.data(), F.mvDepth.data(), device),
+          "orbx_compute_stereo_from_rgbd");
+    int nvalid = 0;
+    for (float d : F.mvDepth) nvalid += d > 0;
+    return nvalid;
+}
+
+template <class Frame>
+int ComputeStereoFromRGBD(Frame& F, const cv::Mat& imDepth, float depthFactor, int device = 0) {
+    if (imDepth.type() != kCv16U && imDepth.type() != CV_32F)
+        throw std::invalid_argument("ComputeStereoFromRGBD: CV_16U or CV_32F depth expected");
+    return ComputeStereoFromRGBD(F, imDepth.data,
+                                 imDepth.type() == kCv16U ? ORBX_DEPTH_U16 : ORBX_DEPTH_F32,
+                                 (size_t)imDepth.step, imDepth.cols, imDepth.rows, depthFactor,
+                                 device);
 }
 
 // CSR copies of mFeatVec (after ComputeBoW) and mGrid (after AssignFeaturesToGrid); the other

@@ -7,6 +7,8 @@ Host-side mirror of the reference's operator interface for this path:
 * ``ORBmatcher`` — ORB_SLAM2::ORBmatcher descriptor matching (include/ORBmatcher.h)
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
+* ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
+  (src/Frame.cc:132-236; ComputeStereoFromRGBD :689-710, UnprojectStereo :713-727)
 
 Everything routes through liborbx.so (include/orbx.h).  There is no CPU fallback.
 """
@@ -18,7 +20,8 @@ from .extractor import (ORBextractor, compute_stereo_matches, compute_stereo_mat
 from .matcher import ORBmatcher, descriptor_distance
 from .vocabulary import Vocabulary, bow_score_l1
 from .kfdb import KeyFrameDatabase
+from .tracking import MonoTrackBatch, RGBDTrackBatch
 
 __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_stereo_matches_batch_device",
            "extract_stereo", "descriptor_distance",
-           "StereoBatch", "Vocabulary", "bow_score_l1", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "load"]
+           "StereoBatch", "MonoTrackBatch", "RGBDTrackBatch", "Vocabulary", "bow_score_l1", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "load"]

@@ -162,6 +162,17 @@ SIGNATURES = {
     "orbx_cvt_color_device": (_i, [_vp, _i, _i, _sz, _i, _i, _vp, _sz, _vp]),
     "orbx_is_in_frustum_batch_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp]),
     "orbx_is_in_frustum": (_i, [_vp, _vp, _i, _vp, _f, _f, _vp, _vp, _i]),
+    "orbx_compute_stereo_from_rgbd_batch_device": (_i, [_vp, _i, _sz, _sz, _i, _i, _f, _f, _vp,
+                                                        _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "orbx_compute_stereo_from_rgbd": (_i, [_vp, _i, _sz, _i, _i, _f, _f, _vp, _vp, _i, _vp, _vp,
+                                           _i]),
+    "orbx_rgbd_frame_geometry_batch_device": (_i, [_vp, _vp, _i, _vp, _i, _sz, _sz, _i, _i, _f,
+                                                   _f, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "orbx_unproject_stereo_batch_device": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "orbx_unproject_stereo": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i]),
+    "orbx_close_points_batch_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _vp,
+                                            _vp, _vp, _vp, _vp]),
+    "orbx_close_points": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

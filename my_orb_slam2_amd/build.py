@@ -192,3 +192,33 @@ def build_matcher_test(force: bool = False, verbose: bool = False, cpu: bool = F
     subprocess.run(cmd, check=True)
     os.replace(str(out) + ".tmp", out)
     return out
+
+
+# ---- the RGB-D glue compiled as ORB-SLAM2 would include it (tests/native/rgbd_test.cpp) ---------
+RGBD_SRC = PKG.parent / "tests" / "native" / "rgbd_test.cpp"
+RGBD_BIN = PKG.parent / "tests" / "native" / "rgbd_test"
+
+
+def build_rgbd_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on integration/orbx_slam2_glue.h (ComputeStereoFromRGBD) with the cv stand-in and
+    tests/native/rgbd_standin.h, linked to the in-tree liborbx.so."""
+    root = PKG.parent
+    native = root / "tests" / "native"
+    deps = ([RGBD_SRC, native / "rgbd_standin.h"] + sorted((root / "include").glob("*.h")) +
+            sorted((root / "integration").glob("*.h")) +
+            sorted((native / "cv_standin").rglob("*.hpp")))
+    newest = max(p.stat().st_mtime for p in deps)
+    if not force and RGBD_BIN.exists() and RGBD_BIN.stat().st_mtime >= newest:
+        return RGBD_BIN
+    build(verbose=verbose)
+    # -ffp-contract=off: the reference's float statements restated in the program, as written
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(root / "integration"),
+           "-I" + str(native / "cv_standin"), "-I" + str(native), str(RGBD_SRC), "-L" + str(PKG),
+           "-lorbx", "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
+           "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd", "-pthread", "-o", str(RGBD_BIN) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(RGBD_BIN) + ".tmp", RGBD_BIN)
+    return RGBD_BIN

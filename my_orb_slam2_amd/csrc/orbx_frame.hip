@@ -8,9 +8,18 @@
 //                  fill, then each cell sorted by feature index (the push_back order)
 //   k_frustum      one lane per (frame, local MapPoint): Frame::isInFrustum + PredictScale, the
 //                  SearchByProjection query of every MapPoint in view (SearchLocalPoints)
+//   k_rgbd_depth   one lane per (frame, keypoint): Frame::ComputeStereoFromRGBD on the raw depth
+//                  image (the samples are scaled, not the image), optionally fused with the
+//                  undistortion of the keypoint
+//   k_unproject    one lane per (frame, keypoint): Frame / KeyFrame::UnprojectStereo
+//   k_close_points one workgroup per frame: the depth-sorted close-point pass of
+//                  Tracking::UpdateLastFrame / CreateNewKeyFrame, a bitonic sort of
+//                  (depth bits << 32 | index) keys in LDS, and NeedNewKeyFrame's close counts
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
+#include <cstring>
 #include <mutex>
 #include <vector>
 
@@ -268,6 +277,220 @@ __global__ __launch_bounds__(256) void k_frustum(const orbx_frame_pose* __restri
     }
 }
 
+// ---- RGB-D: depth at the keypoints, unprojection, the close-point pass -------------------------
+
+// (int) of a float as x86 cvttss2si: INT_MIN when out of range or NaN
+__device__ __forceinline__ int x86_trunc(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
+}
+
+// Frame::ComputeStereoFromRGBD (src/Frame.cc:689-710) for keypoint slot i of frame f, on the raw
+// depth image: imDepth.at<float>(v, u) truncates the raw keypoint to a pixel; the sample is
+// converted as Tracking.cc:244-245 converts the image (u16: (float)raw * factor; f32: raw *
+// factor when `scale`, else raw).  A pixel outside the image gives -1 / -1.  FUSED: the
+// undistorted keypoint is computed here (Frame::UndistortKeyPoints) and written to kps_un.
+template <bool FUSED>
+__global__ __launch_bounds__(256) void k_rgbd_depth(UndistParams P, int copy,
+                                                    const uint8_t* __restrict__ img, int type,
+                                                    int scale, size_t row_stride,
+                                                    size_t image_stride, int width, int height,
+                                                    float factor, float mbf,
+                                                    const orbx_keypoint* kps,
+                                                    const orbx_keypoint* kps_un_in,
+                                                    orbx_keypoint* kps_un_out, int kp_stride,
+                                                    const int32_t* __restrict__ d_n,
+                                                    float* __restrict__ u_right,
+                                                    float* __restrict__ depth_out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (i >= min(d_n[f], kp_stride)) return;
+    const size_t k = (size_t)f * kp_stride + i;
+    const orbx_keypoint kp = kps[k];
+    float xu;
+    if (FUSED) {
+        orbx_keypoint ku = kp;
+        if (!copy) undistort_pt(P, kp.x, kp.y, ku.x, ku.y);
+        kps_un_out[k] = ku;
+        xu = ku.x;
+    } else {
+        xu = kps_un_in[k].x;
+    }
+    const int col = x86_trunc(kp.x), row = x86_trunc(kp.y);
+    float d = -1.0f;
+    if (col >= 0 && col < width && row >= 0 && row < height) {
+        const uint8_t* p = img + (size_t)f * image_stride + (size_t)row * row_stride;
+        if (type == ORBX_DEPTH_U16) {
+            d = __fmul_rn((float)((const uint16_t*)p)[col], factor);
+        } else {
+            d = ((const float*)p)[col];
+            if (scale) d = __fmul_rn(d, factor);
+        }
+    }
+    if (d > 0.0f) {
+        depth_out[k] = d;
+        u_right[k] = __fsub_rn(xu, __fdiv_rn(mbf, d));
+    } else {
+        depth_out[k] = -1.0f;
+        u_right[k] = -1.0f;
+    }
+}
+
+// Frame::UnprojectStereo (src/Frame.cc:713-727) / KeyFrame::UnprojectStereo (KeyFrame.cc:629-645)
+// for z > 0: x = (u - cx) * z * invfx, y likewise, x3D = Rwc * (x, y, z) + Ow as cv::gemm's
+// small-matrix path evaluates it (see frustum_query); Rwc is the transpose of F.Rcw.
+__device__ __forceinline__ void unproject_pt(const orbx_frame_pose& F, float u, float v, float z,
+                                             float* out) {
+    const float invfx = __fdiv_rn(1.0f, F.fx), invfy = __fdiv_rn(1.0f, F.fy);
+    const float c[3] = {__fmul_rn(__fmul_rn(__fsub_rn(u, F.cx), z), invfx),
+                        __fmul_rn(__fmul_rn(__fsub_rn(v, F.cy), z), invfy), z};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        float t = __fmul_rn(F.Rcw[r], c[0]);
+        t = __fadd_rn(t, __fmul_rn(F.Rcw[3 + r], c[1]));
+        t = __fadd_rn(t, __fmul_rn(F.Rcw[6 + r], c[2]));
+        out[r] = (float)((double)t + (double)F.Ow[r]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_unproject(const orbx_frame_pose* __restrict__ poses,
+                                                   const orbx_keypoint* __restrict__ keys,
+                                                   int kp_stride, const float* __restrict__ depth,
+                                                   const int32_t* __restrict__ d_n,
+                                                   float* __restrict__ x3d,
+                                                   uint8_t* __restrict__ valid) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, f = blockIdx.y;
+    if (i >= min(d_n[f], kp_stride)) return;
+    const size_t k = (size_t)f * kp_stride + i;
+    const float z = depth[k];
+    if (z > 0.0f) {
+        float o[3];
+        unproject_pt(poses[f], keys[k].x, keys[k].y, z, o);
+        x3d[3 * k] = o[0];
+        x3d[3 * k + 1] = o[1];
+        x3d[3 * k + 2] = o[2];
+    }
+    if (valid) valid[k] = z > 0.0f;
+}
+
+#define CLOSE_MAX_FEATURES 8192
+
+// The close-point pass of Tracking::UpdateLastFrame (src/Tracking.cc:862-912) and
+// CreateNewKeyFrame (:1164-1217), with NeedNewKeyFrame's close counts (:1080-1089); one
+// workgroup per frame.  The features with z > 0 are sorted by (z, index), which is std::sort on
+// vector<pair<float,int>>: a positive float orders as its bit pattern, so the u64 key
+// (bits(z) << 32 | index) orders the pairs; slots without depth get the all-ones key and sink to
+// the end.  A bitonic network over the next power of two >= n sorts them in LDS (8 bytes per
+// slot, 64 KiB at 8192 features).  The loop body runs on the first V sorted entries: the break
+// (z > th_depth && nPoints > min_points, nPoints = j + 1 in both branches) fires at the first
+// position j >= max(L, min_points) with L = #{!(z > th_depth)}, so V = min(M, max(L,
+// min_points) + 1).
+__global__ __launch_bounds__(1024) void k_close_points(
+    const orbx_frame_pose* __restrict__ poses, const orbx_keypoint* __restrict__ keys,
+    int kp_stride, const float* __restrict__ depth, const uint8_t* __restrict__ has_point,
+    const uint8_t* __restrict__ tracked, const int32_t* __restrict__ d_n, int n_one,
+    float th_depth, int min_points, int32_t* __restrict__ order, int32_t* __restrict__ counts,
+    uint8_t* __restrict__ create, float* __restrict__ x3d) {
+    extern __shared__ unsigned long long skey[];
+    const int tid = threadIdx.x, f = blockIdx.x;
+    const int n = d_n ? min(max(d_n[f], 0), kp_stride) : n_one;
+    const size_t base = (size_t)f * kp_stride;
+    int ps = 2;   // sorted span: the power of two >= n
+    while (ps < n) ps <<= 1;
+    int* red = (int*)skey;   // {M, L, nTrackedClose, nNonTrackedClose} before the keys move in
+    if (tid < 4) red[tid] = 0;
+    __syncthreads();
+    int m = 0, l = 0, tc = 0, ntc = 0;
+    for (int i = tid; i < n; i += 1024) {
+        const float z = depth[base + i];
+        if (z > 0.0f) {
+            ++m;
+            if (!(z > th_depth)) ++l;
+            if (z < th_depth) {
+                if (tracked && tracked[base + i]) ++tc;
+                else ++ntc;
+            }
+        }
+    }
+    if (m) atomicAdd(&red[0], m);
+    if (l) atomicAdd(&red[1], l);
+    if (tc) atomicAdd(&red[2], tc);
+    if (ntc) atomicAdd(&red[3], ntc);
+    __syncthreads();
+    const int M = red[0], L = red[1], nTC = red[2], nNTC = red[3];
+    __syncthreads();
+    for (int i = tid; i < ps; i += 1024) {
+        unsigned long long key = ~0ull;
+        if (i < n) {
+            const float z = depth[base + i];
+            if (z > 0.0f) key = ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)i;
+        }
+        skey[i] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= ps; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (ps >> 1); t += 1024) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const unsigned long long a = skey[lo], b = skey[hi];
+                if ((a > b) == ((lo & k) == 0)) {
+                    skey[lo] = b;
+                    skey[hi] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    const int first = max(L, min_points);
+    const int V = first >= M ? M : first + 1;
+    if (tid == 0) {
+        counts[4 * f] = M;
+        counts[4 * f + 1] = V;
+        counts[4 * f + 2] = nTC;
+        counts[4 * f + 3] = nNTC;
+    }
+    const orbx_frame_pose& F = poses[f];
+    for (int j = tid; j < M; j += 1024) {
+        const unsigned long long key = skey[j];
+        const int i = (int)(unsigned)key;
+        order[base + j] = i;
+        if (j < V) {
+            create[base + j] = has_point ? !has_point[base + i] : 1;
+            float o[3];
+            unproject_pt(F, keys[base + i].x, keys[base + i].y, __uint_as_float((unsigned)(key >> 32)), o);
+            x3d[3 * (base + j)] = o[0];
+            x3d[3 * (base + j) + 1] = o[1];
+            x3d[3 * (base + j) + 2] = o[2];
+        }
+    }
+}
+
+// Dynamic LDS of k_close_points for a frame capacity; 64 KiB needs no more than the default
+// limit, the opt-in is made once per device all the same (a no-op where it is the default).
+size_t close_lds(int cap) {
+    size_t p = 2;
+    while (p < (size_t)cap) p <<= 1;
+    return p * sizeof(unsigned long long);
+}
+bool close_prepare() {
+    static std::mutex mu;
+    static bool have[ORBX_MAX_DEVICES] = {};
+    int dev = 0;
+    if (!HIPOK(hipGetDevice(&dev)) || dev < 0 || dev >= ORBX_MAX_DEVICES) return false;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!have[dev])
+        have[dev] = HIPOK(hipFuncSetAttribute((const void*)k_close_points,
+                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                              (int)close_lds(CLOSE_MAX_FEATURES)));
+    return have[dev];
+}
+
+// The depth image arguments of the RGB-D entry points: element size, or 0 when refused.
+int depth_elem(int type) { return type == ORBX_DEPTH_U16 ? 2 : type == ORBX_DEPTH_F32 ? 4 : 0; }
+// Tracking.cc:244: the image is scaled when fabs(mDepthMapFactor - 1.0f) > 1e-5 or it is not
+// CV_32F already
+int depth_scales(int type, float factor) {
+    return type != ORBX_DEPTH_F32 || std::fabs(factor - 1.0f) > 1e-5;
+}
+
 // Device staging of the host-array entry points: a pool of (device, non-blocking stream,
 // growable buffer) slots taken for the length of one call.  After warm-up a call allocates
 // nothing, and it waits only for its own stream, never for the device (the reference calls
@@ -515,6 +738,223 @@ orbx_status orbx_is_in_frustum(const orbx_frame_pose* frame, const orbx_map_poin
         s = ORBX_ERR_DEVICE;
     if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
     if (s == ORBX_OK && nvisible) *nvisible = cnt;
+    return s;
+}
+
+// ---- RGB-D ---------------------------------------------------------------------------------
+
+static orbx_status rgbd_args(int32_t depth_type, size_t row_stride, size_t image_stride,
+                             int32_t width, int32_t height, int32_t kp_stride, int32_t batch) {
+    const int es = depth_elem(depth_type);
+    if (!es) return ORBX_ERR_UNSUPPORTED;
+    if (width <= 0 || height <= 0 || kp_stride < 0 || batch < 0 || batch > 65535 ||
+        row_stride < (size_t)width * es || row_stride % es || image_stride % es ||
+        (batch > 1 && image_stride < row_stride * (size_t)height))
+        return ORBX_ERR_INVALID;
+    return ORBX_OK;
+}
+
+orbx_status orbx_compute_stereo_from_rgbd_batch_device(
+    const void* d_depth, int32_t depth_type, size_t row_stride, size_t image_stride,
+    int32_t width, int32_t height, float factor, float mbf, const orbx_keypoint* d_kps,
+    const orbx_keypoint* d_kps_un, int32_t kp_stride, const int32_t* d_n, int32_t batch,
+    float* d_u_right, float* d_depth_out, void* stream) {
+    const orbx_status a = rgbd_args(depth_type, row_stride, image_stride, width, height,
+                                    kp_stride, batch);
+    if (a != ORBX_OK) return a;
+    if (batch == 0 || kp_stride == 0) return ORBX_OK;
+    if (!d_depth || !d_kps || !d_kps_un || !d_n || !d_u_right || !d_depth_out ||
+        ((uintptr_t)d_depth & (depth_elem(depth_type) - 1)))
+        return ORBX_ERR_INVALID;
+    hipLaunchKernelGGL(k_rgbd_depth<false>, dim3((kp_stride + 255) / 256, batch), dim3(256), 0,
+                       (hipStream_t)stream, UndistParams{}, 1, (const uint8_t*)d_depth,
+                       depth_type, depth_scales(depth_type, factor), row_stride, image_stride,
+                       width, height, factor, mbf, d_kps, d_kps_un, (orbx_keypoint*)nullptr,
+                       kp_stride, d_n, d_u_right, d_depth_out);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+orbx_status orbx_rgbd_frame_geometry_batch_device(
+    const float* K4, const float* dist, int32_t ndist, const void* d_depth, int32_t depth_type,
+    size_t row_stride, size_t image_stride, int32_t width, int32_t height, float factor,
+    float mbf, const orbx_keypoint* d_kps, int32_t kp_stride, const int32_t* d_n, int32_t batch,
+    orbx_keypoint* d_kps_un, float* d_u_right, float* d_depth_out, void* stream) {
+    UndistParams P;
+    if (!make_params(K4, dist, ndist, P)) return ORBX_ERR_INVALID;
+    const orbx_status a = rgbd_args(depth_type, row_stride, image_stride, width, height,
+                                    kp_stride, batch);
+    if (a != ORBX_OK) return a;
+    if (batch == 0 || kp_stride == 0) return ORBX_OK;
+    if (!d_depth || !d_kps || !d_kps_un || !d_n || !d_u_right || !d_depth_out ||
+        ((uintptr_t)d_depth & (depth_elem(depth_type) - 1)))
+        return ORBX_ERR_INVALID;
+    const int copy = dist[0] == 0.0f;   // Frame.cc:431: mvKeysUn = mvKeys
+    hipLaunchKernelGGL(k_rgbd_depth<true>, dim3((kp_stride + 255) / 256, batch), dim3(256), 0,
+                       (hipStream_t)stream, P, copy, (const uint8_t*)d_depth, depth_type,
+                       depth_scales(depth_type, factor), row_stride, image_stride, width, height,
+                       factor, mbf, d_kps, (const orbx_keypoint*)nullptr, d_kps_un, kp_stride,
+                       d_n, d_u_right, d_depth_out);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+orbx_status orbx_compute_stereo_from_rgbd(const void* depth, int32_t depth_type,
+                                          size_t row_stride, int32_t width, int32_t height,
+                                          float factor, float mbf, const orbx_keypoint* kps,
+                                          const orbx_keypoint* kps_un, int32_t n,
+                                          float* u_right, float* depth_out, int device) {
+    const orbx_status a = rgbd_args(depth_type, row_stride, 0, width, height, n, 1);
+    if (a != ORBX_OK) return a;
+    if (n == 0) return ORBX_OK;
+    if (!depth || !kps || !kps_un || !u_right || !depth_out) return ORBX_ERR_INVALID;
+    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t tight = (size_t)width * depth_elem(depth_type), kb = sizeof(orbx_keypoint) * (size_t)n;
+    const size_t o_img = 0, o_k = al(tight * height), o_ku = o_k + al(kb), o_n = o_ku + al(kb),
+                 o_ur = o_n + 256, o_d = o_ur + al(4 * (size_t)n), end = o_d + 4 * (size_t)n;
+    ScratchLease L(device);
+    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    hipStream_t st = L.s->st;
+    uint8_t* d = L.s->buf.as<uint8_t>();
+    orbx_status s = ORBX_OK;
+    if (!HIPOK(hipMemcpy2DAsync(d + o_img, tight, depth, row_stride, tight, height,
+                                hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_k, kps, kb, hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_ku, kps_un, kb, hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_n, &n, 4, hipMemcpyHostToDevice, st)))
+        s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK)
+        s = orbx_compute_stereo_from_rgbd_batch_device(
+            d + o_img, depth_type, tight, 0, width, height, factor, mbf,
+            (const orbx_keypoint*)(d + o_k), (const orbx_keypoint*)(d + o_ku), n,
+            (const int32_t*)(d + o_n), 1, (float*)(d + o_ur), (float*)(d + o_d), st);
+    if (s == ORBX_OK &&
+        (!HIPOK(hipMemcpyAsync(u_right, d + o_ur, 4 * (size_t)n, hipMemcpyDeviceToHost, st)) ||
+         !HIPOK(hipMemcpyAsync(depth_out, d + o_d, 4 * (size_t)n, hipMemcpyDeviceToHost, st))))
+        s = ORBX_ERR_DEVICE;
+    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
+    return s;
+}
+
+orbx_status orbx_unproject_stereo_batch_device(const orbx_frame_pose* d_poses,
+                                               const orbx_keypoint* d_keys, int32_t kp_stride,
+                                               const float* d_depth, const int32_t* d_n,
+                                               int32_t batch, float* d_x3d, uint8_t* d_valid,
+                                               void* stream) {
+    if (batch < 0 || kp_stride < 0 || batch > 65535) return ORBX_ERR_INVALID;
+    if (batch == 0 || kp_stride == 0) return ORBX_OK;
+    if (!d_poses || !d_keys || !d_depth || !d_n || !d_x3d) return ORBX_ERR_INVALID;
+    hipLaunchKernelGGL(k_unproject, dim3((kp_stride + 255) / 256, batch), dim3(256), 0,
+                       (hipStream_t)stream, d_poses, d_keys, kp_stride, d_depth, d_n, d_x3d,
+                       d_valid);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+orbx_status orbx_unproject_stereo(const orbx_frame_pose* pose, const orbx_keypoint* keys,
+                                  const float* depth, int32_t n, float* x3d, uint8_t* valid,
+                                  int device) {
+    if (!pose || n < 0 || (n > 0 && (!keys || !depth || !x3d))) return ORBX_ERR_INVALID;
+    if (n == 0) return ORBX_OK;
+    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t kb = sizeof(orbx_keypoint) * (size_t)n;
+    const size_t o_f = 0, o_n = al(sizeof(orbx_frame_pose)), o_k = o_n + 256, o_d = o_k + al(kb),
+                 o_x = o_d + al(4 * (size_t)n), o_v = o_x + al(12 * (size_t)n),
+                 end = o_v + (size_t)n;
+    ScratchLease L(device);
+    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    hipStream_t st = L.s->st;
+    uint8_t* d = L.s->buf.as<uint8_t>();
+    orbx_status s = ORBX_OK;
+    // x3d goes up first: slots without depth come back as the caller left them
+    if (!HIPOK(hipMemcpyAsync(d + o_f, pose, sizeof(*pose), hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_n, &n, 4, hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_k, keys, kb, hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_d, depth, 4 * (size_t)n, hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_x, x3d, 12 * (size_t)n, hipMemcpyHostToDevice, st)))
+        s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK)
+        s = orbx_unproject_stereo_batch_device(
+            (const orbx_frame_pose*)(d + o_f), (const orbx_keypoint*)(d + o_k), n,
+            (const float*)(d + o_d), (const int32_t*)(d + o_n), 1, (float*)(d + o_x), d + o_v, st);
+    if (s == ORBX_OK &&
+        (!HIPOK(hipMemcpyAsync(x3d, d + o_x, 12 * (size_t)n, hipMemcpyDeviceToHost, st)) ||
+         (valid && !HIPOK(hipMemcpyAsync(valid, d + o_v, (size_t)n, hipMemcpyDeviceToHost, st)))))
+        s = ORBX_ERR_DEVICE;
+    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
+    return s;
+}
+
+orbx_status orbx_close_points_batch_device(const orbx_frame_pose* d_poses,
+                                           const orbx_keypoint* d_keys, int32_t kp_stride,
+                                           const float* d_depth, const uint8_t* d_has_point,
+                                           const uint8_t* d_tracked, const int32_t* d_n,
+                                           int32_t batch, float th_depth, int32_t min_points,
+                                           int32_t* d_order, int32_t* d_counts,
+                                           uint8_t* d_create, float* d_x3d, void* stream) {
+    if (batch < 0 || kp_stride < 0) return ORBX_ERR_INVALID;
+    if (kp_stride > CLOSE_MAX_FEATURES) return ORBX_ERR_UNSUPPORTED;
+    if (batch == 0) return ORBX_OK;
+    if (!d_poses || !d_n || !d_counts ||
+        (kp_stride > 0 && (!d_keys || !d_depth || !d_order || !d_create || !d_x3d)))
+        return ORBX_ERR_INVALID;
+    if (!close_prepare()) return ORBX_ERR_DEVICE;
+    hipLaunchKernelGGL(k_close_points, dim3(batch), dim3(1024), close_lds(kp_stride),
+                       (hipStream_t)stream, d_poses, d_keys, kp_stride, d_depth, d_has_point,
+                       d_tracked, d_n, 0, th_depth, min_points, d_order, d_counts, d_create,
+                       d_x3d);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+orbx_status orbx_close_points(const orbx_frame_pose* pose, const orbx_keypoint* keys,
+                              const float* depth, const uint8_t* has_point,
+                              const uint8_t* tracked, int32_t n, float th_depth,
+                              int32_t min_points, int32_t* order, int32_t* counts,
+                              uint8_t* create, float* x3d, int device) {
+    if (!pose || !counts || n < 0 || (n > 0 && (!keys || !depth || !order || !create || !x3d)))
+        return ORBX_ERR_INVALID;
+    if (n > CLOSE_MAX_FEATURES) return ORBX_ERR_UNSUPPORTED;
+    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t kb = sizeof(orbx_keypoint) * (size_t)n, nb = al((size_t)n);
+    const size_t o_f = 0, o_n = al(sizeof(orbx_frame_pose)), o_c = o_n + 256, o_k = o_c + 256,
+                 o_d = o_k + al(kb), o_h = o_d + al(4 * (size_t)n), o_t = o_h + nb,
+                 o_o = o_t + nb, o_cr = o_o + al(4 * (size_t)n), o_x = o_cr + nb,
+                 end = o_x + 12 * (size_t)n;
+    ScratchLease L(device);
+    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    hipStream_t st = L.s->st;
+    uint8_t* d = L.s->buf.as<uint8_t>();
+    orbx_status s = ORBX_OK;
+    if (!HIPOK(hipMemcpyAsync(d + o_f, pose, sizeof(*pose), hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_n, &n, 4, hipMemcpyHostToDevice, st)) ||
+        (n > 0 &&
+         (!HIPOK(hipMemcpyAsync(d + o_k, keys, kb, hipMemcpyHostToDevice, st)) ||
+          !HIPOK(hipMemcpyAsync(d + o_d, depth, 4 * (size_t)n, hipMemcpyHostToDevice, st)) ||
+          (has_point &&
+           !HIPOK(hipMemcpyAsync(d + o_h, has_point, (size_t)n, hipMemcpyHostToDevice, st))) ||
+          (tracked &&
+           !HIPOK(hipMemcpyAsync(d + o_t, tracked, (size_t)n, hipMemcpyHostToDevice, st))))))
+        s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK)
+        s = orbx_close_points_batch_device(
+            (const orbx_frame_pose*)(d + o_f), (const orbx_keypoint*)(d + o_k), n,
+            (const float*)(d + o_d), has_point ? d + o_h : nullptr, tracked ? d + o_t : nullptr,
+            (const int32_t*)(d + o_n), 1, th_depth, min_points, (int32_t*)(d + o_o),
+            (int32_t*)(d + o_c), d + o_cr, (float*)(d + o_x), st);
+    int32_t c[4] = {0, 0, 0, 0};
+    if (s == ORBX_OK && (!HIPOK(hipMemcpyAsync(c, d + o_c, 16, hipMemcpyDeviceToHost, st)) ||
+                         !HIPOK(hipStreamSynchronize(st))))
+        s = ORBX_ERR_DEVICE;
+    // only what the pass wrote comes back: order[0, M), create / x3d [0, V)
+    if (s == ORBX_OK && c[0] > 0 &&
+        !HIPOK(hipMemcpyAsync(order, d + o_o, 4 * (size_t)c[0], hipMemcpyDeviceToHost, st)))
+        s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK && c[1] > 0 &&
+        (!HIPOK(hipMemcpyAsync(create, d + o_cr, (size_t)c[1], hipMemcpyDeviceToHost, st)) ||
+         !HIPOK(hipMemcpyAsync(x3d, d + o_x, 12 * (size_t)c[1], hipMemcpyDeviceToHost, st))))
+        s = ORBX_ERR_DEVICE;
+    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK) std::memcpy(counts, c, sizeof(c));
     return s;
 }
 

@@ -309,3 +309,137 @@ def is_in_frustum_batch_device(d_frames, nframes: int, d_mps, d_mp_off, max_mps:
     check("orbx_is_in_frustum_batch_device", load().orbx_is_in_frustum_batch_device(
         ptr(d_frames), int(nframes), ptr(d_mps), ptr(d_mp_off), int(max_mps), ptr(d_skip),
         float(viewing_cos_limit), float(th), ptr(d_q), ptr(d_nvisible), ctypes.c_void_p(stream)))
+
+
+# ---- RGB-D frames (include/orbx_frame.h) -----------------------------------------------------
+
+# orbx_depth_type
+DEPTH_U16 = 0
+DEPTH_F32 = 1
+CLOSE_MAX_FEATURES = 8192   # orbx_close_points*: features per frame sorted on chip
+
+
+def _depth_type(img) -> int:
+    dt = img.dtype if isinstance(img, np.ndarray) else str(img.dtype).replace("torch.", "")
+    if dt == np.uint16 or dt in ("uint16", "int16"):   # torch carries u16 bits in int16 too
+        return DEPTH_U16
+    if dt == np.float32 or dt == "float32":
+        return DEPTH_F32
+    raise ValueError(f"depth image of {dt}: uint16 or float32 expected")
+
+
+def compute_stereo_from_rgbd(depth_img: np.ndarray, factor: float, mbf: float, keys: np.ndarray,
+                             keys_un: np.ndarray | None = None, depth_type: int | None = None,
+                             device: int = 0):
+    """Frame::ComputeStereoFromRGBD (src/Frame.cc:689-710) with Tracking.cc:244-245's scaling on
+    the sampled pixels: (mvuRight, mvDepth) from the raw depth image (H x W uint16 or float32,
+    any row stride), mvKeys and mvKeysUn (None: mvKeys)."""
+    from ._lib import check, load, ptr
+    if depth_img.ndim != 2 or depth_img.strides[1] != depth_img.itemsize:
+        raise ValueError("expected an H x W depth image with contiguous rows")
+    k = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+    ku = k if keys_un is None else np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+    if len(ku) != len(k):
+        raise ValueError("keys and keys_un differ in length")
+    h, w = depth_img.shape
+    ur = np.zeros(len(k), np.float32)
+    de = np.zeros(len(k), np.float32)
+    t = _depth_type(depth_img) if depth_type is None else int(depth_type)
+    check("orbx_compute_stereo_from_rgbd", load().orbx_compute_stereo_from_rgbd(
+        ptr(depth_img), t, depth_img.strides[0], w, h, float(np.float32(factor)),
+        float(np.float32(mbf)), ptr(k), ptr(ku), len(k), ptr(ur), ptr(de), device))
+    return ur, de
+
+
+def compute_stereo_from_rgbd_batch_device(d_depth_img, depth_type: int, row_stride: int,
+                                          image_stride: int, width: int, height: int,
+                                          factor: float, mbf: float, d_keys, d_keys_un,
+                                          kp_stride: int, d_n, batch: int, d_u_right, d_depth,
+                                          stream: int = 0):
+    """The same for `batch` frames laid out like orbx_batch_view (device tensors; strides in
+    bytes): fills d_u_right / d_depth [batch][kp_stride]."""
+    from ._lib import check, load, ptr
+    check("orbx_compute_stereo_from_rgbd_batch_device",
+          load().orbx_compute_stereo_from_rgbd_batch_device(
+              ptr(d_depth_img), int(depth_type), int(row_stride), int(image_stride), int(width),
+              int(height), float(np.float32(factor)), float(np.float32(mbf)), ptr(d_keys),
+              ptr(d_keys_un), int(kp_stride), ptr(d_n), int(batch), ptr(d_u_right), ptr(d_depth),
+              ctypes.c_void_p(stream)))
+
+
+def rgbd_frame_geometry_batch_device(K4, dist, d_depth_img, depth_type: int, row_stride: int,
+                                     image_stride: int, width: int, height: int, factor: float,
+                                     mbf: float, d_keys, kp_stride: int, d_n, batch: int,
+                                     d_keys_un, d_u_right, d_depth, stream: int = 0):
+    """UndistortKeyPoints + ComputeStereoFromRGBD in one launch: d_keys_un, d_u_right and
+    d_depth from the raw keypoints and the raw depth images."""
+    from ._lib import check, load, ptr
+    k = np.ascontiguousarray(K4, np.float32)
+    d = np.ascontiguousarray(dist, np.float32)
+    check("orbx_rgbd_frame_geometry_batch_device", load().orbx_rgbd_frame_geometry_batch_device(
+        ptr(k), ptr(d), len(d), ptr(d_depth_img), int(depth_type), int(row_stride),
+        int(image_stride), int(width), int(height), float(np.float32(factor)),
+        float(np.float32(mbf)), ptr(d_keys), int(kp_stride), ptr(d_n), int(batch),
+        ptr(d_keys_un), ptr(d_u_right), ptr(d_depth), ctypes.c_void_p(stream)))
+
+
+def unproject_stereo(frame: np.ndarray, keys: np.ndarray, depth: np.ndarray, x3d=None,
+                     device: int = 0):
+    """Frame::UnprojectStereo (src/Frame.cc:713-727; KeyFrame.cc:629-645 with mvKeys) for every
+    feature: (x3d [n, 3], valid [n]); rows without depth keep the values of `x3d` (zeros)."""
+    from ._lib import check, load, ptr
+    fr = np.ascontiguousarray(frame, FRAME_POSE_DTYPE).reshape(())
+    k = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+    z = np.ascontiguousarray(depth, np.float32)
+    out = (np.zeros((len(k), 3), np.float32) if x3d is None
+           else np.ascontiguousarray(x3d, np.float32).reshape(len(k), 3).copy())
+    valid = np.zeros(len(k), np.uint8)
+    check("orbx_unproject_stereo", load().orbx_unproject_stereo(
+        ptr(fr), ptr(k), ptr(z), len(k), ptr(out), ptr(valid), device))
+    return out, valid
+
+
+def unproject_stereo_batch_device(d_poses, d_keys, kp_stride: int, d_depth, d_n, batch: int,
+                                  d_x3d, d_valid=None, stream: int = 0):
+    """UnprojectStereo for `batch` frames on device tensors (d_x3d [batch][kp_stride][3])."""
+    from ._lib import check, load, ptr
+    check("orbx_unproject_stereo_batch_device", load().orbx_unproject_stereo_batch_device(
+        ptr(d_poses), ptr(d_keys), int(kp_stride), ptr(d_depth), ptr(d_n), int(batch),
+        ptr(d_x3d), ptr(d_valid), ctypes.c_void_p(stream)))
+
+
+def close_points(frame: np.ndarray, keys: np.ndarray, depth: np.ndarray, th_depth: float,
+                 has_point=None, tracked=None, min_points: int = 100, out=None,
+                 device: int = 0):
+    """The close-point pass of Tracking::UpdateLastFrame / CreateNewKeyFrame (src/Tracking.cc:
+    862-912, 1164-1217) with NeedNewKeyFrame's counts (:1080-1089) for one frame: returns
+    (order [n], counts {M, V, nTrackedClose, nNonTrackedClose}, create [n], x3d [n, 3]); only
+    order[:M], create[:V] and x3d[:V] are written (`out` = (order, create, x3d) to write into)."""
+    from ._lib import check, load, ptr
+    fr = np.ascontiguousarray(frame, FRAME_POSE_DTYPE).reshape(())
+    k = np.ascontiguousarray(keys, KEYPOINT_DTYPE)
+    z = np.ascontiguousarray(depth, np.float32)
+    n = len(k)
+    hp = None if has_point is None else np.ascontiguousarray(has_point, np.uint8)
+    tr = None if tracked is None else np.ascontiguousarray(tracked, np.uint8)
+    if out is None:
+        out = (np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros((n, 3), np.float32))
+    order, create, x3d = out
+    counts = np.zeros(4, np.int32)
+    check("orbx_close_points", load().orbx_close_points(
+        ptr(fr), ptr(k), ptr(z), ptr(hp), ptr(tr), n, float(np.float32(th_depth)),
+        int(min_points), ptr(order), ptr(counts), ptr(create), ptr(x3d), device))
+    return order, counts, create, x3d
+
+
+def close_points_batch_device(d_poses, d_keys, kp_stride: int, d_depth, d_has_point, d_tracked,
+                              d_n, batch: int, th_depth: float, d_order, d_counts, d_create,
+                              d_x3d, min_points: int = 100, stream: int = 0):
+    """The close-point pass for `batch` frames on device tensors: d_order [batch][kp_stride]
+    int32, d_counts [batch][4] int32, d_create [batch][kp_stride] uint8, d_x3d
+    [batch][kp_stride][3] float32; d_has_point / d_tracked may be None."""
+    from ._lib import check, load, ptr
+    check("orbx_close_points_batch_device", load().orbx_close_points_batch_device(
+        ptr(d_poses), ptr(d_keys), int(kp_stride), ptr(d_depth), ptr(d_has_point),
+        ptr(d_tracked), ptr(d_n), int(batch), float(np.float32(th_depth)), int(min_points),
+        ptr(d_order), ptr(d_counts), ptr(d_create), ptr(d_x3d), ctypes.c_void_p(stream)))

@@ -24,9 +24,10 @@ import numpy as np
 
 from ._lib import KEYPOINT_DTYPE, check
 from .extractor import ORBextractor
-from .features import (FRAME_GRID_COLS, FRAME_GRID_ROWS, PROJ_FRAME_MAPPOINTS, PROJ_QUERY_DTYPE,
-                       FeatureSetC, assign_grid_batch_device, image_bounds,
-                       is_in_frustum_batch_device, undistort_keypoints_batch_device)
+from .features import (CLOSE_MAX_FEATURES, FRAME_GRID_COLS, FRAME_GRID_ROWS, PROJ_FRAME_MAPPOINTS,
+                       PROJ_QUERY_DTYPE, FeatureSetC, _depth_type, assign_grid_batch_device,
+                       close_points_batch_device, image_bounds, is_in_frustum_batch_device,
+                       rgbd_frame_geometry_batch_device, undistort_keypoints_batch_device)
 from .matcher import ORBmatcher
 
 
@@ -127,3 +128,84 @@ class MonoTrackBatch:
         nkp, _, desc = self.ext.batch_fetch(0, self.batch)
         ku = self.keys_un.cpu().numpy().view(KEYPOINT_DTYPE).reshape(self.batch, self.kp_cap)
         return nkp, ku, desc
+
+
+class RGBDTrackBatch(MonoTrackBatch):
+    """The RGB-D front-end on top of the mono one.  Per frame, the reference's RGB-D Tracking
+    adds (src/Tracking.cc:208-260, the RGB-D Frame constructor src/Frame.cc:132-184):
+
+      imDepth.convertTo(CV_32F, mDepthMapFactor)   Tracking.cc:244-245 (applied here to the
+                                                   sampled pixels, not to the image)
+      Frame::ComputeStereoFromRGBD                 Frame.cc:689-710: mvuRight, mvDepth
+      Frame::UnprojectStereo + the close-point pass  Frame.cc:713-727; Tracking.cc:862-912,
+                                                   1164-1217 and the counts of :1080-1089
+
+    ``frames(images, depth)`` runs the extraction, then undistortion and depth sampling in one
+    launch (orbx_rgbd_frame_geometry_batch_device), then the grid; ``u_right`` / ``depth`` are
+    [B, kp_cap] device tensors and the featureset carries u_right, so the projection searches
+    (search_by_projection_batch_device, LAST_FRAME / FUSE) see it.  ``depth_factor`` is
+    mDepthMapFactor after Tracking.cc:159-163 (already inverted: 1/5000 for TUM)."""
+
+    def __init__(self, batch: int, width: int, height: int, K4, dist, mbf: float,
+                 depth_factor: float = 1.0, th_depth: float = float("inf"), **kw):
+        import torch
+        super().__init__(batch, width, height, K4, dist, **kw)
+        if self.kp_cap > CLOSE_MAX_FEATURES:
+            raise ValueError(f"{self.kp_cap} keypoint slots per frame: the close-point pass "
+                             f"sorts at most {CLOSE_MAX_FEATURES}")
+        self.mbf = float(np.float32(mbf))
+        self.depth_factor = float(np.float32(depth_factor))
+        self.th_depth = float(np.float32(th_depth))
+        kc = self.kp_cap
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        self.u_right = torch.full((batch, kc), -1.0, **f32)
+        self.depth = torch.full((batch, kc), -1.0, **f32)
+        self.order = torch.zeros((batch, kc), dtype=torch.int32, device=self.dev)
+        self.counts = torch.zeros((batch, 4), dtype=torch.int32, device=self.dev)
+        self.create = torch.zeros((batch, kc), dtype=torch.uint8, device=self.dev)
+        self.x3d = torch.zeros((batch, kc, 3), **f32)
+
+    def _featureset(self):
+        v = super()._featureset()
+        self.c.u_right = self.u_right.data_ptr()
+        return v
+
+    def frames(self, images, depth, stream: int = 0):
+        """Frame construction for [B, H, W] uint8 images and their [B, H, W] raw depth maps
+        (uint16 -- or int16 holding the same bits -- or float32 device tensors, rows and
+        images at any stride)."""
+        B, H, W = images.shape
+        if B != self.batch or (W, H) != (self.width, self.height):
+            raise ValueError("batch shape differs from the prepared one")
+        if tuple(depth.shape) != (B, H, W) or depth.stride(2) != 1:
+            raise ValueError("depth maps must be [B, H, W] with contiguous rows")
+        dtype = _depth_type(depth)
+        es = depth.element_size()
+        self.ext.extract_batch_device(images, stream)
+        v = self._featureset()
+        rgbd_frame_geometry_batch_device(
+            self.K4, self.dist, depth, dtype, depth.stride(1) * es, depth.stride(0) * es, W, H,
+            self.depth_factor, self.mbf, v.kps, self.kp_cap, v.nkp, B, self.keys_un,
+            self.u_right, self.depth, stream)
+        assign_grid_batch_device(self.keys_un, self.kp_cap, v.nkp, B, self.bounds,
+                                 self.grid_off, self.grid_feat, stream=stream)
+        return v
+
+    def close_points(self, d_poses, d_has_point=None, d_tracked=None, th_depth=None,
+                     min_points: int = 100, stream: int = 0):
+        """The close-point pass of every frame of the last ``frames`` call with the poses
+        d_poses (FRAME_POSE_DTYPE records, device): fills ``order``, ``counts`` ({M, V,
+        nTrackedClose, nNonTrackedClose}), ``create`` and ``x3d``.  d_has_point / d_tracked:
+        [B, kp_cap] byte masks or None."""
+        v = self.ext.batch_view()
+        close_points_batch_device(
+            d_poses, self.keys_un, self.kp_cap, self.depth, d_has_point, d_tracked, v.nkp,
+            self.batch, self.th_depth if th_depth is None else th_depth, self.order,
+            self.counts, self.create, self.x3d, min_points, stream)
+        return self.order, self.counts, self.create, self.x3d
+
+    def fetch_stereo(self):
+        """Host copies (u_right [B, kp_cap], depth [B, kp_cap]) of the last ``frames`` call."""
+        import torch
+        torch.cuda.synchronize(self.dev)
+        return self.u_right.cpu().numpy(), self.depth.cpu().numpy()
