@@ -74,6 +74,23 @@ orbx_status orbx_kfdb_detect_loop(orbx_kfdb* db, const uint32_t* qwords, const d
 /* Per-kernel time of the last detect call (ms): the database scan and the selection. */
 orbx_status orbx_kfdb_last_timing(const orbx_kfdb* db, double* scan_ms, double* select_ms);
 
+/* Test / diagnostic read-back of the per-slot arrays, for the first n slots (n <= the slot
+ * count): what the last detect call that launched its kernels left in common (shared words,
+ * connected slots included), score ((float)L1 score of every alive slot), first (query
+ * position of the smallest shared word, INT_MAX without one), acc / best (accScore and
+ * pBestKF of the slots in lScoreAndMatch, -1 elsewhere; written only when some unconnected
+ * slot shared a word), and the current state (mRelocScore).  Waits for the database's stream
+ * and holds its mutex; a NULL output is skipped.  ORBX_ERR_STATE before the first detect call
+ * that reached the device. */
+orbx_status orbx_kfdb_debug_read(orbx_kfdb* db, int32_t* common, float* score, int32_t* first,
+                                 float* state, float* acc, int32_t* best, int32_t n);
+
+/* The compile-time limits (host only, no handle; a NULL output is skipped): query words and
+ * connected keyframes per detect call (more: ORBX_ERR_UNSUPPORTED), retained entries the
+ * selection sorts on chip (more: ORBX_ERR_UNSUPPORTED), covisibles per slot (more at create:
+ * ORBX_ERR_INVALID). */
+orbx_status orbx_kfdb_limits(int32_t* qmax, int32_t* excl_max, int32_t* rcap, int32_t* kmax);
+
 #ifdef __cplusplus
 }
 #endif

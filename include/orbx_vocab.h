@@ -64,6 +64,9 @@ orbx_status orbx_bow_db_score_device(const uint32_t* d_qword, const double* d_qv
                                      int32_t nkf, const int32_t* d_kf_off,
                                      const uint32_t* d_word, const double* d_val,
                                      int32_t* d_common, float* d_score, void* stream);
+/* The largest nq orbx_bow_db_score* takes (the query lives in LDS; one more word gives
+ * ORBX_ERR_UNSUPPORTED).  Host only; it evaluates the launcher's own size expression. */
+int32_t orbx_bow_db_score_max_query(void);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,7 @@
 #include <climits>
 #include <cstring>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/orbx_kfdb.h"
@@ -521,7 +522,12 @@ orbx_status orbx_kfdb_add(orbx_kfdb* db, const uint32_t* words, const double* va
     db->off.push_back((int32_t)db->words.size());
     db->alive.push_back(1);
     db->cov.insert(db->cov.end(), (size_t)db->prm.covisibles, -1);
-    if (slot) *slot = (int32_t)db->alive.size() - 1;
+    // the empty row must reach the device: the buffers are not cleared, and after clear() this
+    // slot number still holds the previous database's row there
+    const int32_t s = (int32_t)db->alive.size() - 1;
+    db->cov_lo = std::min(db->cov_lo, s);
+    db->cov_hi = std::max(db->cov_hi, s);
+    if (slot) *slot = s;
     return ORBX_OK;
 }
 
@@ -589,6 +595,32 @@ orbx_status orbx_kfdb_detect_loop(orbx_kfdb* db, const uint32_t* qwords, const d
                                   int32_t nq, const int32_t* connected, int32_t nc,
                                   float min_score, int32_t* cand, int32_t cap, int32_t* ncand) {
     return detect(db, true, qwords, qvalues, nq, connected, nc, min_score, cand, cap, ncand);
+}
+
+orbx_status orbx_kfdb_debug_read(orbx_kfdb* db, int32_t* common, float* score, int32_t* first,
+                                 float* state, float* acc, int32_t* best, int32_t n) {
+    if (!db || n < 0) return ORBX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(db->mu);
+    if ((size_t)n > db->alive.size()) return ORBX_ERR_INVALID;
+    if (n == 0) return ORBX_OK;
+    if ((size_t)n > db->dev_slots) return ORBX_ERR_STATE;   // nothing uploaded yet
+    if (!HIPOK(hipSetDevice(db->prm.device)) || !HIPOK(hipStreamSynchronize(db->stream)))
+        return ORBX_ERR_DEVICE;
+    const std::pair<void*, const DevBuf*> rd[] = {
+        {common, &db->d_common}, {score, &db->d_score}, {first, &db->d_first},
+        {state, &db->d_state},   {acc, &db->d_acc},     {best, &db->d_best}};
+    for (const auto& r : rd)
+        if (r.first && !HIPOK(hipMemcpy(r.first, r.second->p, 4 * (size_t)n, hipMemcpyDeviceToHost)))
+            return ORBX_ERR_DEVICE;
+    return ORBX_OK;
+}
+
+orbx_status orbx_kfdb_limits(int32_t* qmax, int32_t* excl_max, int32_t* rcap, int32_t* kmax) {
+    if (qmax) *qmax = QMAX;
+    if (excl_max) *excl_max = EXCL_MAX;
+    if (rcap) *rcap = RCAP;
+    if (kmax) *kmax = KMAX;
+    return ORBX_OK;
 }
 
 orbx_status orbx_kfdb_last_timing(const orbx_kfdb* db, double* scan_ms, double* select_ms) {

@@ -131,6 +131,10 @@ __global__ __launch_bounds__(256) void k_bow_score(const uint32_t* __restrict__ 
     }
 }
 
+// k_bow_score's dynamic LDS: query words | query weights | 64 terms per wave
+size_t bow_score_lds(size_t nq) { return ((4 * nq + 7) & ~(size_t)7) + 8 * (nq + 256); }
+constexpr size_t BOW_SCORE_LDS_MAX = 64 * 1024;
+
 }  // namespace
 
 struct orbx_vocabulary {
@@ -346,8 +350,8 @@ orbx_status orbx_bow_db_score_device(const uint32_t* d_qword, const double* d_qv
     if (nq < 0 || nkf < 0 || (nkf > 0 && (!d_kf_off || !d_common || !d_score)) ||
         (nq > 0 && (!d_qword || !d_qval)))
         return ORBX_ERR_INVALID;
-    const size_t lds = ((4 * (size_t)nq + 7) & ~(size_t)7) + 8 * ((size_t)nq + 256);
-    if (lds > 64 * 1024) return ORBX_ERR_UNSUPPORTED;   // query BowVector up to ~5400 words
+    const size_t lds = bow_score_lds((size_t)nq);
+    if (lds > BOW_SCORE_LDS_MAX) return ORBX_ERR_UNSUPPORTED;   // orbx_bow_db_score_max_query
     if (nkf == 0) return ORBX_OK;
     hipLaunchKernelGGL(k_bow_score, dim3((nkf + 3) / 4), dim3(256), lds, (hipStream_t)stream,
                        d_qword, d_qval, nq, nkf, d_kf_off, d_word, d_val, d_common, d_score);
@@ -396,6 +400,15 @@ orbx_status orbx_bow_db_score(const uint32_t* qword, const double* qval, int32_t
     }
     buf.release();
     return s;
+}
+
+int32_t orbx_bow_db_score_max_query(void) {
+    int32_t lo = 0, hi = (int32_t)(BOW_SCORE_LDS_MAX / 8);   // bow_score_lds ascends with nq
+    while (lo < hi) {
+        const int32_t mid = lo + (hi - lo + 1) / 2;
+        if (bow_score_lds((size_t)mid) <= BOW_SCORE_LDS_MAX) lo = mid; else hi = mid - 1;
+    }
+    return lo;
 }
 
 double orbx_bow_score_l1(const uint32_t* w1, const double* v1, int32_t n1, const uint32_t* w2,

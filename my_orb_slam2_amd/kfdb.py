@@ -107,6 +107,40 @@ class KeyFrameDatabase:
         return self._result(self._L.orbx_kfdb_detect_loop, "orbx_kfdb_detect_loop", self._h,
                             ptr(w), ptr(v), len(w), ptr(c), len(c), float(minScore))
 
+    def debug_read(self, n: int | None = None):
+        """orbx_kfdb_debug_read for the first n slots (default: all): dict of common / first /
+        best (int32) and score / state / acc (float32) as the last detect call left them."""
+        n = len(self) if n is None else int(n)
+        i32 = {k: np.zeros(n, np.int32) for k in ("common", "first", "best")}
+        f32 = {k: np.zeros(n, np.float32) for k in ("score", "state", "acc")}
+        check("orbx_kfdb_debug_read", self._L.orbx_kfdb_debug_read(
+            self._h, ptr(i32["common"]), ptr(f32["score"]), ptr(i32["first"]), ptr(f32["state"]),
+            ptr(f32["acc"]), ptr(i32["best"]), n))
+        return dict(i32, **f32)
+
+    @staticmethod
+    def limits():
+        """orbx_kfdb_limits: dict of the compile-time QMAX, EXCL_MAX, RCAP and KMAX."""
+        v = [ctypes.c_int32() for _ in range(4)]
+        check("orbx_kfdb_limits", load().orbx_kfdb_limits(*[ctypes.byref(x) for x in v]))
+        return dict(zip(("QMAX", "EXCL_MAX", "RCAP", "KMAX"), (x.value for x in v)))
+
+    def detect_raw(self, bow, connected=None, min_score: float = 0.0, cap: int | None = None):
+        """One detect call without retry (loop query if `connected` is not None):
+        (status, ncand, the first min(ncand, cap) candidates)."""
+        w, v = _bow(bow)
+        cap = max(len(self), 1) if cap is None else int(cap)
+        out = np.full(max(cap, 1), -1, np.int32)
+        n = ctypes.c_int32(0)
+        if connected is None:
+            code = self._L.orbx_kfdb_detect_relocalization(self._h, ptr(w), ptr(v), len(w),
+                                                           ptr(out), cap, ctypes.byref(n))
+        else:
+            c = np.ascontiguousarray(connected, np.int32)
+            code = self._L.orbx_kfdb_detect_loop(self._h, ptr(w), ptr(v), len(w), ptr(c), len(c),
+                                                 float(min_score), ptr(out), cap, ctypes.byref(n))
+        return code, n.value, out[:max(0, min(n.value, cap))].copy()
+
     def last_timing(self):
         """(scan_ms, select_ms) of the last detect call (HIP events on the database stream)."""
         a, b = ctypes.c_double(), ctypes.c_double()

@@ -65,6 +65,11 @@ def bow_score_l1(bow1, bow2) -> float:
     return float(load().orbx_bow_score_l1(ptr(w1), ptr(v1), len(w1), ptr(w2), ptr(v2), len(w2)))
 
 
+def bow_db_score_max_query() -> int:
+    """orbx_bow_db_score_max_query: the largest query BowVector bow_db_score takes."""
+    return int(load().orbx_bow_db_score_max_query())
+
+
 def bow_db_score(query_bow, kf_bows, device: int = 0):
     """Scoring pass of KeyFrameDatabase::DetectRelocalizationCandidates
     (src/KeyFrameDatabase.cc:220-278) on the GPU: for every keyframe BowVector, the number of

@@ -35,6 +35,8 @@ def _setup(L):
     L.oracle_kfdb_detect_reloc.argtypes = [_vp, _vp, _vp, _i, _vp, _i]
     L.oracle_kfdb_detect_loop.restype = _i
     L.oracle_kfdb_detect_loop.argtypes = [_vp, _vp, _vp, _i, _vp, _i, ctypes.c_float, _vp, _i]
+    L.oracle_kfdb_debug_read.restype = _i
+    L.oracle_kfdb_debug_read.argtypes = [_vp] * 9 + [_i]
     L._kfdb_ready = True
     return L
 
@@ -66,6 +68,20 @@ class OracleKeyFrameDatabase:
     def set_covisibles(self, slot, neighbours):
         nb = np.ascontiguousarray(neighbours, np.int32)
         self._L.oracle_kfdb_set_covisibles(self._h, int(slot), _a(nb), len(nb))
+
+    def debug_read(self):
+        """The last query's per-keyframe read-back (oracle_kfdb_debug_read), or None before any
+        query: dict of listed / words / first (int32), score / query_score / reloc_score / acc
+        (float32), best (int32), plus loop (bool) and selected (lKFsSharingWords not empty)."""
+        n = self.n
+        i32 = {k: np.zeros(n, np.int32) for k in ("listed", "words", "first", "best")}
+        f32 = {k: np.zeros(n, np.float32) for k in ("score", "query_score", "reloc_score", "acc")}
+        r = self._L.oracle_kfdb_debug_read(
+            self._h, _a(i32["listed"]), _a(i32["words"]), _a(i32["first"]), _a(f32["score"]),
+            _a(f32["query_score"]), _a(f32["reloc_score"]), _a(f32["acc"]), _a(i32["best"]), n)
+        if r < 0:
+            return None
+        return dict(i32, **f32, loop=bool(r & 1), selected=bool(r & 2))
 
     def DetectRelocalizationCandidates(self, bow):
         w = np.ascontiguousarray(bow[0], np.uint32)

@@ -13,6 +13,7 @@
 // Conventions where the reference is undefined (same as include/orbx_kfdb.h): mRelocScore
 // starts at 0 (uninitialised in KeyFrame.cc:35's initialiser list), and each detect call
 // gets a fresh query id (F->mnId / pKF->mnId, never 0, which the ctor gives mn*Query).
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <list>
@@ -36,6 +37,7 @@ struct OKeyFrame {
     unsigned long mnRelocQuery = 0;
     int mnRelocWords = 0;
     float mRelocScore = 0.f;         // convention (uninitialised in the reference)
+    bool erased = false;             // read-back only: in no inverted-file list any more
 
     // KeyFrame::GetBestCovisibilityKeyFrames (KeyFrame.cc:178-186)
     std::vector<int> best_covisibles(int N) const {
@@ -49,6 +51,25 @@ struct ODatabase {
     std::unordered_map<uint32_t, std::list<int>> inv;       // mvInvertedFile
     unsigned long next_query = 1;
     int covisibles = 10;
+    // read-back of the last query (oracle_kfdb_debug_read); nothing below reads these
+    unsigned long rb_id = 0;
+    bool rb_loop = false, rb_listed = false;   // rb_listed: lKFsSharingWords was not empty
+    std::vector<uint32_t> rb_qw;
+    std::vector<double> rb_qv;
+    std::vector<int> rb_first, rb_best;        // query position of the word that listed the slot
+    std::vector<float> rb_acc;
+
+    void rb_begin(unsigned long id, bool loop, const std::vector<uint32_t>& qw,
+                  const std::vector<double>& qv) {
+        rb_id = id;
+        rb_loop = loop;
+        rb_listed = false;
+        rb_qw = qw;
+        rb_qv = qv;
+        rb_first.assign(kfs.size(), INT_MAX);
+        rb_best.assign(kfs.size(), -1);
+        rb_acc.assign(kfs.size(), -1.0f);
+    }
 
     double score(const std::vector<uint32_t>& qw, const std::vector<double>& qv,
                  const OKeyFrame& k) const {
@@ -60,8 +81,10 @@ struct ODatabase {
     std::vector<int> detect_loop(const std::vector<uint32_t>& qw, const std::vector<double>& qv,
                                  const std::set<int>& spConnectedKeyFrames, float minScore) {
         const unsigned long id = next_query++;
+        rb_begin(id, true, qw, qv);
         std::list<int> lKFsSharingWords;
-        for (uint32_t w : qw) {                                           // :89-110
+        for (size_t wi = 0; wi < qw.size(); ++wi) {                       // :89-110
+            const uint32_t w = qw[wi];
             auto it = inv.find(w);
             if (it == inv.end()) continue;
             for (int i : it->second) {
@@ -71,12 +94,14 @@ struct ODatabase {
                     if (!spConnectedKeyFrames.count(i)) {
                         pKFi.mnLoopQuery = id;
                         lKFsSharingWords.push_back(i);
+                        rb_first[i] = (int)wi;
                     }
                 }
                 pKFi.mnLoopWords++;
             }
         }
         if (lKFsSharingWords.empty()) return {};                          // :113-114
+        rb_listed = true;
         std::list<std::pair<float, int>> lScoreAndMatch;
         int maxCommonWords = 0;                                           // :120-125
         for (int i : lKFsSharingWords)
@@ -109,6 +134,8 @@ struct ODatabase {
                 }
             }
             lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+            rb_acc[it.second] = accScore;
+            rb_best[it.second] = pBestKF;
             if (accScore > bestAccScore) bestAccScore = accScore;
         }
         float minScoreToRetain = 0.75f * bestAccScore;                    // :187
@@ -129,8 +156,10 @@ struct ODatabase {
     // KeyFrameDatabase::DetectRelocalizationCandidates (:220-337)
     std::vector<int> detect_reloc(const std::vector<uint32_t>& qw, const std::vector<double>& qv) {
         const unsigned long id = next_query++;
+        rb_begin(id, false, qw, qv);
         std::list<int> lKFsSharingWords;
-        for (uint32_t w : qw) {                                           // :230-245
+        for (size_t wi = 0; wi < qw.size(); ++wi) {                       // :230-245
+            const uint32_t w = qw[wi];
             auto it = inv.find(w);
             if (it == inv.end()) continue;
             for (int i : it->second) {
@@ -139,11 +168,13 @@ struct ODatabase {
                     pKFi.mnRelocWords = 0;
                     pKFi.mnRelocQuery = id;
                     lKFsSharingWords.push_back(i);
+                    rb_first[i] = (int)wi;
                 }
                 pKFi.mnRelocWords++;
             }
         }
         if (lKFsSharingWords.empty()) return {};                          // :247-248
+        rb_listed = true;
         int maxCommonWords = 0;                                           // :251-257
         for (int i : lKFsSharingWords)
             if (kfs[i].mnRelocWords > maxCommonWords) maxCommonWords = kfs[i].mnRelocWords;
@@ -175,6 +206,8 @@ struct ODatabase {
                 }
             }
             lAccScoreAndMatch.push_back(std::make_pair(accScore, pBestKF));
+            rb_acc[it.second] = accScore;
+            rb_best[it.second] = pBestKF;
             if (accScore > bestAccScore) bestAccScore = accScore;
         }
         float minScoreToRetain = 0.75f * bestAccScore;                    // :318
@@ -226,7 +259,8 @@ int oracle_kfdb_add(void* h, const uint32_t* w, const double* v, int n) {
 // KeyFrameDatabase::erase (:48-67)
 void oracle_kfdb_erase(void* h, int slot) {
     ODatabase* d = (ODatabase*)h;
-    const OKeyFrame& k = d->kfs[slot];
+    OKeyFrame& k = d->kfs[slot];
+    k.erased = true;
     for (uint32_t w : k.words) {
         std::list<int>& l = d->inv[w];
         for (auto it = l.begin(); it != l.end(); ++it)
@@ -264,6 +298,39 @@ int oracle_kfdb_detect_loop(void* h, const uint32_t* qw, const double* qv, int n
                                    std::vector<double>(qv, qv + nq),
                                    std::set<int>(conn, conn + nc), min_score),
                     out, cap);
+}
+
+// Read-back of the last detect call for the first n keyframes (any output may be NULL):
+//   listed[s]  1 if the query put s into lKFsSharingWords (mn*Query == its id)
+//   words[s]   mnRelocWords / mnLoopWords of a listed keyframe, 0 otherwise (a keyframe the
+//              loop query found connected has its counter reset at every word: not reported)
+//   first[s]   query position of the word that listed s (INT_MAX if not listed)
+//   score[s]   (float)score(query, s) of every keyframe still in the inverted file, listed or
+//              not (what a scan of the whole database computes); -0.0f for erased ones
+//   query_score[s]  mRelocScore (relocalisation query) / mLoopScore (loop query) as stored
+//   reloc_score[s]  mRelocScore, the state the next relocalisation query may read
+//   acc[s], best[s] accScore and pBestKF of the keyframes in lScoreAndMatch, -1 elsewhere
+// Returns -1 before any query, else bit 0 = the query was a loop query, bit 1 =
+// lKFsSharingWords was not empty (acc / best are this query's).
+int oracle_kfdb_debug_read(void* h, int32_t* listed, int32_t* words, int32_t* first, float* score,
+                           float* query_score, float* reloc_score, float* acc, int32_t* best,
+                           int n) {
+    ODatabase* d = (ODatabase*)h;
+    if (d->rb_id == 0) return -1;
+    for (int s = 0; s < n && s < (int)d->kfs.size(); ++s) {
+        const OKeyFrame& k = d->kfs[s];
+        const bool in = (d->rb_loop ? k.mnLoopQuery : k.mnRelocQuery) == d->rb_id;
+        const bool known = s < (int)d->rb_first.size();   // existed at the query
+        if (listed) listed[s] = in;
+        if (words) words[s] = in ? (d->rb_loop ? k.mnLoopWords : k.mnRelocWords) : 0;
+        if (first) first[s] = known ? d->rb_first[s] : INT_MAX;
+        if (score) score[s] = k.erased ? -0.0f : (float)d->score(d->rb_qw, d->rb_qv, k);
+        if (query_score) query_score[s] = d->rb_loop ? k.mLoopScore : k.mRelocScore;
+        if (reloc_score) reloc_score[s] = k.mRelocScore;
+        if (acc) acc[s] = known ? d->rb_acc[s] : -1.0f;
+        if (best) best[s] = known ? d->rb_best[s] : -1;
+    }
+    return (d->rb_loop ? 1 : 0) | (d->rb_listed ? 2 : 0);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 """KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc:76-208, 220-337).
 
 CPU: the C++ restatement (oracle/orb_kfdb_oracle.cpp) against an independent pure-Python
-restatement below (inverted file, keyframe state, float32 arithmetic of the reference), over
+restatement in tests/kfdb_cases.py (inverted file, keyframe state, float32 arithmetic of the reference), over
 query sequences that exercise the persistent state (mRelocScore of neighbours that share a
 word but miss the 0.8 filter is the previous query's value), erase and clear.
 GPU: the HBM-resident database (my_orb_slam2_amd.kfdb, csrc/orbx_kfdb.hip) against the C++
@@ -13,143 +13,7 @@ import pytest
 
 from my_orb_slam2_amd import synth
 
-F32 = np.float32
-
-
-class PyKeyFrameDatabase:
-    """Pure-Python restatement (test-only), statement by statement with the reference."""
-
-    def __init__(self, covisibles=10):
-        self.K = covisibles
-        self.kfs = []            # dicts: words, values, ordered, state fields
-        self.inv = {}            # word -> list of slots in add order
-        self.qid = 1
-
-    def add(self, bow):
-        w, v = bow
-        s = len(self.kfs)
-        self.kfs.append(dict(w=[int(x) for x in w], v=[float(x) for x in v], ordered=[],
-                             lq=0, lw=0, ls=F32(0), rq=0, rw=0, rs=F32(0)))
-        for x in w:
-            self.inv.setdefault(int(x), []).append(s)
-        return s
-
-    def erase(self, s):
-        for x in self.kfs[s]["w"]:
-            lst = self.inv[x]
-            if s in lst:
-                lst.remove(s)
-
-    def clear(self):
-        self.kfs, self.inv = [], {}
-
-    def set_covisibles(self, s, nb):
-        self.kfs[s]["ordered"] = [int(x) for x in nb]
-
-    @staticmethod
-    def _score(qw, qv, k):
-        # L1Scoring::score (ScoringObject.cpp:23-67): merged walk in ascending word order
-        pos = {w: i for i, w in enumerate(k["w"])}
-        acc = 0.0
-        for w, vi in zip(qw, qv):
-            j = pos.get(int(w))
-            if j is not None:
-                wi = k["v"][j]
-                acc += abs(vi - wi) - abs(vi) - abs(wi)
-        return F32(-acc / 2.0)
-
-    def DetectRelocalizationCandidates(self, bow):
-        qw, qv = [int(x) for x in bow[0]], [float(x) for x in bow[1]]
-        qid, self.qid = self.qid, self.qid + 1
-        sharing = []
-        for w in qw:
-            for s in self.inv.get(w, []):
-                k = self.kfs[s]
-                if k["rq"] != qid:
-                    k["rw"] = 0
-                    k["rq"] = qid
-                    sharing.append(s)
-                k["rw"] += 1
-        if not sharing:
-            return []
-        mx = max(self.kfs[s]["rw"] for s in sharing)
-        minc = int(F32(mx) * F32(0.8))
-        scored = []
-        for s in sharing:
-            k = self.kfs[s]
-            if k["rw"] > minc:
-                k["rs"] = self._score(qw, qv, k)
-                scored.append((k["rs"], s))
-        if not scored:
-            return []
-        accl, best_acc = [], F32(0)
-        for sc, s in scored:
-            best, acc, bk = sc, sc, s
-            for n in self.kfs[s]["ordered"][:self.K]:
-                k2 = self.kfs[n]
-                if k2["rq"] != qid:
-                    continue
-                acc = F32(acc + k2["rs"])
-                if k2["rs"] > best:
-                    bk, best = n, k2["rs"]
-            accl.append((acc, bk))
-            if acc > best_acc:
-                best_acc = acc
-        thr = F32(F32(0.75) * best_acc)
-        out, seen = [], set()
-        for acc, bk in accl:
-            if acc > thr and bk not in seen:
-                out.append(bk)
-                seen.add(bk)
-        return out
-
-    def DetectLoopCandidates(self, bow, connected, min_score):
-        qw, qv = [int(x) for x in bow[0]], [float(x) for x in bow[1]]
-        conn = set(int(x) for x in connected)
-        min_score = F32(min_score)
-        qid, self.qid = self.qid, self.qid + 1
-        sharing = []
-        for w in qw:
-            for s in self.inv.get(w, []):
-                k = self.kfs[s]
-                if k["lq"] != qid:
-                    k["lw"] = 0
-                    if s not in conn:
-                        k["lq"] = qid
-                        sharing.append(s)
-                k["lw"] += 1
-        if not sharing:
-            return []
-        mx = max(self.kfs[s]["lw"] for s in sharing)
-        minc = int(F32(mx) * F32(0.8))
-        scored = []
-        for s in sharing:
-            k = self.kfs[s]
-            if k["lw"] > minc:
-                k["ls"] = self._score(qw, qv, k)
-                if k["ls"] >= min_score:
-                    scored.append((k["ls"], s))
-        if not scored:
-            return []
-        accl, best_acc = [], min_score
-        for sc, s in scored:
-            best, acc, bk = sc, sc, s
-            for n in self.kfs[s]["ordered"][:self.K]:
-                k2 = self.kfs[n]
-                if k2["lq"] == qid and k2["lw"] > minc:
-                    acc = F32(acc + k2["ls"])
-                    if k2["ls"] > best:
-                        bk, best = n, k2["ls"]
-            accl.append((acc, bk))
-            if acc > best_acc:
-                best_acc = acc
-        thr = F32(F32(0.75) * best_acc)
-        out, seen = [], set()
-        for acc, bk in accl:
-            if acc > thr and bk not in seen:
-                out.append(bk)
-                seen.add(bk)
-        return out
+from kfdb_cases import PyKeyFrameDatabase
 
 
 def _build(dbs, bows, cov):
