@@ -203,6 +203,66 @@ orbx_status orbx_close_points(const orbx_frame_pose* pose, const orbx_keypoint* 
                               int32_t min_points, int32_t* order, int32_t* counts,
                               uint8_t* create, float* x3d, int device);
 
+/* ---- Stereo rectification of raw pairs (Examples/Stereo/stereo_euroc.cc:96-98 builds the two
+ * maps with cv::initUndistortRectifyMap, :136-137 run cv::remap(..., cv::INTER_LINEAR) on both
+ * images of every frame before TrackStereo; Examples/ROS/ORB_SLAM2/src/ros_stereo.cc:106-107,
+ * 161-162 likewise) ----
+ *
+ * OpenCV 3.2's algorithms restated (modules/imgproc/src/undistort.cpp, imgwarp.cpp): PARITY
+ * UNPINNED against the library; bit-exact between the GPU, these host helpers and the numpy
+ * restatement of tests/remap_cases.py.
+ *
+ * cv::initUndistortRectifyMap(K, D, R, P(:, :3), size, CV_32F, map1, map2)
+ * (stereo_euroc.cc:96-98), host only, in double as written (no contraction): iR = (P33 * R)^-1
+ * by the 3x3 closed form, then per pixel the forward distortion k1 k2 p1 p2 [k3 [k4 k5 k6]] of
+ * the normalised ray.  K, R, P33 row-major 3x3; R9_or_null == NULL: identity; ndist 4, 5 or 8
+ * (12 / 14, the thin-prism and tilt terms: ORBX_ERR_UNSUPPORTED); map1 / map2 width*height
+ * floats. */
+orbx_status orbx_init_undistort_rectify_map(const double K[9], const double* dist, int32_t ndist,
+                                            const double* R9_or_null, const double P33[9],
+                                            int32_t width, int32_t height, float* map1,
+                                            float* map2);
+/* cv::remap's conversion of a CV_32FC1 map pair to fixed point (stereo_euroc.cc:136-137, the
+ * first step of remap INTER_LINEAR), host only: sx = cvRound(map1 * 32.0f) (float product, x86
+ * cvtss2si: half to even, NaN / out of range INT_MIN), xy[2i] = saturate_cast<short>(sx >> 5),
+ * a[i] = (sy & 31) * 32 + (sx & 31); the layout of OpenCV's CV_16SC2 + CV_16UC1 maps. */
+orbx_status orbx_remap_fixed_point(const float* map1, const float* map2, size_t n, int16_t* xy,
+                                   uint16_t* a);
+
+/* One camera's map on the device (dst_w x dst_h entries from map1 / map2, tightly packed rows),
+ * converted at create time for a source of src_w x src_h pixels.  Immutable after create and
+ * usable from several threads.  src_w or src_h above 32767 (the short saturation):
+ * ORBX_ERR_UNSUPPORTED; without a GPU: ORBX_ERR_DEVICE. */
+typedef struct orbx_rectifier orbx_rectifier;
+orbx_status orbx_rectifier_create(const float* map1, const float* map2, int32_t dst_w,
+                                  int32_t dst_h, int32_t src_w, int32_t src_h, int device,
+                                  orbx_rectifier** out);
+orbx_status orbx_rectifier_destroy(orbx_rectifier* r);
+
+/* cv::remap(src 8UC1, dst, map1, map2, cv::INTER_LINEAR) with BORDER_CONSTANT 0
+ * (stereo_euroc.cc:136-137) on `batch` device images (image i at base + i*image_stride, rows
+ * row_stride bytes apart): dst = (sum of the four taps times their 5-bit weight products + 512)
+ * >> 10, taps outside the source 0.  Any base address, any row stride >= width; src and dst must
+ * not overlap; bytes of a destination row past dst_w are left untouched.  Rows of one image
+ * spanning 4 GiB or more: ORBX_ERR_UNSUPPORTED. */
+orbx_status orbx_remap_batch_device(const orbx_rectifier* r, const uint8_t* d_src,
+                                    size_t src_row_stride, size_t src_image_stride,
+                                    uint8_t* d_dst, size_t dst_row_stride,
+                                    size_t dst_image_stride, int32_t batch, void* stream);
+/* Both views of `batch` pairs, each with its own map, in one launch (stereo_euroc.cc:136-137;
+ * ros_stereo.cc:161-162); the strides are shared by the two sides.  Rectifiers of different
+ * destination size or on different devices: ORBX_ERR_INVALID. */
+orbx_status orbx_remap_stereo_batch_device(
+    const orbx_rectifier* r_left, const orbx_rectifier* r_right, const uint8_t* d_src_left,
+    const uint8_t* d_src_right, size_t src_row_stride, size_t src_image_stride,
+    uint8_t* d_dst_left, uint8_t* d_dst_right, size_t dst_row_stride, size_t dst_image_stride,
+    int32_t batch, void* stream);
+/* One host image (copied to the device for the call), stereo_euroc.cc:136. */
+orbx_status orbx_remap(const orbx_rectifier* r, const uint8_t* src, size_t src_stride,
+                       uint8_t* dst, size_t dst_stride);
+/* Images a lane of the remap kernel handles with one read of its map entries. */
+int32_t orbx_remap_images_per_chunk(void);
+
 #ifdef __cplusplus
 }
 #endif

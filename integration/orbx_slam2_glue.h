@@ -9,6 +9,9 @@
 //                                   replaces Frame::ComputeStereoFromRGBD (src/Frame.cc:689-710)
 //                                   and the whole-image imDepth.convertTo in front of it
 //                                   (src/Tracking.cc:244-245)
+//   Rectifier(M1, M2, srcSize)     replaces the per-frame cv::remap(imRaw, imRect, M1, M2,
+//                                   cv::INTER_LINEAR) of Examples/Stereo/stereo_euroc.cc:136-137
+//                                   (maps from cv::initUndistortRectifyMap, :96-98)
 //   OrbxView / BuildView(f, view)   the orbx_featureset of a Frame / KeyFrame (mFeatVec, mGrid)
 //   SearchByBoW(m, pKF, F, out)     ORBmatcher::SearchByBoW(KeyFrame*, Frame&, ...) (:182-319)
 //
@@ -151,6 +154,46 @@ int ComputeStereoFromRGBD(Frame& F, const cv::Mat& imDepth, float depthFactor, i
                                  (size_t)imDepth.step, imDepth.cols, imDepth.rows, depthFactor,
                                  device);
 }
+
+// stereo_euroc.cc:136-137 (ros_stereo.cc:161-162): cv::remap(imRaw, imRect, M1, M2,
+// cv::INTER_LINEAR) of one 8UC1 image on the device.  M1 / M2 are the CV_32FC1 maps
+// cv::initUndistortRectifyMap(..., CV_32F, M1, M2) wrote (:96-98); srcCols x srcRows is the raw
+// image's size.  One Rectifier per camera, built once; remap() may be called from several threads.
+class Rectifier {
+public:
+    Rectifier(const cv::Mat& M1, const cv::Mat& M2, int srcCols, int srcRows, int device = 0) {
+        if (M1.empty() || M1.type() != CV_32F || M2.type() != CV_32F || M1.rows != M2.rows ||
+            M1.cols != M2.cols)
+            throw std::invalid_argument("Rectifier: two CV_32FC1 maps of one size expected");
+        const cv::Mat a = M1.isContinuous() ? M1 : M1.clone(), b = M2.isContinuous() ? M2 : M2.clone();
+        check(orbx_rectifier_create(reinterpret_cast<const float*>(a.data),
+                                    reinterpret_cast<const float*>(b.data), M1.cols, M1.rows,
+                                    srcCols, srcRows, device, &r_),
+              "orbx_rectifier_create");
+        cols_ = M1.cols;
+        rows_ = M1.rows;
+        src_cols_ = srcCols;
+        src_rows_ = srcRows;
+    }
+    ~Rectifier() { orbx_rectifier_destroy(r_); }
+    Rectifier(const Rectifier&) = delete;
+    Rectifier& operator=(const Rectifier&) = delete;
+
+    // dst is (re)allocated as cv::remap does unless it already is a rows x cols CV_8UC1 image
+    // (then its rows may be padded: bytes past the last column are left untouched)
+    void remap(const cv::Mat& src, cv::Mat& dst) const {
+        if (src.type() != CV_8UC1 || src.cols != src_cols_ || src.rows != src_rows_)
+            throw std::invalid_argument("Rectifier::remap: CV_8UC1 image of the source size expected");
+        if (dst.empty() || dst.type() != CV_8UC1 || dst.rows != rows_ || dst.cols != cols_)
+            dst.create(rows_, cols_, CV_8UC1);
+        check(orbx_remap(r_, src.data, (size_t)src.step, dst.data, (size_t)dst.step), "orbx_remap");
+    }
+    const orbx_rectifier* handle() const { return r_; }
+
+private:
+    orbx_rectifier* r_ = nullptr;
+    int cols_ = 0, rows_ = 0, src_cols_ = 0, src_rows_ = 0;
+};
 
 // CSR copies of mFeatVec (after ComputeBoW) and mGrid (after AssignFeaturesToGrid); the other
 // arrays are the frame's own (mvKeysUn, mDescriptors, mvuRight).  Rebuild after either changes.

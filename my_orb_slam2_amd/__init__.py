@@ -9,6 +9,8 @@ Host-side mirror of the reference's operator interface for this path:
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
   (src/Frame.cc:132-236; ComputeStereoFromRGBD :689-710, UnprojectStereo :713-727)
+* ``Rectifier`` / ``RectifiedStereoBatch`` — cv::initUndistortRectifyMap + cv::remap on raw stereo
+  pairs ahead of the stereo frame (Examples/Stereo/stereo_euroc.cc:96-98, :136-137)
 
 Everything routes through liborbx.so (include/orbx.h).  There is no CPU fallback.
 """
@@ -21,7 +23,11 @@ from .matcher import ORBmatcher, descriptor_distance
 from .vocabulary import Vocabulary, bow_score_l1
 from .kfdb import KeyFrameDatabase
 from .tracking import MonoTrackBatch, RGBDTrackBatch
+from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
+                      load_stereo_settings, remap_fixed_point, remap_stereo_batch_device)
 
 __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_stereo_matches_batch_device",
            "extract_stereo", "descriptor_distance",
-           "StereoBatch", "MonoTrackBatch", "RGBDTrackBatch", "Vocabulary", "bow_score_l1", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "load"]
+           "StereoBatch", "MonoTrackBatch", "RGBDTrackBatch", "Vocabulary", "bow_score_l1", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "load",
+           "Rectifier", "RectifiedStereoBatch", "init_undistort_rectify_map", "load_stereo_settings",
+           "remap_fixed_point", "remap_stereo_batch_device"]

@@ -176,6 +176,15 @@ SIGNATURES = {
     "orbx_close_points_batch_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _i, _vp,
                                             _vp, _vp, _vp, _vp]),
     "orbx_close_points": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp, _i]),
+    "orbx_init_undistort_rectify_map": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "orbx_remap_fixed_point": (_i, [_vp, _vp, _sz, _vp, _vp]),
+    "orbx_rectifier_create": (_i, [_vp, _vp, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "orbx_rectifier_destroy": (_i, [_vp]),
+    "orbx_remap_batch_device": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _sz, _i, _vp]),
+    "orbx_remap_stereo_batch_device": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _sz, _i,
+                                            _vp]),
+    "orbx_remap": (_i, [_vp, _vp, _sz, _vp, _sz]),
+    "orbx_remap_images_per_chunk": (_i, []),
 }
 
 _lib = None

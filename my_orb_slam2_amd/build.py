@@ -23,7 +23,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
-           "orbx_kfdb.hip", "orbx_bf.hip"]
+           "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_kernels.h", "orbx_host.h",
            "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
            "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
@@ -222,3 +222,32 @@ def build_rgbd_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
     subprocess.run(cmd, check=True)
     os.replace(str(RGBD_BIN) + ".tmp", RGBD_BIN)
     return RGBD_BIN
+
+
+# ---- the rectifier glue compiled as ORB-SLAM2 would include it (tests/native/remap_test.cpp) ----
+REMAP_SRC = PKG.parent / "tests" / "native" / "remap_test.cpp"
+REMAP_BIN = PKG.parent / "tests" / "native" / "remap_test"
+
+
+def build_remap_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on integration/orbx_slam2_glue.h (orbx_glue::Rectifier) with the cv stand-in, linked to
+    the in-tree liborbx.so."""
+    root = PKG.parent
+    native = root / "tests" / "native"
+    deps = ([REMAP_SRC] + sorted((root / "include").glob("*.h")) +
+            sorted((root / "integration").glob("*.h")) +
+            sorted((native / "cv_standin").rglob("*.hpp")))
+    newest = max(p.stat().st_mtime for p in deps)
+    if not force and REMAP_BIN.exists() and REMAP_BIN.stat().st_mtime >= newest:
+        return REMAP_BIN
+    build(verbose=verbose)
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(root / "integration"),
+           "-I" + str(native / "cv_standin"), str(REMAP_SRC), "-L" + str(PKG),
+           "-lorbx", "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
+           "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd", "-pthread", "-o", str(REMAP_BIN) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(REMAP_BIN) + ".tmp", REMAP_BIN)
+    return REMAP_BIN
