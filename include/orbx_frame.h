@@ -109,6 +109,65 @@ orbx_status orbx_is_in_frustum(const orbx_frame_pose* frame, const orbx_map_poin
                                int32_t n, const uint8_t* skip, float viewing_cos_limit,
                                float th, orbx_proj_query* q, int32_t* nvisible, int device);
 
+/* ---- The per-MapPoint projection loop of the other six projection searches (orbx_proj_mode
+ * LAST_FRAME :1402-1458, KEYFRAME :1544-1596, KF_SCW :321-390, FUSE :881-946, FUSE_SCW :1035-1105,
+ * SIM3 :1166-1247 / :1284-1327 of src/ORBmatcher.cc) ----
+ *
+ * One job's constants.  cam: the view projected into -- the current Frame (LAST_FRAME, KEYFRAME),
+ * the KeyFrame (KF_SCW, FUSE, FUSE_SCW; for the Scw modes Rcw / tcw / Ow already decomposed from
+ * Scw as ORBmatcher.cc:1042-1046 does once per call), or for SIM3 Rcw = sR21, tcw = t21 (Ow
+ * unused) with the target keyframe's intrinsics, bounds and scale tables.  pre_R / pre_t: SIM3's
+ * first transform (R1w, t1w); LAST_FRAME's last-frame pose (Rlw, tlw); otherwise unused.  mb /
+ * mono: LAST_FRAME only (CurrentFrame.mb, bMono).  th: the search window factor.  240 bytes. */
+typedef struct {
+    orbx_frame_pose cam;
+    float pre_R[9];
+    float pre_t[3];
+    float mb;
+    float th;
+    int32_t mono;
+    int32_t reserved[3];
+} orbx_proj_job;
+
+/* For every MapPoint i of every job j (job j's MapPoints at [d_mp_off[j], d_mp_off[j+1]) of
+ * d_mps, queries written at the same indices of d_q), the projection the reference's loop of
+ * `mode` computes, in its types and order (all jobs of a call share the mode):
+ *   Pc     = cam.Rcw*P + cam.tcw in cv::gemm's small-matrix form (as orbx_is_in_frustum); SIM3:
+ *            of P1 = pre_R*P + pre_t
+ *   depth  LAST_FRAME: invz < 0 rejects (after invz); KEYFRAME: no test; others: Pc.z < 0 rejects
+ *   invz   KF_SCW, FUSE: 1.0f / z; others: (float)(1.0 / (double)z)
+ *   u, v   LAST_FRAME, KEYFRAME: (fx*xc)*invz + cx with the Frame bounds (u < min_x || u > max_x
+ *          rejects, so NaN passes); others: x = xc*invz, fx*x + cx with KeyFrame::IsInImage
+ *          (u >= min_x && u < max_x, so NaN fails)
+ *   d      (float)cv::norm(P - cam.Ow) (SIM3: of Pc; LAST_FRAME: none), d < 0.8f*min_dist ||
+ *          d > 1.2f*max_dist rejects; KF_SCW, FUSE, FUSE_SCW: (P - Ow).dot(normal) < 0.5*d in
+ *          double rejects
+ *   level  L = PredictScale(d) on the raw max_dist (as orbx_is_in_frustum); LAST_FRAME:
+ *          L = d_src_keys[i].octave, an octave outside [0, cam.nlevels) gives an inactive query
+ *          (the reference indexes mvScaleFactors unchecked)
+ *   query  {u, v, ur, th*scale[L], min_level, max_level, L, angle}: ur = u - mbf*invz for
+ *          LAST_FRAME and FUSE, else 0; levels (L-1, L+1) for KEYFRAME and for LAST_FRAME unless
+ *          forward (L, -1) or backward (0, L), else (-1, -1); angle = d_src_keys[i].angle for
+ *          LAST_FRAME and KEYFRAME, else 0.  LAST_FRAME per job: tlc.z = row 2 of pre_R*cam.Ow +
+ *          pre_t (gemm form), forward = tlc.z > mb && !mono, backward = -tlc.z > mb && !mono.
+ * Rejected, or d_skip[i] != 0 (no MapPoint, outlier, bad, already found, IsInKeyFrame): the
+ * inactive query {0, 0, 0, -1, -1, -1, -1, 0}.  A job whose cam.nlevels is outside [1, 16] gets
+ * inactive queries only.  d_nactive[j] (optional) = job j's active queries.  d_src_keys (point
+ * i's source feature; octave and angle are read) is required for LAST_FRAME and KEYFRAME.
+ * max_mps >= every job's MapPoint count; the MapPoints of a call number at most 1 << 24.
+ * d_mps and d_q are read and written as 16-byte accesses: a base that is not 16-byte aligned
+ * is ORBX_ERR_INVALID.  mode outside the six (ORBX_PROJ_FRAME_MAPPOINTS is orbx_is_in_frustum*): ORBX_ERR_INVALID. */
+orbx_status orbx_project_map_points_batch_device(
+    int32_t mode, const orbx_proj_job* d_jobs, int32_t njobs, const orbx_map_point* d_mps,
+    const int32_t* d_mp_off, int32_t max_mps, const orbx_keypoint* d_src_keys,
+    const uint8_t* d_skip, orbx_proj_query* d_q, int32_t* d_nactive, void* stream);
+/* One job, host arrays (copied to the device for the call).  The argument checks run before the
+ * device is touched; without a GPU: ORBX_ERR_DEVICE. */
+orbx_status orbx_project_map_points(int32_t mode, const orbx_proj_job* job,
+                                    const orbx_map_point* mps, int32_t n,
+                                    const orbx_keypoint* src_keys, const uint8_t* skip,
+                                    orbx_proj_query* q, int32_t* nactive, int device);
+
 /* Tracking's colour input (src/Tracking.cc:189-214): cv::cvtColor(*2GRAY) for 3- or 4-channel
  * 8-bit images, OpenCV 3.2's integer path RGB2Gray<uchar> (Y = (R*4899 + G*9617 + B*1868 +
  * 8192) >> 14).  rgb = 1 for RGB/RGBA order (mbRGB), 0 for BGR/BGRA.  OpenCV builds with IPP

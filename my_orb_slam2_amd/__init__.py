@@ -23,6 +23,8 @@ from .matcher import ORBmatcher, descriptor_distance
 from .vocabulary import Vocabulary, bow_score_l1
 from .kfdb import KeyFrameDatabase
 from .tracking import MonoTrackBatch, RGBDTrackBatch
+from .features import (PROJ_JOB_DTYPE, PROJ_SIM3, proj_job, project_map_points,
+                       project_map_points_batch_device)
 from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
                       load_stereo_settings, remap_fixed_point, remap_stereo_batch_device)
 
@@ -30,4 +32,6 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "extract_stereo", "descriptor_distance",
            "StereoBatch", "MonoTrackBatch", "RGBDTrackBatch", "Vocabulary", "bow_score_l1", "KeyFrameDatabase", "KEYPOINT_DTYPE", "OrbxError", "load",
            "Rectifier", "RectifiedStereoBatch", "init_undistort_rectify_map", "load_stereo_settings",
-           "remap_fixed_point", "remap_stereo_batch_device"]
+           "remap_fixed_point", "remap_stereo_batch_device",
+           "PROJ_JOB_DTYPE", "PROJ_SIM3", "proj_job", "project_map_points",
+           "project_map_points_batch_device"]

@@ -165,6 +165,9 @@ SIGNATURES = {
     "orbx_cvt_color_device": (_i, [_vp, _i, _i, _sz, _i, _i, _vp, _sz, _vp]),
     "orbx_is_in_frustum_batch_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp]),
     "orbx_is_in_frustum": (_i, [_vp, _vp, _i, _vp, _f, _f, _vp, _vp, _i]),
+    "orbx_project_map_points_batch_device": (_i, [_i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                                  _vp]),
+    "orbx_project_map_points": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "orbx_compute_stereo_from_rgbd_batch_device": (_i, [_vp, _i, _sz, _sz, _i, _i, _f, _f, _vp,
                                                         _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "orbx_compute_stereo_from_rgbd": (_i, [_vp, _i, _sz, _i, _i, _f, _f, _vp, _vp, _i, _vp, _vp,

@@ -251,3 +251,29 @@ def build_remap_test(force: bool = False, verbose: bool = False) -> pathlib.Path
     subprocess.run(cmd, check=True)
     os.replace(str(REMAP_BIN) + ".tmp", REMAP_BIN)
     return REMAP_BIN
+
+
+# ---- the projection loops restated over the cv stand-in (tests/native/project_ref.cpp) ----------
+PROJECT_REF_SRC = PKG.parent / "tests" / "native" / "project_ref.cpp"
+PROJECT_REF_BIN = PKG.parent / "tests" / "native" / "project_ref"
+
+
+def build_project_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on the cv stand-in and the record layouts of include/orbx_frame.h only: no liborbx and
+    no GPU (the CPU reference of orbx_project_map_points*)."""
+    root = PKG.parent
+    native = root / "tests" / "native"
+    deps = ([PROJECT_REF_SRC] + sorted((root / "include").glob("*.h")) +
+            sorted((native / "cv_standin").rglob("*.hpp")))
+    newest = max(p.stat().st_mtime for p in deps)
+    if not force and PROJECT_REF_BIN.exists() and PROJECT_REF_BIN.stat().st_mtime >= newest:
+        return PROJECT_REF_BIN
+    # -ffp-contract=off: the reference's float statements as written
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(native / "cv_standin"),
+           str(PROJECT_REF_SRC), "-o", str(PROJECT_REF_BIN) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(PROJECT_REF_BIN) + ".tmp", PROJECT_REF_BIN)
+    return PROJECT_REF_BIN

@@ -8,6 +8,8 @@
 //                  fill, then each cell sorted by feature index (the push_back order)
 //   k_frustum      one lane per (frame, local MapPoint): Frame::isInFrustum + PredictScale, the
 //                  SearchByProjection query of every MapPoint in view (SearchLocalPoints)
+//   k_project      one lane per (job, MapPoint): the projection loop of the other six
+//                  SearchByProjection / Fuse / SearchBySim3 modes, one template instance per mode
 //   k_rgbd_depth   one lane per (frame, keypoint): Frame::ComputeStereoFromRGBD on the raw depth
 //                  image (the samples are scaled, not the image), optionally fused with the
 //                  undistortion of the keypoint
@@ -483,6 +485,173 @@ bool close_prepare() {
     return have[dev];
 }
 
+// ---- the projection loops of the other six SearchByProjection modes ---------------------------
+
+// cv::gemm(R, P, 1, t, 1) small-matrix path, as in frustum_query
+__device__ __forceinline__ void gemm3(const float* __restrict__ R, const float* P,
+                                      const float* __restrict__ t, float* out) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        float s = __fmul_rn(R[3 * r], P[0]);
+        s = __fadd_rn(s, __fmul_rn(R[3 * r + 1], P[1]));
+        s = __fadd_rn(s, __fmul_rn(R[3 * r + 2], P[2]));
+        out[r] = (float)((double)s + (double)t[r]);
+    }
+}
+
+// (float)cv::norm(a): squares accumulated in double, sqrt, stored in a float
+__device__ __forceinline__ float norm3(const float* a) {
+    double ss = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ss = __dadd_rn(ss, __dmul_rn((double)a[k], (double)a[k]));
+    return (float)__dsqrt_rn(ss);
+}
+
+// The per-MapPoint body of the reference's loop for MODE (include/orbx_frame.h lists the steps;
+// ORBmatcher.cc LAST_FRAME :1402-1458, KEYFRAME :1544-1596, KF_SCW :321-390, FUSE :881-946,
+// FUSE_SCW :1035-1105, SIM3 :1166-1247).  The mode is a template argument, so each instance holds
+// one loop only.  key_octave / key_angle: the source feature (LAST_FRAME, KEYFRAME).
+template <int MODE>
+__device__ __forceinline__ bool project_query(const orbx_proj_job& J, const float* P,
+                                              float min_dist, const float* Pn, float max_dist,
+                                              int key_octave, float key_angle,
+                                              orbx_proj_query& q) {
+    constexpr bool FRAME = MODE == ORBX_PROJ_LAST_FRAME || MODE == ORBX_PROJ_KEYFRAME;
+    constexpr bool NORMAL = MODE == ORBX_PROJ_KF_SCW || MODE == ORBX_PROJ_FUSE ||
+                            MODE == ORBX_PROJ_FUSE_SCW;
+    const orbx_frame_pose& F = J.cam;
+    const int nlevels = F.nlevels;
+    if (nlevels < 1 || nlevels > 16) return false;
+    float Pc[3];
+    if (MODE == ORBX_PROJ_SIM3) {
+        float P1[3];
+        gemm3(J.pre_R, P, J.pre_t, P1);
+        gemm3(F.Rcw, P1, F.tcw, Pc);
+    } else {
+        gemm3(F.Rcw, P, F.tcw, Pc);
+    }
+    if (!FRAME && Pc[2] < 0.0f) return false;
+    const float invz = (MODE == ORBX_PROJ_KF_SCW || MODE == ORBX_PROJ_FUSE)
+                           ? __fdiv_rn(1.0f, Pc[2])
+                           : (float)__ddiv_rn(1.0, (double)Pc[2]);
+    if (MODE == ORBX_PROJ_LAST_FRAME && invz < 0.0f) return false;
+    float u, v;
+    if (FRAME) {
+        u = __fadd_rn(__fmul_rn(__fmul_rn(F.fx, Pc[0]), invz), F.cx);
+        v = __fadd_rn(__fmul_rn(__fmul_rn(F.fy, Pc[1]), invz), F.cy);
+        if (u < F.min_x || u > F.max_x) return false;
+        if (v < F.min_y || v > F.max_y) return false;
+    } else {
+        const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+        u = __fadd_rn(__fmul_rn(F.fx, x), F.cx);
+        v = __fadd_rn(__fmul_rn(F.fy, y), F.cy);
+        // KeyFrame::IsInImage
+        if (!(u >= F.min_x && u < F.max_x && v >= F.min_y && v < F.max_y)) return false;
+    }
+    int lvl;
+    if (MODE == ORBX_PROJ_LAST_FRAME) {
+        lvl = key_octave;
+        if (lvl < 0 || lvl >= nlevels) return false;   // the reference reads out of bounds
+    } else {
+        float PO[3] = {0.0f, 0.0f, 0.0f};
+        float dist;
+        if (MODE == ORBX_PROJ_SIM3) {
+            dist = norm3(Pc);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) PO[k] = __fsub_rn(P[k], F.Ow[k]);
+            dist = norm3(PO);
+        }
+        const float maxD = __fmul_rn(1.2f, max_dist), minD = __fmul_rn(0.8f, min_dist);
+        if (dist < minD || dist > maxD) return false;
+        if (NORMAL) {
+            double dot = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                dot = __dadd_rn(dot, __dmul_rn((double)PO[k], (double)Pn[k]));
+            if (dot < __dmul_rn(0.5, (double)dist)) return false;
+        }
+        const float ratio = __fdiv_rn(max_dist, dist);
+        lvl = x86_trunc(ceilf(__fdiv_rn(glibc_logf(ratio), F.log_scale_factor)));
+        if (lvl < 0) lvl = 0;
+        else if (lvl >= nlevels) lvl = nlevels - 1;
+    }
+    q.u = u;
+    q.v = v;
+    q.ur = (MODE == ORBX_PROJ_LAST_FRAME || MODE == ORBX_PROJ_FUSE)
+               ? __fsub_rn(u, __fmul_rn(F.mbf, invz)) : 0.0f;
+    q.radius = __fmul_rn(J.th, F.scale[lvl]);
+    q.min_level = q.max_level = -1;
+    if (MODE == ORBX_PROJ_KEYFRAME) {
+        q.min_level = lvl - 1;
+        q.max_level = lvl + 1;
+    } else if (MODE == ORBX_PROJ_LAST_FRAME) {
+        float tlc[3];
+        gemm3(J.pre_R, F.Ow, J.pre_t, tlc);
+        const bool forward = tlc[2] > J.mb && !J.mono, backward = -tlc[2] > J.mb && !J.mono;
+        q.min_level = forward ? lvl : backward ? 0 : lvl - 1;
+        q.max_level = forward ? -1 : backward ? lvl : lvl + 1;
+    }
+    q.pred_level = lvl;
+    q.angle = FRAME ? key_angle : 0.0f;
+    return true;
+}
+
+// One lane per (job, MapPoint), grid (ceil(max_mps / 256), njobs).  The job record is indexed by
+// the block, so its loads are uniform; the 32-byte MapPoint and query go as two 16-byte accesses.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_project(const orbx_proj_job* __restrict__ jobs,
+                                                 const orbx_map_point* __restrict__ mps,
+                                                 const int32_t* __restrict__ mp_off,
+                                                 const orbx_keypoint* __restrict__ keys,
+                                                 const uint8_t* __restrict__ skip,
+                                                 orbx_proj_query* __restrict__ q,
+                                                 int32_t* __restrict__ nactive) {
+    constexpr bool FRAME = MODE == ORBX_PROJ_LAST_FRAME || MODE == ORBX_PROJ_KEYFRAME;
+    const int j = blockIdx.y;
+    const int b = mp_off[j], e = mp_off[j + 1];
+    const int i = b + blockIdx.x * 256 + threadIdx.x;
+    bool act = false;
+    if (i < e) {
+        orbx_proj_query out;
+        if (!skip || !skip[i]) {
+            const float4* m4 = reinterpret_cast<const float4*>(mps + i);
+            const float4 a = m4[0], c = m4[1];
+            const float P[3] = {a.x, a.y, a.z}, Pn[3] = {c.x, c.y, c.z};
+            int oct = 0;
+            float ang = 0.0f;
+            if (FRAME) {
+                if (MODE == ORBX_PROJ_LAST_FRAME) oct = keys[i].octave;
+                ang = keys[i].angle;
+            }
+            act = project_query<MODE>(jobs[j], P, a.w, Pn, c.w, oct, ang, out);
+        }
+        float4 o0, o1;
+        if (act) {
+            o0 = make_float4(out.u, out.v, out.ur, out.radius);
+            o1 = make_float4(__int_as_float(out.min_level), __int_as_float(out.max_level),
+                             __int_as_float(out.pred_level), out.angle);
+        } else {
+            o0 = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+            o1 = make_float4(__int_as_float(-1), __int_as_float(-1), __int_as_float(-1), 0.0f);
+        }
+        float4* q4 = reinterpret_cast<float4*>(q + i);
+        q4[0] = o0;
+        q4[1] = o1;
+    }
+    if (nactive) {
+        const uint64_t m = __ballot(act);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&nactive[j], (int)__popcll(m));
+    }
+}
+
+bool proj_mode_ok(int32_t mode) {
+    return mode == ORBX_PROJ_KF_SCW || mode == ORBX_PROJ_LAST_FRAME ||
+           mode == ORBX_PROJ_KEYFRAME || mode == ORBX_PROJ_FUSE || mode == ORBX_PROJ_FUSE_SCW ||
+           mode == ORBX_PROJ_SIM3;
+}
+constexpr int32_t PROJECT_MAX_POINTS = 1 << 24;
+
 // The depth image arguments of the RGB-D entry points: element size, or 0 when refused.
 int depth_elem(int type) { return type == ORBX_DEPTH_U16 ? 2 : type == ORBX_DEPTH_F32 ? 4 : 0; }
 // Tracking.cc:244: the image is scaled when fabs(mDepthMapFactor - 1.0f) > 1e-5 or it is not
@@ -738,6 +907,91 @@ orbx_status orbx_is_in_frustum(const orbx_frame_pose* frame, const orbx_map_poin
         s = ORBX_ERR_DEVICE;
     if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
     if (s == ORBX_OK && nvisible) *nvisible = cnt;
+    return s;
+}
+
+orbx_status orbx_project_map_points_batch_device(
+    int32_t mode, const orbx_proj_job* d_jobs, int32_t njobs, const orbx_map_point* d_mps,
+    const int32_t* d_mp_off, int32_t max_mps, const orbx_keypoint* d_src_keys,
+    const uint8_t* d_skip, orbx_proj_query* d_q, int32_t* d_nactive, void* stream) {
+    if (!proj_mode_ok(mode) || njobs < 0 || njobs > 65535 || max_mps < 0 ||
+        max_mps > PROJECT_MAX_POINTS)
+        return ORBX_ERR_INVALID;
+    if ((mode == ORBX_PROJ_LAST_FRAME || mode == ORBX_PROJ_KEYFRAME) && !d_src_keys)
+        return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_jobs || !d_mp_off || (max_mps > 0 && (!d_mps || !d_q))) return ORBX_ERR_INVALID;
+    // the MapPoint and query records move as 16-byte accesses
+    if ((((uintptr_t)d_mps) | ((uintptr_t)d_q)) & 15) return ORBX_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (d_nactive && !HIPOK(hipMemsetAsync(d_nactive, 0, 4 * (size_t)njobs, st)))
+        return ORBX_ERR_DEVICE;
+    if (max_mps == 0) return ORBX_OK;
+    const dim3 grid((max_mps + 255) / 256, njobs), block(256);
+#define ORBX_LAUNCH_PROJECT(M)                                                                  \
+    case M:                                                                                     \
+        hipLaunchKernelGGL(k_project<M>, grid, block, 0, st, d_jobs, d_mps, d_mp_off,           \
+                           d_src_keys, d_skip, d_q, d_nactive);                                 \
+        break;
+    switch (mode) {
+        ORBX_LAUNCH_PROJECT(ORBX_PROJ_KF_SCW)
+        ORBX_LAUNCH_PROJECT(ORBX_PROJ_LAST_FRAME)
+        ORBX_LAUNCH_PROJECT(ORBX_PROJ_KEYFRAME)
+        ORBX_LAUNCH_PROJECT(ORBX_PROJ_FUSE)
+        ORBX_LAUNCH_PROJECT(ORBX_PROJ_FUSE_SCW)
+        ORBX_LAUNCH_PROJECT(ORBX_PROJ_SIM3)
+    }
+#undef ORBX_LAUNCH_PROJECT
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+orbx_status orbx_project_map_points(int32_t mode, const orbx_proj_job* job,
+                                    const orbx_map_point* mps, int32_t n,
+                                    const orbx_keypoint* src_keys, const uint8_t* skip,
+                                    orbx_proj_query* q, int32_t* nactive, int device) {
+    if (!proj_mode_ok(mode) || !job || n < 0 || n > PROJECT_MAX_POINTS ||
+        (n > 0 && (!mps || !q)))
+        return ORBX_ERR_INVALID;
+    const bool keyed = mode == ORBX_PROJ_LAST_FRAME || mode == ORBX_PROJ_KEYFRAME;
+    if (keyed && !src_keys) return ORBX_ERR_INVALID;
+    if (n == 0) {
+        if (nactive) *nactive = 0;
+        return ORBX_OK;
+    }
+    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_j = 0, o_off = al(sizeof(orbx_proj_job)), o_cnt = o_off + 256,
+                 o_mp = o_cnt + 256, o_sk = o_mp + al(sizeof(orbx_map_point) * (size_t)n),
+                 o_k = o_sk + al((size_t)n),
+                 o_q = o_k + (keyed ? al(sizeof(orbx_keypoint) * (size_t)n) : 0),
+                 end = o_q + sizeof(orbx_proj_query) * (size_t)n;
+    ScratchLease L(device);
+    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    hipStream_t st = L.s->st;
+    uint8_t* d = L.s->buf.as<uint8_t>();
+    const int32_t off[2] = {0, n};
+    int32_t cnt = 0;
+    orbx_status s = ORBX_OK;
+    if (!HIPOK(hipMemcpyAsync(d + o_j, job, sizeof(*job), hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_off, off, sizeof(off), hipMemcpyHostToDevice, st)) ||
+        !HIPOK(hipMemcpyAsync(d + o_mp, mps, sizeof(orbx_map_point) * (size_t)n,
+                              hipMemcpyHostToDevice, st)) ||
+        (skip && !HIPOK(hipMemcpyAsync(d + o_sk, skip, (size_t)n, hipMemcpyHostToDevice, st))) ||
+        (keyed && !HIPOK(hipMemcpyAsync(d + o_k, src_keys, sizeof(orbx_keypoint) * (size_t)n,
+                                        hipMemcpyHostToDevice, st))))
+        s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK)
+        s = orbx_project_map_points_batch_device(
+            mode, (const orbx_proj_job*)(d + o_j), 1, (const orbx_map_point*)(d + o_mp),
+            (const int32_t*)(d + o_off), n, keyed ? (const orbx_keypoint*)(d + o_k) : nullptr,
+            skip ? d + o_sk : nullptr, (orbx_proj_query*)(d + o_q), (int32_t*)(d + o_cnt), st);
+    if (s == ORBX_OK &&
+        (!HIPOK(hipMemcpyAsync(q, d + o_q, sizeof(orbx_proj_query) * (size_t)n,
+                               hipMemcpyDeviceToHost, st)) ||
+         !HIPOK(hipMemcpyAsync(&cnt, d + o_cnt, 4, hipMemcpyDeviceToHost, st))))
+        s = ORBX_ERR_DEVICE;
+    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
+    if (s == ORBX_OK && nactive) *nactive = cnt;
     return s;
 }
 

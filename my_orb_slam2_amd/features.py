@@ -311,6 +311,61 @@ def is_in_frustum_batch_device(d_frames, nframes: int, d_mps, d_mp_off, max_mps:
         float(viewing_cos_limit), float(th), ptr(d_q), ptr(d_nvisible), ctypes.c_void_p(stream)))
 
 
+# ---- the projection loops of the other six projection modes (include/orbx_frame.h) ------------
+
+# orbx_proj_job: the view projected into, SIM3's first transform / LAST_FRAME's last-frame pose,
+# CurrentFrame.mb and bMono (LAST_FRAME), th (240 bytes)
+PROJ_JOB_DTYPE = np.dtype([("cam", FRAME_POSE_DTYPE), ("pre_R", "<f4", 9), ("pre_t", "<f4", 3),
+                           ("mb", "<f4"), ("th", "<f4"), ("mono", "<i4"),
+                           ("reserved", "<i4", 3)])
+
+
+def proj_job(cam, th: float, pre_R=None, pre_t=None, mb: float = 0.0,
+             mono: bool = True) -> np.ndarray:
+    """One orbx_proj_job record.  `cam` is a frame_pose record of the view projected into (the
+    current Frame, the KeyFrame with Rcw / tcw / Ow decomposed from Scw, or for SIM3 Rcw = sR21,
+    tcw = t21); pre_R / pre_t: SIM3's (R1w, t1w) or LAST_FRAME's (Rlw, tlw); mb / mono:
+    LAST_FRAME's CurrentFrame.mb and bMono."""
+    j = np.zeros((), PROJ_JOB_DTYPE)
+    j["cam"] = np.asarray(cam, FRAME_POSE_DTYPE).reshape(())
+    j["pre_R"] = np.eye(3, dtype=np.float32).reshape(9) if pre_R is None else \
+        np.asarray(pre_R, np.float32).reshape(9)
+    j["pre_t"] = 0 if pre_t is None else np.asarray(pre_t, np.float32).reshape(3)
+    j["mb"], j["th"], j["mono"] = np.float32(mb), np.float32(th), int(bool(mono))
+    return j
+
+
+def project_map_points(mode: int, job: np.ndarray, mps: np.ndarray, src_keys=None, skip=None,
+                       device: int = 0):
+    """The per-MapPoint projection loop of one projection search on the GPU (k_project; every
+    orbx_proj_mode but PROJ_FRAME_MAPPOINTS, which is is_in_frustum): returns the queries
+    (PROJ_QUERY_DTYPE, radius -1 = rejected or skipped) and the active count.  src_keys
+    (KEYPOINT_DTYPE, point i's source feature) is needed by PROJ_LAST_FRAME / PROJ_KEYFRAME."""
+    from ._lib import check, load, ptr
+    jb = np.ascontiguousarray(job, PROJ_JOB_DTYPE).reshape(())
+    m = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+    ks = None if src_keys is None else np.ascontiguousarray(src_keys, KEYPOINT_DTYPE)
+    if (sk is not None and len(sk) != len(m)) or (ks is not None and len(ks) != len(m)):
+        raise ValueError("one skip flag and one source keypoint per MapPoint")
+    q = np.zeros(len(m), PROJ_QUERY_DTYPE)
+    na = ctypes.c_int32(0)
+    check("orbx_project_map_points", load().orbx_project_map_points(
+        int(mode), ptr(jb), ptr(m), len(m), ptr(ks), ptr(sk), ptr(q), ctypes.byref(na), device))
+    return q, na.value
+
+
+def project_map_points_batch_device(mode: int, d_jobs, njobs: int, d_mps, d_mp_off, max_mps: int,
+                                    d_src_keys, d_skip, d_q, d_nactive=None, stream: int = 0):
+    """The same for `njobs` jobs on device arrays (torch tensors): job j's MapPoints at
+    [d_mp_off[j], d_mp_off[j+1]) of d_mps, its constants in d_jobs[j] (PROJ_JOB_DTYPE), queries
+    into d_q at the same indices, active counts into d_nactive[j]."""
+    from ._lib import check, load, ptr
+    check("orbx_project_map_points_batch_device", load().orbx_project_map_points_batch_device(
+        int(mode), ptr(d_jobs), int(njobs), ptr(d_mps), ptr(d_mp_off), int(max_mps),
+        ptr(d_src_keys), ptr(d_skip), ptr(d_q), ptr(d_nactive), ctypes.c_void_p(stream)))
+
+
 # ---- RGB-D frames (include/orbx_frame.h) -----------------------------------------------------
 
 # orbx_depth_type

@@ -25,8 +25,9 @@ import numpy as np
 from ._lib import KEYPOINT_DTYPE, check
 from .extractor import ORBextractor
 from .features import (CLOSE_MAX_FEATURES, FRAME_GRID_COLS, FRAME_GRID_ROWS, PROJ_FRAME_MAPPOINTS,
-                       PROJ_QUERY_DTYPE, FeatureSetC, _depth_type, assign_grid_batch_device,
-                       close_points_batch_device, image_bounds, is_in_frustum_batch_device,
+                       PROJ_LAST_FRAME, PROJ_QUERY_DTYPE, FeatureSetC, _depth_type,
+                       assign_grid_batch_device, close_points_batch_device, image_bounds,
+                       is_in_frustum_batch_device, project_map_points_batch_device,
                        rgbd_frame_geometry_batch_device, undistort_keypoints_batch_device)
 from .matcher import ORBmatcher
 
@@ -106,6 +107,35 @@ class MonoTrackBatch:
         set, i.e. bad or already matched), nToMatch into d_nvisible[j]."""
         is_in_frustum_batch_device(d_frames, self.batch, d_mps, d_mp_off, max_mps, d_skip, d_q,
                                    d_nvisible, 0.5, th, stream)
+
+    def project_last_frame(self, d_jobs, d_mps, d_mp_off, max_mps: int, d_src_keys, d_skip, d_q,
+                           d_nactive=None, stream: int = 0):
+        """TrackWithMotionModel's projection loop for every frame (ORBmatcher.cc:1402-1458):
+        frame j's last-frame MapPoints at [d_mp_off[j], d_mp_off[j+1]) of d_mps, the last
+        frame's feature of each in d_src_keys (octave and angle are read), the job constants in
+        d_jobs[j] (PROJ_JOB_DTYPE: the current pose as `cam`, the last frame's Rlw / tlw as
+        pre_R / pre_t, mb, mono, th); d_skip marks slots without a MapPoint and outliers
+        (:1419-1421).  Writes the SearchByProjection queries into d_q (radius -1: rejected or
+        skipped) and the active count into d_nactive[j]."""
+        project_map_points_batch_device(PROJ_LAST_FRAME, d_jobs, self.batch, d_mps, d_mp_off,
+                                        max_mps, d_src_keys, d_skip, d_q, d_nactive, stream)
+
+    def track_with_motion_model(self, d_jobs, d_mps, d_mp_off, max_mps: int, d_src_keys, d_skip,
+                                d_q, d_qdesc, d_match, d_nmatches, d_claimed=None,
+                                d_nactive=None, stream: int = 0):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) for every frame of the last
+        ``frames`` call (Tracking.cc:915-946, ORBmatcher.cc:1392-1538): ``project_last_frame``,
+        then the batched LAST_FRAME search on the same stream, queries indexed like the
+        MapPoints (d_mp_off).  d_match holds the frame-local feature of each MapPoint or -1; a
+        mask of those features is the d_claimed ``search_local_points`` takes afterwards.
+        The batched search has no per-query ORBX_QF_NO_CLAIM: temporal points without
+        observations (Tracking::UpdateLastFrame) go through orbx_search_by_projection_ex
+        (ORBmatcher.search_by_projection_ex) frame by frame, as before."""
+        self.project_last_frame(d_jobs, d_mps, d_mp_off, max_mps, d_src_keys, d_skip, d_q,
+                                d_nactive, stream)
+        self.matcher.search_by_projection_batch_device(
+            PROJ_LAST_FRAME, self, d_qdesc, d_q, d_mp_off, d_match, d_nmatches, d_claimed,
+            stream=stream)
 
     def __call__(self, images, d_qdesc, d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
                  stream: int = 0, local_map=None):
