@@ -308,6 +308,28 @@ const char* orbx_kernel_name(int id);
 orbx_status orbx_extractor_launch_info(const orbx_extractor* h, int batch, int* strip_rows,
                                        int* stereo_split);
 
+/* The regime a batched call of `batch` images would run in after orbx_extractor_prepare: the
+ * content-independent choices of the FAST / octree / orientation launches (host only, no
+ * device work; the launcher evaluates the same expressions).  The directed tests assert the
+ * regime they mean with it before they rely on it. */
+typedef struct {
+    int32_t octree_threads;       /* k_octree threads per list (128 or 256)                   */
+    int32_t packed;               /* 1: child counts packed two to a word (while the level's
+                                     candidates fit kcap; wide counts otherwise)              */
+    int32_t ncap, kcap;           /* octree node / in-LDS candidate capacities in effect      */
+    int32_t spatial;              /* 1: k_orient_desc walks keypoints in the spatial order    */
+    int32_t fast_cells_per_wave;  /* k_fast cells per wave: 4, 2 or 1                         */
+    int32_t chain;                /* 1: the pyramid is one chain launch (in_place calls only) */
+    int32_t nlevels;
+    int32_t cand_cap[16];         /* per level: FAST candidate slots (candidates beyond kcap
+                                     move the level's octree to the global scratch)           */
+    int32_t nfeat[16];            /* per level: the octree's quota (mnFeaturesPerLevel)       */
+} orbx_regime_info;
+/* in_place != 0: the call extracts the images already in the level-0 slots
+ * (orbx_extract_batch_resident, orbx_extract). */
+orbx_status orbx_extractor_regime_info(const orbx_extractor* h, int batch, int in_place,
+                                       orbx_regime_info* out);
+
 /* Library / device information.  orbx_version() ends in "orbx-src:<hash>", the hash of the
  * sources the library was built from (my_orb_slam2_amd/build.py). */
 const char* orbx_version(void);

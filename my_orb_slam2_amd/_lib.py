@@ -55,6 +55,15 @@ class HostPyramid(ctypes.Structure):
                 ("step", ctypes.c_size_t * 16)]
 
 
+class RegimeInfo(ctypes.Structure):
+    """orbx_regime_info (include/orbx.h)."""
+    _fields_ = [("octree_threads", ctypes.c_int32), ("packed", ctypes.c_int32),
+                ("ncap", ctypes.c_int32), ("kcap", ctypes.c_int32), ("spatial", ctypes.c_int32),
+                ("fast_cells_per_wave", ctypes.c_int32), ("chain", ctypes.c_int32),
+                ("nlevels", ctypes.c_int32), ("cand_cap", ctypes.c_int32 * 16),
+                ("nfeat", ctypes.c_int32 * 16)]
+
+
 # name -> (restype, argtypes); the exported C ABI (include/orbx.h)
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -96,6 +105,7 @@ SIGNATURES = {
     "orbx_profile_collect": (_i, [_vp, _vp, _vp]),
     "orbx_kernel_name": (ctypes.c_char_p, [_i]),
     "orbx_extractor_launch_info": (_i, [_vp, _i, _vp, ctypes.POINTER(_i)]),
+    "orbx_extractor_regime_info": (_i, [_vp, _i, _i, ctypes.POINTER(RegimeInfo)]),
     # include/orbx_match.h
     "orbx_matcher_create": (_i, [_vp, ctypes.POINTER(_vp)]),
     "orbx_matcher_destroy": (_i, [_vp]),

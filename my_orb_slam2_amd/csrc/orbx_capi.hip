@@ -306,6 +306,15 @@ static int fast_cells_per_wave(int ncells, int batch, int ncu) {
     return nc;
 }
 
+// The other batch-size switches of extract_launch (orbx_extractor_regime_info reports them).
+static int octree_small(int batch) { return batch <= OCT_SMALL_BATCH ? 1 : 0; }
+static int side_mode_of(const orbx_extractor* h, int batch) {
+    return (h->side_auto && batch < SIDE_MIN_BATCH) ? 0 : h->side_mode;
+}
+static int chain_of(const orbx_extractor* h, int in_place, int side_mode, int batch) {
+    return (h->hg.chain_ok && in_place && side_mode == 0 && batch <= CHAIN_MAX_BATCH) ? 1 : 0;
+}
+
 // Stream captures (extract1_graph) against waits on an event recorded on another stream: the
 // runtime refuses hipStreamWaitEvent (hipErrorStreamCaptureIsolation) while the stream the event
 // was last recorded on is being captured, even when the record came before the capture began.
@@ -1012,7 +1021,7 @@ ExtractLaunch extract_launch(orbx_extractor* h, const uint8_t* d_imgs, const uin
     a.octree_lds1 = h->octree_lds1;
     a.kcap_small = h->kcap_small;
     a.octree_lds_small = h->octree_lds_small;
-    a.oct_small = batch <= OCT_SMALL_BATCH ? 1 : 0;
+    a.oct_small = octree_small(batch);
     a.fast_nc = fast_cells_per_wave(h->hg.n_cells, batch, h->ncu);
     a.kps = h->d_kps.as<float>();
     a.desc = h->d_desc.as<uint8_t>();
@@ -1025,12 +1034,10 @@ ExtractLaunch extract_launch(orbx_extractor* h, const uint8_t* d_imgs, const uin
     // small batch's kernels are latency chains, and the fork / join events between the two
     // streams cost more than the overlap gives (an explicit orbx_extractor_set_overlap applies
     // at every batch size)
-    a.side_mode = (h->side_auto && batch < SIDE_MIN_BATCH) ? 0
-                                                                                     : h->side_mode;
+    a.side_mode = side_mode_of(h, batch);
     a.side_at = h->side_at;
     a.side_lv = h->side_lv;
-    a.chain = (h->hg.chain_ok && a.in_place && a.side_mode == 0 &&
-               batch <= CHAIN_MAX_BATCH) ? 1 : 0;
+    a.chain = chain_of(h, a.in_place, a.side_mode, batch);
     strip_heights(h, batch, a.sth);
     return a;
 }
@@ -1497,6 +1504,30 @@ orbx_status orbx_extractor_launch_info(const orbx_extractor* h, int batch, int* 
     if (strip_rows)
         for (int l = 0; l < h->hg.nlevels; ++l) strip_rows[l] = h->hg.lv[l].strip ? sth[l] : 0;
     if (stereo_split) *stereo_split = stereo_split_of(std::max(batch / 2, 1));
+    return ORBX_OK;
+}
+
+orbx_status orbx_extractor_regime_info(const orbx_extractor* h, int batch, int in_place,
+                                       orbx_regime_info* out) {
+    if (!h || !out || batch < 1) return ORBX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->have_geom) return ORBX_ERR_STATE;
+    const Geometry& G = h->hg;
+    static_assert(sizeof(out->cand_cap) / sizeof(out->cand_cap[0]) == ORBX_MAX_LEVELS, "levels");
+    memset(out, 0, sizeof(*out));
+    const int small = octree_small(batch);
+    out->octree_threads = octree_threads(batch, G.nlevels);
+    out->packed = small ? 0 : 1;
+    out->ncap = h->ncap;
+    out->kcap = small ? h->kcap_small : h->kcap;
+    out->spatial = orient_spatial(batch) ? 1 : 0;
+    out->fast_cells_per_wave = fast_cells_per_wave(G.n_cells, batch, h->ncu);
+    out->chain = chain_of(h, in_place ? 1 : 0, side_mode_of(h, batch), batch);
+    out->nlevels = G.nlevels;
+    for (int l = 0; l < G.nlevels; ++l) {
+        out->cand_cap[l] = G.lv[l].cand_cap;
+        out->nfeat[l] = G.lv[l].nfeat;
+    }
     return ORBX_OK;
 }
 

@@ -1039,7 +1039,9 @@ __global__ __launch_bounds__(NT) void k_octree(const Geometry* __restrict__ g,
     int part = 0;
     for (int c = tid; c < L.ncells; c += NT) part += cc[c] & 0xFFFF;
     const int ncand = block_sum<NT / 64>(part, sm.tmp);
-    if (ncand == 0 || L.n_ini < 1 || L.nfeat <= 0) {
+    // (a quota of 0 still runs: the reference's loop tests the list size against N only after
+    // its first round of splits, so such a level keeps up to four keypoints per root)
+    if (ncand == 0 || L.n_ini < 1) {
         if (tid == 0) ocnt[b * g->nlevels + level] = 0;
         return;
     }
@@ -1423,14 +1425,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OD_WPE))) v
 // ----------------------------------------------------------------------------------------
 // launch sequence
 // ----------------------------------------------------------------------------------------
+int octree_threads(int batch, int nlevels) {
+    return (long long)batch * nlevels <= 256 ? OCT_NT_SMALL : OCT_NT;
+}
+
+bool orient_spatial(int batch) { return batch >= OD_SPATIAL_MIN_BATCH; }
+
 hipError_t launch_extract(const ExtractLaunch& a, hipStream_t st) {
     const Geometry& G = *a.hg;
     KernelTimer dummy;
     KernelTimer& T = a.timer ? *a.timer : dummy;
-    const int nt = (long long)a.batch * G.nlevels <= 256 ? OCT_NT_SMALL : OCT_NT;
+    const int nt = octree_threads(a.batch, G.nlevels);
     // the spatial orientation order pays on large batches only (its L1 / L2 reuse); a lone
     // frame keeps the list order and skips the octree's bucket pass (operm = null)
-    uint16_t* const operm = a.batch >= OD_SPATIAL_MIN_BATCH ? a.operm : nullptr;
+    uint16_t* const operm = orient_spatial(a.batch) ? a.operm : nullptr;
     auto fast = [&](int c0, int c1, hipStream_t s) {
         if (c1 <= c0) return;
         const int nc = a.fast_nc;

@@ -10,8 +10,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (BatchView, ExtractorParams, HostPyramid, KERNELS, KEYPOINT_DTYPE, check, load,
-                   ptr)
+from ._lib import (BatchView, ExtractorParams, HostPyramid, KERNELS, KEYPOINT_DTYPE, RegimeInfo,
+                   check, load, ptr)
 
 
 class _DeviceArray:
@@ -257,6 +257,20 @@ class ORBextractor:
         check("orbx_extractor_launch_info", self._L.orbx_extractor_launch_info(
             self._h, batch, ptr(rows), ctypes.byref(split)))
         return rows, split.value
+
+    def regime_info(self, batch: int, in_place: bool = False) -> dict:
+        """The regime a batched call of `batch` images at the prepared size runs in
+        (include/orbx.h orbx_extractor_regime_info): octree_threads, packed, ncap, kcap,
+        spatial, fast_cells_per_wave, chain, and per level cand_cap and nfeat.  in_place: the
+        call extracts the level-0 slots (``extract_batch_resident``, ``extractor(image)``)."""
+        r = RegimeInfo()
+        check("orbx_extractor_regime_info", self._L.orbx_extractor_regime_info(
+            self._h, batch, int(in_place), ctypes.byref(r)))
+        out = {k: int(getattr(r, k)) for k in ("octree_threads", "packed", "ncap", "kcap",
+                                               "spatial", "fast_cells_per_wave", "chain")}
+        out["cand_cap"] = [int(v) for v in r.cand_cap[:r.nlevels]]
+        out["nfeat"] = [int(v) for v in r.nfeat[:r.nlevels]]
+        return out
 
     def batch_view(self) -> BatchView:
         v = BatchView()

@@ -8,6 +8,7 @@ import math
 import numpy as np
 import pytest
 
+from extract_cases import octree_reference   # DistributeOctTree on Python lists (shared)
 from my_orb_slam2_amd import synth
 
 CIRCLE = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3),
@@ -156,85 +157,6 @@ def gaussian_reference(src, simd):
 def test_gaussian_matches_restatement(oracle_mod, simd, size):
     src = synth.frame(3, *size)
     assert np.array_equal(oracle_mod.gaussian7(src, simd), gaussian_reference(src, simd))
-
-
-def octree_reference(cands, minX, maxX, minY, maxY, N):
-    """DistributeOctTree (src/ORBextractor.cc:539-765) on Python lists; node identity
-    = allocation sequence number (the documented tie-break)."""
-    if not cands:
-        return []
-    seq = [0]
-    nIni = int(np.round(np.float32(maxX - minX) / np.float32(maxY - minY)))
-    if nIni < 1:
-        return []
-    hX = np.float32(maxX - minX) / np.float32(nIni)
-
-    def node(x0, y0, x1, y1, keys):
-        seq[0] += 1
-        return {"r": (x0, y0, x1, y1), "k": keys, "more": len(keys) != 1, "seq": seq[0]}
-
-    roots = [node(int(hX * np.float32(i)), 0, int(hX * np.float32(i + 1)), maxY - minY, [])
-             for i in range(nIni)]
-    for c in cands:
-        roots[int(np.float32(c[0]) / hX)]["k"].append(c)
-    for r in roots:
-        r["more"] = len(r["k"]) != 1
-    lst = [r for r in roots if r["k"]]
-
-    def divide(n):
-        x0, y0, x1, y1 = n["r"]
-        hx = int(math.ceil(np.float32(x1 - x0) / np.float32(2)))
-        hy = int(math.ceil(np.float32(y1 - y0) / np.float32(2)))
-        sx, sy = x0 + hx, y0 + hy
-        rects = [(x0, y0, sx, sy), (sx, y0, x1, sy), (x0, sy, sx, y1), (sx, sy, x1, y1)]
-        parts = [[], [], [], []]
-        for c in n["k"]:
-            parts[(0 if c[1] < sy else 2) if c[0] < sx else (1 if c[1] < sy else 3)].append(c)
-        return [(rects[q], parts[q]) for q in range(4)]
-
-    finish = False
-    while not finish:
-        prev = len(lst)
-        new_front, rest, vsize = [], [], []
-        for n in lst:
-            if not n["more"]:
-                rest.append(n)
-                continue
-            for rect, keys in divide(n):
-                if keys:
-                    ch = node(*rect, keys)
-                    new_front.insert(0, ch)
-                    if len(keys) > 1:
-                        vsize.append(ch)
-        lst = new_front + rest
-        if len(lst) >= N or len(lst) == prev:
-            finish = True
-        elif len(lst) + 3 * len(vsize) > N:
-            while not finish:
-                prev = len(lst)
-                order = sorted(vsize, key=lambda n: (len(n["k"]), n["seq"]))
-                vsize = []
-                for n in reversed(order):
-                    kids = []
-                    for rect, keys in divide(n):
-                        if keys:
-                            ch = node(*rect, keys)
-                            kids.insert(0, ch)
-                            if len(keys) > 1:
-                                vsize.append(ch)
-                    lst = kids + [m for m in lst if m is not n]
-                    if len(lst) >= N:
-                        break
-                if len(lst) >= N or len(lst) == prev:
-                    finish = True
-    out = []
-    for n in lst:
-        best = n["k"][0]
-        for c in n["k"][1:]:
-            if c[2] > best[2]:
-                best = c
-        out.append(best)
-    return out
 
 
 @pytest.mark.parametrize("seed,size,nf", [(0, (1241, 376), 2000), (4, (640, 480), 1000),
