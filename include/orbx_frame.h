@@ -74,7 +74,7 @@ typedef struct {
  * of a MapPoint in view is the one SearchByProjection(Frame&, vpMapPoints, th) builds from
  * mTrackProjX / mTrackProjY / mTrackProjXR / mnTrackScaleLevel / mTrackViewCos
  * (ORBmatcher.cc:46-80). */
-typedef struct {
+typedef struct orbx_frame_pose {
     float Rcw[9];
     float tcw[3];
     float Ow[3];

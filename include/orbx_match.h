@@ -260,6 +260,102 @@ orbx_status orbx_search_for_triangulation_batch_device(
     const float* scale, int32_t nlevels, int32_t only_stereo, const int32_t* d_job_off,
     int32_t* d_match12, int32_t* d_nmatches, void* stream);
 
+/* ---- The per-match loop behind SearchForTriangulation: LocalMapping::CreateNewMapPoints,
+ * src/LocalMapping.cc:356-507 (parallax test :370-394, linear triangulation :398-413 or
+ * KeyFrame::UnprojectStereo :416-423, depth signs :430-436, reprojection chi2 :439-489, scale
+ * consistency :492-507).  What stays with the caller per job: the baseline / median-depth skip
+ * (:308-327), ComputeF12 (:331), ratio_factor = 1.5f * mfScaleFactor (:294); per success:
+ * new MapPoint, AddObservation, AddMapPoint (:510-525). ----
+ *
+ * One code per exit of the loop body: the three ways to succeed, the empty slot, then the
+ * `continue` statements. */
+typedef enum {
+    ORBX_TRI_OK_TRIANGULATED = 0, /* :394-415 the SVD branch, all tests passed                 */
+    ORBX_TRI_OK_STEREO1 = 1,      /* :416-419 mpCurrentKeyFrame->UnprojectStereo(idx1)         */
+    ORBX_TRI_OK_STEREO2 = 2,      /* :420-423 pKF2->UnprojectStereo(idx2)                      */
+    ORBX_TRI_NO_MATCH = 3,        /* the slot holds -1 (no pair), or the slot was refused      */
+    ORBX_TRI_LOW_PARALLAX = 4,    /* :424-425; also UnprojectStereo's empty Mat (depth <= 0)   */
+    ORBX_TRI_W_ZERO = 5,          /* :409-410 x3D.at<float>(3) == 0                            */
+    ORBX_TRI_BEHIND_1 = 6,        /* :431-432 z1 <= 0                                          */
+    ORBX_TRI_BEHIND_2 = 7,        /* :435-436 z2 <= 0                                          */
+    ORBX_TRI_REPROJ_1 = 8,        /* :450-451 / :461-462                                       */
+    ORBX_TRI_REPROJ_2 = 9,        /* :476-477 / :487-488                                       */
+    ORBX_TRI_DIST_ZERO = 10,      /* :498-499                                                  */
+    ORBX_TRI_SCALE = 11,          /* :506-507                                                  */
+    ORBX_TRI_CODE_COUNT = 12
+} orbx_tri_code;
+
+typedef struct orbx_frame_pose orbx_frame_pose;   /* include/orbx_frame.h */
+
+/* cosParallaxStereo of every feature of one keyframe (:387, :389), host only:
+ * out[i] = (float)cos(2 * atan2(mb / 2, depth[i])) with mb / 2 a float division and libm's double
+ * atan2 and cos.  Computed once per keyframe when it is uploaded: the device never evaluates a
+ * double cos or atan2, and the term is exactly what the host's libm gives.
+ * (With libstdc++ and the `using namespace std` the reference's DBoW2 headers bring in, the
+ * unqualified calls at :387 resolve to the float overloads; glibc 2.35's float forms differ from
+ * this by one unit in the last place for about 0.16 % of depths.  A caller that wants those fills
+ * the table itself: the kernel only reads it.)  n < 0 or a NULL array with n > 0:
+ * ORBX_ERR_INVALID. */
+orbx_status orbx_parallax_stereo_cos(float mb, const float* depth, int32_t n, float* out);
+
+/* The loop for njobs keyframe pairs (kf1[j] = mpCurrentKeyFrame, kf2[j] = pKF2) of `db`, fed by
+ * exactly what orbx_search_for_triangulation_batch_device wrote: d_match12 / d_job_off, one slot
+ * per KF1 feature holding the KF2 feature or -1.  On one stream the two calls chain with no host
+ * step.
+ *   d_poses       one orbx_frame_pose per keyframe of db; read: Rcw, tcw, Ow, fx, fy, cx, cy, mbf,
+ *                 scale[] (mvScaleFactors; mvLevelSigma2[o] = scale[o] * scale[o],
+ *                 ORBextractor.cc:421-422) and nlevels
+ *   d_depth       mvDepth, d_cos_stereo: orbx_parallax_stereo_cos of it; per feature of db, indexed
+ *                 like db->keys (keyframe k's at feat_off[k])
+ *   d_keys_raw    mvKeys (KeyFrame::UnprojectStereo reads the raw keypoint, KeyFrame.cc:634-635);
+ *                 NULL: db->keys.  db->keys is mvKeysUn, db->u_right mvuRight (NULL: monocular)
+ *   mb            the baseline d_cos_stereo was built with; the kernel reads the table only
+ *   ratio_factor  1.5f * mpCurrentKeyFrame->mfScaleFactor
+ *   d_status      [slot] an orbx_tri_code; -1 slots get ORBX_TRI_NO_MATCH
+ *   d_x3d         [3 * slot ..] x3D, written on the three OK codes only, otherwise untouched
+ *   d_nnew        [njobs] the OK slots of each job (nnew of :525)
+ * Arithmetic: xn from float products with a 1.0 third entry; ray = Rwc * xn in cv::gemm's
+ * small-matrix form; ray.dot(ray) and cv::norm in double; cosParallaxRays < 0.9998, 5.991 *
+ * sigmaSquare and 7.8 * sigmaSquare compared in double; invz = (float)(1.0 / z); :388 is an
+ * `else if` (with both features stereo only cosParallaxStereo1 is read); :482 uses the current
+ * keyframe's mbf for keyframe 2.  Restated from OpenCV 3.2 [unverified-OpenCV]:
+ * the rows of A (cv::addWeighted in double), cv::SVD::compute (one-sided Jacobi, at most 30
+ * sweeps) and x3D.rowRange(0,3) / w (Mat::convertTo).  hypot is glibc 2.35's.
+ * UnprojectStereo with depth <= 0 returns an empty Mat, on which the reference's next statement
+ * throws; the slot gets ORBX_TRI_LOW_PARALLAX (the exit for "no point could be formed").
+ * Statuses: m, db, d_poses, d_depth, d_cos_stereo, d_kf1, d_kf2, d_job_off, d_match12, d_status,
+ * d_x3d or d_nnew NULL (with njobs > 0), njobs < 0 or > 65535, db->max_feat outside [0, 32768],
+ * mb negative or NaN: ORBX_ERR_INVALID; njobs == 0: ORBX_OK, nothing is touched.  What only the
+ * device can see is refused per slot: a keyframe index outside [0, nkf) or a pose whose nlevels
+ * is outside [1, 16] (the whole job), a match outside KF2's features, or an octave outside
+ * [0, nlevels): the slots get ORBX_TRI_NO_MATCH, nothing of them is read, and the matcher is
+ * flagged, so the next orbx_matcher_sync returns ORBX_ERR_CAPACITY. */
+orbx_status orbx_triangulate_matches_batch_device(
+    orbx_matcher* m, const orbx_kf_db* db, int32_t njobs, const int32_t* d_kf1,
+    const int32_t* d_kf2, const orbx_frame_pose* d_poses, const float* d_depth,
+    const float* d_cos_stereo, const orbx_keypoint* d_keys_raw, float mb, float ratio_factor,
+    const int32_t* d_job_off, const int32_t* d_match12, int32_t* d_status, float* d_x3d,
+    int32_t* d_nnew, void* stream);
+
+/* One keyframe pair from host arrays (copied to the device for the call), taking the (idx1, idx2)
+ * list orbx_search_for_triangulation returns: status[p] and x3d[3p ..] belong to pair p, x3d
+ * written on the OK codes only; *nnew (optional) the OK count.  keys: mvKeysUn; keys_raw: mvKeys
+ * (NULL: keys); u_right NULL: monocular; depth (mvDepth) may be NULL where u_right is.
+ * cos_stereo1 / cos_stereo2 NULL: orbx_parallax_stereo_cos(mb, depth) is computed here.
+ * The checks run before the device is touched.  ORBX_ERR_INVALID: a NULL pose, keys, pairs,
+ * status or x3d (with npairs > 0), a negative count, depth NULL with u_right given, mb negative or
+ * NaN, a pair index outside its keyframe, an idx1 that occurs twice, an octave of a paired
+ * feature outside [0, nlevels), nlevels < 1.  nlevels > 16 or a keyframe above 32768 features:
+ * ORBX_ERR_UNSUPPORTED.  npairs == 0: ORBX_OK.  Without a GPU: ORBX_ERR_DEVICE.  Calls are
+ * serialised inside the library. */
+orbx_status orbx_triangulate_matches(
+    const orbx_frame_pose* pose1, const orbx_frame_pose* pose2, const orbx_keypoint* keys1,
+    const orbx_keypoint* keys_raw1, const float* u_right1, const float* depth1,
+    const float* cos_stereo1, int32_t n1, const orbx_keypoint* keys2,
+    const orbx_keypoint* keys_raw2, const float* u_right2, const float* depth2,
+    const float* cos_stereo2, int32_t n2, float mb, float ratio_factor, const int32_t* pairs,
+    int32_t npairs, int32_t* status, float* x3d, int32_t* nnew, int device);
+
 /* SearchByProjection over njobs frames at once — one Tracking::SearchLocalPoints
  * (Tracking.cc:1297-1347, ORBmatcher.cc:41-136) per frame, or any other
  * non-initialisation orbx_proj_mode, each job independent of the others.

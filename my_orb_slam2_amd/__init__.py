@@ -5,6 +5,8 @@ Host-side mirror of the reference's operator interface for this path:
 * ``ORBextractor`` — ORB_SLAM2::ORBextractor (include/ORBextractor.h:45-111)
 * ``compute_stereo_matches`` — Frame::ComputeStereoMatches (src/Frame.cc:496-686)
 * ``ORBmatcher`` — ORB_SLAM2::ORBmatcher descriptor matching (include/ORBmatcher.h)
+* ``triangulate_matches`` / ``ORBmatcher.triangulate_matches_batch_device`` — the per-match loop of
+  LocalMapping::CreateNewMapPoints behind SearchForTriangulation (src/LocalMapping.cc:356-507)
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
@@ -19,7 +21,8 @@ from __future__ import annotations
 from ._lib import KEYPOINT_DTYPE, OrbxError, load
 from .extractor import (ORBextractor, compute_stereo_matches, compute_stereo_matches_batch_device,
                         extract_stereo, StereoBatch)
-from .matcher import ORBmatcher, descriptor_distance
+from .matcher import (ORBmatcher, TRI_CODES, descriptor_distance, parallax_stereo_cos,
+                      triangulate_matches)
 from .vocabulary import Vocabulary, bow_score_l1
 from .kfdb import KeyFrameDatabase
 from .tracking import MonoTrackBatch, RGBDTrackBatch
@@ -34,4 +37,5 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "Rectifier", "RectifiedStereoBatch", "init_undistort_rectify_map", "load_stereo_settings",
            "remap_fixed_point", "remap_stereo_batch_device",
            "PROJ_JOB_DTYPE", "PROJ_SIM3", "proj_job", "project_map_points",
-           "project_map_points_batch_device"]
+           "project_map_points_batch_device", "TRI_CODES", "parallax_stereo_cos",
+           "triangulate_matches"]

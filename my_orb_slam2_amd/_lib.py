@@ -122,6 +122,11 @@ SIGNATURES = {
     "orbx_search_by_bow_kf_frame_batch_device": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "orbx_search_for_triangulation_batch_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
                                                         _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "orbx_parallax_stereo_cos": (_i, [_f, _vp, _i, _vp]),
+    "orbx_triangulate_matches_batch_device": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _f,
+                                                   _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "orbx_triangulate_matches": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                      _vp, _i, _f, _f, _vp, _i, _vp, _vp, _vp, _i]),
     "orbx_search_by_projection_batch_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp,
                                                     _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "orbx_matcher_sync": (_i, [_vp, _vp]),

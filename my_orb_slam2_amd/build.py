@@ -23,7 +23,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
-           "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip"]
+           "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_kernels.h", "orbx_host.h",
            "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
            "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
@@ -277,3 +277,30 @@ def build_project_ref(force: bool = False, verbose: bool = False) -> pathlib.Pat
     subprocess.run(cmd, check=True)
     os.replace(str(PROJECT_REF_BIN) + ".tmp", PROJECT_REF_BIN)
     return PROJECT_REF_BIN
+
+
+# ---- CreateNewMapPoints' loop restated over the cv stand-in (tests/native/triangulate_ref.cpp) ----
+TRIANGULATE_REF_SRC = PKG.parent / "tests" / "native" / "triangulate_ref.cpp"
+TRIANGULATE_REF_BIN = PKG.parent / "tests" / "native" / "triangulate_ref"
+
+
+def build_triangulate_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on the cv stand-in and the record layouts of include/ only: no liborbx and no GPU (the
+    CPU reference of orbx_triangulate_matches*)."""
+    root = PKG.parent
+    native = root / "tests" / "native"
+    deps = ([TRIANGULATE_REF_SRC] + sorted((root / "include").glob("*.h")) +
+            sorted((native / "cv_standin").rglob("*.hpp")))
+    newest = max(p.stat().st_mtime for p in deps)
+    if (not force and TRIANGULATE_REF_BIN.exists() and
+            TRIANGULATE_REF_BIN.stat().st_mtime >= newest):
+        return TRIANGULATE_REF_BIN
+    # -ffp-contract=off: the reference's float statements as written
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(native / "cv_standin"),
+           str(TRIANGULATE_REF_SRC), "-o", str(TRIANGULATE_REF_BIN) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(TRIANGULATE_REF_BIN) + ".tmp", TRIANGULATE_REF_BIN)
+    return TRIANGULATE_REF_BIN

@@ -682,6 +682,43 @@ orbx_status orbx_search_for_triangulation_batch_device(
     return ORBX_OK;
 }
 
+orbx_status orbx_triangulate_matches_batch_device(
+    orbx_matcher* m, const orbx_kf_db* db, int32_t njobs, const int32_t* d_kf1,
+    const int32_t* d_kf2, const orbx_frame_pose* d_poses, const float* d_depth,
+    const float* d_cos_stereo, const orbx_keypoint* d_keys_raw, float mb, float ratio_factor,
+    const int32_t* d_job_off, const int32_t* d_match12, int32_t* d_status, float* d_x3d,
+    int32_t* d_nnew, void* stream) {
+    if (!m || !db || njobs < 0 || njobs > 65535 || !(mb >= 0.0f)) return ORBX_ERR_INVALID;
+    if (db->max_feat < 0 || db->max_feat > MAX_FEAT) return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_kf1 || !d_kf2 || !d_poses || !d_depth || !d_cos_stereo || !d_job_off || !d_match12 ||
+        !d_status || !d_x3d || !d_nnew || !db->feat_off || !db->keys)
+        return ORBX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
+    TriPointsLaunch L{};
+    L.nkf = db->nkf;
+    L.feat_off = db->feat_off;
+    L.keys = db->keys;
+    L.keys_raw = d_keys_raw;
+    L.u_right = db->u_right;
+    L.depth = d_depth;
+    L.cos_stereo = d_cos_stereo;
+    L.poses = d_poses;
+    L.kf1 = d_kf1;
+    L.kf2 = d_kf2;
+    L.job_off = d_job_off;
+    L.match12 = d_match12;
+    L.ratio_factor = ratio_factor;
+    L.status = d_status;
+    L.x3d = d_x3d;
+    L.nnew = d_nnew;
+    L.err = m->d_err;
+    if (!HIPOK(launch_triangulate_points(L, db->max_feat, njobs, (hipStream_t)stream)))
+        return ORBX_ERR_DEVICE;
+    return ORBX_OK;
+}
+
 orbx_status orbx_search_by_projection_batch_device(
     orbx_matcher* m, int32_t mode, const orbx_featureset* frames, int32_t njobs,
     const int32_t* d_feat_off, const int32_t* d_grid_off, int32_t max_feat,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
 
 namespace orbx {
@@ -45,6 +46,33 @@ struct TriLaunch {
     int32_t* nmatches;
     int* err;
 };
+
+// The per-match loop behind SearchForTriangulation (orbx_triangulate.hip): job j's slots are
+// [job_off[j], job_off[j + 1]), one per KF1 feature, match12[slot] the KF2 feature or -1.
+// feat_off / keys / u_right are the database's; depth / cos_stereo / keys_raw (may be null) are
+// indexed like keys.  err: set when a lane refuses its slot (see include/orbx_match.h).
+struct TriPointsLaunch {
+    int nkf;
+    const int32_t* feat_off;
+    const orbx_keypoint* keys;
+    const orbx_keypoint* keys_raw;
+    const float* u_right;
+    const float* depth;
+    const float* cos_stereo;
+    const orbx_frame_pose* poses;
+    const int32_t* kf1;
+    const int32_t* kf2;
+    const int32_t* job_off;
+    const int32_t* match12;
+    float ratio_factor;
+    int32_t* status;
+    float* x3d;
+    int32_t* nnew;
+    int* err;
+};
+// Zeroes nnew[njobs] and launches k_triangulate_points over (max_feat, njobs).
+hipError_t launch_triangulate_points(const TriPointsLaunch& a, int max_feat, int njobs,
+                                     hipStream_t st);
 
 // Projection searches (modes of orbx_proj_mode plus PROJ_INIT) over njobs independent jobs
 // (frames).  With t_off == nullptr there is one job: target T, queries [0, nq).  Otherwise

@@ -1,0 +1,540 @@
+// orbx_triangulate.hip — the per-match loop behind SearchForTriangulation:
+// LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:356-507 (include/orbx_match.h,
+// orbx_triangulate_matches*).
+//
+// k_triangulate_points runs the loop body with one lane per (job, KF1 feature slot): no LDS, no
+// communication between lanes but the ballot that counts a job's new points.  Work per lane is
+// bounded: the Jacobi SVD runs at most SVD_MAX_SWEEPS sweeps of six column pairs.
+//
+// The float / double steps follow the reference's types; the library is built with
+// -ffp-contract=off, so every operation is rounded on its own as on x86-64.  Forms evaluated
+// inside OpenCV 3.2 are restated ([unverified-OpenCV]): the rows of A
+// (cv::addWeighted), cv::SVD::compute (JacobiSVDImpl_<float>) and x3D.rowRange(0,3)/w
+// (Mat::convertTo).  hypot() is glibc 2.35's (sysdeps/ieee754/dbl-64/e_hypot.c, the form without
+// a fused multiply-add, which is the one x86-64 runs), restated bit for bit.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/orbx_frame.h"
+#include "../../include/orbx_match.h"
+#include "orbx_host.h"
+#include "orbx_match_kernels.h"
+
+using namespace orbx;
+
+namespace {
+
+constexpr int SVD_MAX_SWEEPS = 30;   // max(m, 30) with m = 4 (lapack.cpp, JacobiSVDImpl_)
+
+__device__ __forceinline__ float fm(float a, float b) { return __fmul_rn(a, b); }
+__device__ __forceinline__ float fa(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float fs(float a, float b) { return __fsub_rn(a, b); }
+__device__ __forceinline__ double dm(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double da(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double ds(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ double dd(double a, double b) { return __ddiv_rn(a, b); }
+
+// glibc 2.35 __hypot for finite and non-finite doubles (e_hypot.c: kernel() without
+// __FP_FAST_FMA, SCALE 0x1p-600, LARGE_VAL 0x1p+511, TINY_VAL 0x1p-459, EPS 0x1p-54)
+__device__ __forceinline__ double hypot_kernel(double ax, double ay) {
+    double t1, t2;
+    double h = __dsqrt_rn(da(dm(ax, ax), dm(ay, ay)));
+    if (h <= dm(2.0, ay)) {
+        const double delta = ds(h, ay);
+        t1 = dm(ax, ds(dm(2.0, delta), ax));
+        t2 = dm(ds(delta, dm(2.0, ds(ax, ay))), delta);
+    } else {
+        const double delta = ds(h, ax);
+        t1 = dm(dm(2.0, delta), ds(ax, dm(2.0, ay)));
+        t2 = da(dm(ds(dm(4.0, delta), ay), ay), dm(delta, delta));
+    }
+    return ds(h, dd(da(t1, t2), dm(2.0, h)));
+}
+__device__ __forceinline__ double glibc_hypot(double x, double y) {
+    if (!isfinite(x) || !isfinite(y)) {
+        if (isinf(x) || isinf(y)) return INFINITY;
+        return da(x, y);
+    }
+    x = fabs(x);
+    y = fabs(y);
+    const double ax = x < y ? y : x, ay = x < y ? x : y;
+    if (ax > 0x1p+511) {
+        if (ay <= dm(ax, 0x1p-54)) return da(ax, ay);
+        return dd(hypot_kernel(dm(ax, 0x1p-600), dm(ay, 0x1p-600)), 0x1p-600);
+    }
+    if (ay < 0x1p-459) {
+        if (ax >= dd(ay, 0x1p-54)) return da(ax, ay);
+        return dm(hypot_kernel(dd(ax, 0x1p-600), dd(ay, 0x1p-600)), 0x1p-600);
+    }
+    if (ax >= dd(ay, 0x1p-54)) return da(ax, ay);
+    return hypot_kernel(ax, ay);
+}
+
+// cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on a 4x4 CV_32F A, reduced to vt.row(3)
+// [unverified-OpenCV]: _SVDcompute transposes A into At (row i = column i of A) and runs
+// JacobiSVDImpl_<float>(At, W, Vt, m = 4, n = 4, eps = 2 * FLT_EPSILON): one-sided Jacobi on the
+// rows of At, pair moments in double, rotations in float, at most 30 sweeps; then W[i] =
+// sqrt(|At row i|^2) and a selection sort, descending, that moves the Vt rows with W.  The
+// normalisation and completion of u do not touch vt.  A is row-major; v receives vt.row(3).
+__device__ __forceinline__ void svd4_vt_row3(const float* A, float* v) {
+    float At[4][4], Vt[4][4];
+    double W[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double sd = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = A[4 * k + i];
+            At[i][k] = t;
+            sd = da(sd, dm((double)t, (double)t));
+            Vt[i][k] = i == k ? 1.0f : 0.0f;
+        }
+        W[i] = sd;
+    }
+    const float eps = 2.0f * 1.1920928955078125e-07f;
+    for (int iter = 0; iter < SVD_MAX_SWEEPS; ++iter) {
+        bool changed = false;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = i + 1; j < 4; ++j) {
+                double a = W[i], p = 0.0, b = W[j];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) p = da(p, dm((double)At[i][k], (double)At[j][k]));
+                if (fabs(p) <= dm((double)eps, __dsqrt_rn(dm(a, b)))) continue;
+                p = dm(p, 2.0);
+                const double beta = ds(a, b), gamma = glibc_hypot(p, beta);
+                float c, s;
+                if (beta < 0.0) {
+                    const double delta = dm(ds(gamma, beta), 0.5);
+                    s = (float)__dsqrt_rn(dd(delta, gamma));
+                    c = (float)dd(p, dm(dm(gamma, (double)s), 2.0));
+                } else {
+                    c = (float)__dsqrt_rn(dd(da(gamma, beta), dm(gamma, 2.0)));
+                    s = (float)dd(p, dm(dm(gamma, (double)c), 2.0));
+                }
+                a = b = 0.0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float t0 = fa(fm(c, At[i][k]), fm(s, At[j][k]));
+                    const float t1 = fa(fm(-s, At[i][k]), fm(c, At[j][k]));
+                    At[i][k] = t0;
+                    At[j][k] = t1;
+                    a = da(a, dm((double)t0, (double)t0));
+                    b = da(b, dm((double)t1, (double)t1));
+                }
+                W[i] = a;
+                W[j] = b;
+                changed = true;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float t0 = fa(fm(c, Vt[i][k]), fm(s, Vt[j][k]));
+                    const float t1 = fa(fm(-s, Vt[i][k]), fm(c, Vt[j][k]));
+                    Vt[i][k] = t0;
+                    Vt[j][k] = t1;
+                }
+            }
+        }
+        if (!changed) break;
+    }
+    int id[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double sd = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sd = da(sd, dm((double)At[i][k], (double)At[i][k]));
+        W[i] = __dsqrt_rn(sd);
+        id[i] = i;
+    }
+    // for i: j = argmax of W[i..] (first on ties: W[j] < W[k]); swap i and j
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        int j = i;
+        double wj = W[i];
+#pragma unroll
+        for (int k = i + 1; k < 4; ++k)
+            if (wj < W[k]) {
+                j = k;
+                wj = W[k];
+            }
+#pragma unroll
+        for (int k = i + 1; k < 4; ++k)
+            if (j == k) {
+                const double tw = W[i];
+                W[i] = W[k];
+                W[k] = tw;
+                const int ti = id[i];
+                id[i] = id[k];
+                id[k] = ti;
+            }
+    }
+    const int r = id[3];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        v[k] = r == 0 ? Vt[0][k] : r == 1 ? Vt[1][k] : r == 2 ? Vt[2][k] : Vt[3][k];
+}
+
+// Rcw.row(r).dot(x3Dt) + tcw(r): Mat::dot in double, + the float in double, stored in a float
+__device__ __forceinline__ float row_dot(const orbx_frame_pose& F, int r, const float* X) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s = da(s, dm((double)F.Rcw[3 * r + k], (double)X[k]));
+    return (float)da(s, (double)F.tcw[r]);
+}
+
+// (float)cv::norm(X - Ow)
+__device__ __forceinline__ float dist_to(const float* X, const float* Ow) {
+    double ss = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float d = fs(X[k], Ow[k]);
+        ss = da(ss, dm((double)d, (double)d));
+    }
+    return (float)__dsqrt_rn(ss);
+}
+
+// KeyFrame::UnprojectStereo for z > 0 (KeyFrame.cc:629-645), as k_unproject evaluates it
+__device__ __forceinline__ void unproject_kf(const orbx_frame_pose& F, float u, float v, float z,
+                                             float* out) {
+    const float invfx = __fdiv_rn(1.0f, F.fx), invfy = __fdiv_rn(1.0f, F.fy);
+    const float c[3] = {fm(fm(fs(u, F.cx), z), invfx), fm(fm(fs(v, F.cy), z), invfy), z};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        float t = fm(F.Rcw[r], c[0]);
+        t = fa(t, fm(F.Rcw[3 + r], c[1]));
+        t = fa(t, fm(F.Rcw[6 + r], c[2]));
+        out[r] = (float)da((double)t, (double)F.Ow[r]);
+    }
+}
+
+// One feature of a keyframe as the loop reads it.
+struct TriFeat {
+    float x, y;        // mvKeysUn[idx].pt
+    float rx, ry;      // mvKeys[idx].pt (UnprojectStereo)
+    int octave;
+    float ur;          // mvuRight[idx]
+    float depth;       // mvDepth[idx]
+    float cos_stereo;  // cos(2*atan2(mb/2, mvDepth[idx])), orbx_parallax_stereo_cos
+};
+
+// The reprojection test of one keyframe (:439-463 / :466-489).  mbf is the current keyframe's in
+// both (:456, :482).
+__device__ __forceinline__ bool reproj_ok(const orbx_frame_pose& F, const TriFeat& f, bool stereo,
+                                          float mbf, float z, const float* X) {
+    const float sigma2 = fm(F.scale[f.octave], F.scale[f.octave]);
+    const float x = row_dot(F, 0, X), y = row_dot(F, 1, X);
+    const float invz = (float)dd(1.0, (double)z);
+    const float u = fa(fm(fm(F.fx, x), invz), F.cx);
+    const float v = fa(fm(fm(F.fy, y), invz), F.cy);
+    const float ex = fs(u, f.x), ey = fs(v, f.y);
+    if (!stereo)
+        return !((double)fa(fm(ex, ex), fm(ey, ey)) > dm(5.991, (double)sigma2));
+    const float u_r = fs(u, fm(mbf, invz));
+    const float er = fs(u_r, f.ur);
+    return !((double)fa(fa(fm(ex, ex), fm(ey, ey)), fm(er, er)) > dm(7.8, (double)sigma2));
+}
+
+// The loop body :361-507 for one match; X receives x3D on the three OK codes.
+__device__ __forceinline__ int triangulate_one(const orbx_frame_pose& F1,
+                                               const orbx_frame_pose& F2, const TriFeat& f1,
+                                               const TriFeat& f2, float ratio_factor, float* X) {
+    const bool st1 = f1.ur >= 0.0f, st2 = f2.ur >= 0.0f;
+    const float xn1[3] = {fm(fs(f1.x, F1.cx), __fdiv_rn(1.0f, F1.fx)),
+                          fm(fs(f1.y, F1.cy), __fdiv_rn(1.0f, F1.fy)), 1.0f};
+    const float xn2[3] = {fm(fs(f2.x, F2.cx), __fdiv_rn(1.0f, F2.fx)),
+                          fm(fs(f2.y, F2.cy), __fdiv_rn(1.0f, F2.fy)), 1.0f};
+    // ray = Rwc * xn: cv::gemm's small-matrix form without an added term
+    float ray1[3], ray2[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        ray1[r] = fa(fa(fm(F1.Rcw[r], xn1[0]), fm(F1.Rcw[3 + r], xn1[1])), fm(F1.Rcw[6 + r], xn1[2]));
+        ray2[r] = fa(fa(fm(F2.Rcw[r], xn2[0]), fm(F2.Rcw[3 + r], xn2[1])), fm(F2.Rcw[6 + r], xn2[2]));
+    }
+    double dot = 0.0, s1 = 0.0, s2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        dot = da(dot, dm((double)ray1[k], (double)ray2[k]));
+        s1 = da(s1, dm((double)ray1[k], (double)ray1[k]));
+        s2 = da(s2, dm((double)ray2[k], (double)ray2[k]));
+    }
+    const float cos_rays = (float)dd(dot, dm(__dsqrt_rn(s1), __dsqrt_rn(s2)));
+    const float cps0 = fa(cos_rays, 1.0f);
+    float cps1 = cps0, cps2 = cps0;
+    if (st1) cps1 = f1.cos_stereo;          // :386-389: `else if`, so never both
+    else if (st2) cps2 = f2.cos_stereo;
+    const float cps = cps2 < cps1 ? cps2 : cps1;   // std::min(cps1, cps2)
+
+    int code;
+    if (cos_rays < cps && cos_rays > 0.0f && (st1 || st2 || (double)cos_rays < 0.9998)) {
+        // A.row = xn * Tcw.row(2) - Tcw.row(r): MatOp_AddEx -> cv::addWeighted(a, xn, b, -1, 0),
+        // for CV_32F evaluated in double: (float)(a*alpha + b*beta + gamma)  [unverified-OpenCV]
+        float A[16];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t10 = k < 3 ? F1.Rcw[k] : F1.tcw[0], t11 = k < 3 ? F1.Rcw[3 + k] : F1.tcw[1],
+                        t12 = k < 3 ? F1.Rcw[6 + k] : F1.tcw[2];
+            const float t20 = k < 3 ? F2.Rcw[k] : F2.tcw[0], t21 = k < 3 ? F2.Rcw[3 + k] : F2.tcw[1],
+                        t22 = k < 3 ? F2.Rcw[6 + k] : F2.tcw[2];
+            A[k] = (float)da(da(dm((double)t12, (double)xn1[0]), dm((double)t10, -1.0)), 0.0);
+            A[4 + k] = (float)da(da(dm((double)t12, (double)xn1[1]), dm((double)t11, -1.0)), 0.0);
+            A[8 + k] = (float)da(da(dm((double)t22, (double)xn2[0]), dm((double)t20, -1.0)), 0.0);
+            A[12 + k] = (float)da(da(dm((double)t22, (double)xn2[1]), dm((double)t21, -1.0)), 0.0);
+        }
+        float v[4];
+        svd4_vt_row3(A, v);
+        if (v[3] == 0.0f) return ORBX_TRI_W_ZERO;
+        // x3D.rowRange(0,3) / w: convertTo(alpha = 1.0 / w): x * (float)alpha + 0.0f, a plain copy
+        // when |alpha - 1| < DBL_EPSILON  [unverified-OpenCV]
+        const double alpha = dd(1.0, (double)v[3]);
+        if (fabs(ds(alpha, 1.0)) < 2.220446049250313e-16) {
+            X[0] = v[0], X[1] = v[1], X[2] = v[2];
+        } else {
+            const float sc = (float)alpha;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) X[k] = fa(fm(v[k], sc), 0.0f);
+        }
+        code = ORBX_TRI_OK_TRIANGULATED;
+    } else if (st1 && cps1 < cps2) {
+        if (!(f1.depth > 0.0f)) return ORBX_TRI_LOW_PARALLAX;   // UnprojectStereo returns no point
+        unproject_kf(F1, f1.rx, f1.ry, f1.depth, X);
+        code = ORBX_TRI_OK_STEREO1;
+    } else if (st2 && cps2 < cps1) {
+        if (!(f2.depth > 0.0f)) return ORBX_TRI_LOW_PARALLAX;
+        unproject_kf(F2, f2.rx, f2.ry, f2.depth, X);
+        code = ORBX_TRI_OK_STEREO2;
+    } else {
+        return ORBX_TRI_LOW_PARALLAX;
+    }
+
+    const float z1 = row_dot(F1, 2, X);
+    if (z1 <= 0.0f) return ORBX_TRI_BEHIND_1;
+    const float z2 = row_dot(F2, 2, X);
+    if (z2 <= 0.0f) return ORBX_TRI_BEHIND_2;
+    if (!reproj_ok(F1, f1, st1, F1.mbf, z1, X)) return ORBX_TRI_REPROJ_1;
+    if (!reproj_ok(F2, f2, st2, F1.mbf, z2, X)) return ORBX_TRI_REPROJ_2;   // :482: KF1's mbf
+    const float dist1 = dist_to(X, F1.Ow), dist2 = dist_to(X, F2.Ow);
+    if (dist1 == 0.0f || dist2 == 0.0f) return ORBX_TRI_DIST_ZERO;
+    const float ratio_dist = __fdiv_rn(dist2, dist1);
+    const float ratio_octave = __fdiv_rn(F1.scale[f1.octave], F2.scale[f2.octave]);
+    if (fm(ratio_dist, ratio_factor) < ratio_octave || ratio_dist > fm(ratio_octave, ratio_factor))
+        return ORBX_TRI_SCALE;
+    return code;
+}
+
+// One lane per (job, KF1 feature slot), grid (ceil(max_feat / 256), njobs); a job with more slots
+// than the grid's lanes (a keyframe above max_feat) is covered by further rounds of the same
+// blocks, so every slot receives a code.  The two pose records are indexed by the block, so their
+// loads are uniform.
+__global__ __launch_bounds__(256) void k_triangulate_points(TriPointsLaunch g) {
+    const int j = blockIdx.y;
+    const int a = g.kf1[j], b = g.kf2[j];
+    const int s0 = g.job_off[j], span = g.job_off[j + 1] - s0;
+    const bool job_ok = a >= 0 && a < g.nkf && b >= 0 && b < g.nkf;
+    int n1 = 0, n2 = 0, b1 = 0, b2 = 0;
+    bool levels_ok = false;
+    if (job_ok) {
+        b1 = g.feat_off[a];
+        b2 = g.feat_off[b];
+        n1 = g.feat_off[a + 1] - b1;
+        n2 = g.feat_off[b + 1] - b2;
+        const int l1 = g.poses[a].nlevels, l2 = g.poses[b].nlevels;
+        levels_ok = l1 >= 1 && l1 <= MATCH_MAX_LEVELS && l2 >= 1 && l2 <= MATCH_MAX_LEVELS;
+    }
+    int nok = 0;
+    for (int base = blockIdx.x * 256; base < span; base += gridDim.x * 256) {
+        const int i = base + threadIdx.x;
+        bool ok = false;
+        if (i < span) {
+            const int slot = s0 + i;
+            int code = ORBX_TRI_NO_MATCH;
+            bool refuse = !job_ok || !levels_ok;
+            if (!refuse && i < n1) {
+                const int i2 = g.match12[slot];
+                if (i2 >= 0 && i2 < n2) {
+                    const orbx_frame_pose& F1 = g.poses[a];
+                    const orbx_frame_pose& F2 = g.poses[b];
+                    const orbx_keypoint k1 = g.keys[b1 + i], k2 = g.keys[b2 + i2];
+                    if (k1.octave < 0 || k1.octave >= F1.nlevels || k2.octave < 0 ||
+                        k2.octave >= F2.nlevels) {
+                        refuse = true;
+                    } else {
+                        TriFeat f1, f2;
+                        f1.x = k1.x, f1.y = k1.y, f1.octave = k1.octave;
+                        f2.x = k2.x, f2.y = k2.y, f2.octave = k2.octave;
+                        f1.rx = k1.x, f1.ry = k1.y, f2.rx = k2.x, f2.ry = k2.y;
+                        if (g.keys_raw) {
+                            f1.rx = g.keys_raw[b1 + i].x, f1.ry = g.keys_raw[b1 + i].y;
+                            f2.rx = g.keys_raw[b2 + i2].x, f2.ry = g.keys_raw[b2 + i2].y;
+                        }
+                        f1.ur = g.u_right ? g.u_right[b1 + i] : -1.0f;
+                        f2.ur = g.u_right ? g.u_right[b2 + i2] : -1.0f;
+                        f1.depth = g.depth[b1 + i], f2.depth = g.depth[b2 + i2];
+                        f1.cos_stereo = g.cos_stereo[b1 + i];
+                        f2.cos_stereo = g.cos_stereo[b2 + i2];
+                        float X[3];
+                        code = triangulate_one(F1, F2, f1, f2, g.ratio_factor, X);
+                        ok = code <= ORBX_TRI_OK_STEREO2;
+                        if (ok) {
+                            g.x3d[3 * (size_t)slot] = X[0];
+                            g.x3d[3 * (size_t)slot + 1] = X[1];
+                            g.x3d[3 * (size_t)slot + 2] = X[2];
+                        }
+                    }
+                } else if (i2 != -1) {
+                    refuse = true;
+                }
+            }
+            g.status[slot] = code;
+            if (refuse) atomicOr(g.err, 1);
+        }
+        nok += (int)__popcll(__ballot(ok));
+    }
+    if ((threadIdx.x & 63) == 0 && nok) atomicAdd(&g.nnew[j], nok);
+}
+
+}  // namespace
+
+namespace orbx {
+
+hipError_t launch_triangulate_points(const TriPointsLaunch& a, int max_feat, int njobs,
+                                     hipStream_t st) {
+    hipError_t e = hipMemsetAsync(a.nnew, 0, 4 * (size_t)njobs, st);
+    if (e != hipSuccess || max_feat == 0) return e;
+    hipLaunchKernelGGL(k_triangulate_points, dim3((max_feat + 255) / 256, njobs), dim3(256), 0, st,
+                       a);
+    return hipGetLastError();
+}
+
+}  // namespace orbx
+
+extern "C" {
+
+// LocalMapping.cc:387 / :389 with libm's double cos and atan2 (mb / 2 is a float division); see
+// include/orbx_match.h on the float overloads.
+orbx_status orbx_parallax_stereo_cos(float mb, const float* depth, int32_t n, float* out) {
+    if (n < 0 || (n > 0 && (!depth || !out))) return ORBX_ERR_INVALID;
+    const double half = (double)(mb / 2);
+    for (int32_t i = 0; i < n; ++i) out[i] = (float)::cos(2 * ::atan2(half, (double)depth[i]));
+    return ORBX_OK;
+}
+
+orbx_status orbx_triangulate_matches(
+    const orbx_frame_pose* pose1, const orbx_frame_pose* pose2, const orbx_keypoint* keys1,
+    const orbx_keypoint* keys_raw1, const float* u_right1, const float* depth1,
+    const float* cos_stereo1, int32_t n1, const orbx_keypoint* keys2,
+    const orbx_keypoint* keys_raw2, const float* u_right2, const float* depth2,
+    const float* cos_stereo2, int32_t n2, float mb, float ratio_factor, const int32_t* pairs,
+    int32_t npairs, int32_t* status, float* x3d, int32_t* nnew, int device) {
+    if (!pose1 || !pose2 || n1 < 0 || n2 < 0 || npairs < 0 || !(mb >= 0.0f) ||
+        (n1 > 0 && !keys1) || (n2 > 0 && !keys2) || (npairs > 0 && (!pairs || !status || !x3d)) ||
+        (u_right1 && !depth1 && n1 > 0) || (u_right2 && !depth2 && n2 > 0))
+        return ORBX_ERR_INVALID;
+    if (pose1->nlevels < 1 || pose2->nlevels < 1) return ORBX_ERR_INVALID;
+    if (pose1->nlevels > MATCH_MAX_LEVELS || pose2->nlevels > MATCH_MAX_LEVELS || n1 > 32768 ||
+        n2 > 32768)
+        return ORBX_ERR_UNSUPPORTED;
+    std::vector<int32_t> match12((size_t)n1, -1);
+    for (int32_t p = 0; p < npairs; ++p) {
+        const int32_t i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
+        if (i1 < 0 || i1 >= n1 || i2 < 0 || i2 >= n2 || match12[(size_t)i1] != -1)
+            return ORBX_ERR_INVALID;
+        if (keys1[i1].octave < 0 || keys1[i1].octave >= pose1->nlevels || keys2[i2].octave < 0 ||
+            keys2[i2].octave >= pose2->nlevels)
+            return ORBX_ERR_INVALID;
+        match12[(size_t)i1] = i2;
+    }
+    if (nnew) *nnew = 0;
+    if (npairs == 0) return ORBX_OK;
+    if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
+        return ORBX_ERR_DEVICE;
+
+    // one staging block: every input, then the outputs
+    const size_t n = (size_t)n1 + (size_t)n2;
+    const bool raw = keys_raw1 || keys_raw2, stereo = u_right1 || u_right2;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o_pose = 0, o_idx = al(2 * sizeof(orbx_frame_pose)), o_keys = o_idx + 256,
+                 o_raw = o_keys + al(sizeof(orbx_keypoint) * n),
+                 o_ur = o_raw + (raw ? al(sizeof(orbx_keypoint) * n) : 0),
+                 o_depth = o_ur + (stereo ? al(4 * n) : 0), o_cos = o_depth + al(4 * n),
+                 o_match = o_cos + al(4 * n), in_end = o_match + al(4 * (size_t)n1),
+                 o_cnt = in_end, o_status = o_cnt + 256, o_x3d = o_status + al(4 * (size_t)n1),
+                 end = o_x3d + al(12 * (size_t)n1);
+    std::vector<uint8_t> h(end, 0);
+    std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
+    std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
+    int32_t* idx = (int32_t*)(h.data() + o_idx);   // feat_off[3], kf1, kf2, job_off[2]
+    idx[0] = 0, idx[1] = n1, idx[2] = n1 + n2, idx[3] = 0, idx[4] = 1, idx[5] = 0, idx[6] = n1;
+    auto put = [&](size_t off, const void* a, const void* b, size_t elem) {
+        if (a && n1) std::memcpy(h.data() + off, a, elem * (size_t)n1);
+        if (b && n2) std::memcpy(h.data() + off + elem * (size_t)n1, b, elem * (size_t)n2);
+    };
+    put(o_keys, keys1, keys2, sizeof(orbx_keypoint));
+    if (raw) put(o_raw, keys_raw1 ? keys_raw1 : keys1, keys_raw2 ? keys_raw2 : keys2, sizeof(orbx_keypoint));
+    if (stereo) {
+        float* ur = (float*)(h.data() + o_ur);
+        for (size_t k = 0; k < n; ++k) ur[k] = -1.0f;
+        put(o_ur, u_right1, u_right2, 4);
+    }
+    put(o_depth, depth1, depth2, 4);
+    float* cs = (float*)(h.data() + o_cos);
+    if (cos_stereo1) put(o_cos, cos_stereo1, nullptr, 4);
+    else if (depth1) orbx_parallax_stereo_cos(mb, depth1, n1, cs);
+    if (cos_stereo2) put(o_cos, nullptr, cos_stereo2, 4);
+    else if (depth2) orbx_parallax_stereo_cos(mb, depth2, n2, cs + n1);
+    if (n1) std::memcpy(h.data() + o_match, match12.data(), 4 * (size_t)n1);
+
+    static std::mutex mu;
+    static DevBuf bufs[ORBX_MAX_DEVICES];          // live for the process, like its stream
+    static hipStream_t streams[ORBX_MAX_DEVICES];
+    std::lock_guard<std::mutex> lk(mu);
+    DevBuf& buf = bufs[device];
+    if (!streams[device] &&
+        !HIPOK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking)))
+        return ORBX_ERR_DEVICE;
+    if (!buf.ensure(end)) return ORBX_ERR_DEVICE;
+    uint8_t* d = buf.as<uint8_t>();
+    hipStream_t st = streams[device];
+    if (!HIPOK(hipMemcpyAsync(d, h.data(), in_end + 256, hipMemcpyHostToDevice, st)))
+        return ORBX_ERR_DEVICE;
+    TriPointsLaunch L{};
+    L.nkf = 2;
+    L.feat_off = (const int32_t*)(d + o_idx);
+    L.keys = (const orbx_keypoint*)(d + o_keys);
+    L.keys_raw = raw ? (const orbx_keypoint*)(d + o_raw) : nullptr;
+    L.u_right = stereo ? (const float*)(d + o_ur) : nullptr;
+    L.depth = (const float*)(d + o_depth);
+    L.cos_stereo = (const float*)(d + o_cos);
+    L.poses = (const orbx_frame_pose*)(d + o_pose);
+    L.kf1 = L.feat_off + 3;
+    L.kf2 = L.feat_off + 4;
+    L.job_off = L.feat_off + 5;
+    L.match12 = (const int32_t*)(d + o_match);
+    L.ratio_factor = ratio_factor;
+    L.status = (int32_t*)(d + o_status);
+    L.x3d = (float*)(d + o_x3d);
+    L.nnew = (int32_t*)(d + o_cnt);
+    L.err = (int*)(d + o_cnt) + 1;     // zeroed with the block; the host checks came first
+    orbx_status s = ORBX_OK;
+    if (!HIPOK(launch_triangulate_points(L, n1, 1, st)) ||
+        !HIPOK(hipMemcpyAsync(h.data() + o_cnt, d + o_cnt, end - o_cnt, hipMemcpyDeviceToHost, st)))
+        s = ORBX_ERR_DEVICE;
+    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
+    if (s != ORBX_OK) return s;
+    const int32_t* hs = (const int32_t*)(h.data() + o_status);
+    const float* hx = (const float*)(h.data() + o_x3d);
+    for (int32_t p = 0; p < npairs; ++p) {
+        const int32_t i1 = pairs[2 * p];
+        status[p] = hs[i1];
+        if (hs[i1] <= ORBX_TRI_OK_STEREO2)
+            for (int k = 0; k < 3; ++k) x3d[3 * (size_t)p + k] = hx[3 * (size_t)i1 + k];
+    }
+    if (nnew) *nnew = *(const int32_t*)(h.data() + o_cnt);
+    return ORBX_OK;
+}
+
+}  // extern "C"

@@ -35,6 +35,68 @@ def compute_three_maxima(histo_counts) -> tuple[int, int, int]:
     return tuple(o.value for o in out)
 
 
+# orbx_tri_code (include/orbx_match.h): the exits of CreateNewMapPoints' loop body
+TRI_CODES = ("OK_TRIANGULATED", "OK_STEREO1", "OK_STEREO2", "NO_MATCH", "LOW_PARALLAX", "W_ZERO",
+             "BEHIND_1", "BEHIND_2", "REPROJ_1", "REPROJ_2", "DIST_ZERO", "SCALE")
+(TRI_OK_TRIANGULATED, TRI_OK_STEREO1, TRI_OK_STEREO2, TRI_NO_MATCH, TRI_LOW_PARALLAX, TRI_W_ZERO,
+ TRI_BEHIND_1, TRI_BEHIND_2, TRI_REPROJ_1, TRI_REPROJ_2, TRI_DIST_ZERO, TRI_SCALE) = range(12)
+
+
+def parallax_stereo_cos(mb: float, depth) -> np.ndarray:
+    """orbx_parallax_stereo_cos: cosParallaxStereo of every feature of a keyframe
+    (LocalMapping.cc:387), (float)cos(2 * atan2(mb / 2, depth)) by the host's libm; computed once
+    when the keyframe is uploaded."""
+    d = np.ascontiguousarray(depth, np.float32).reshape(-1)
+    out = np.empty(len(d), np.float32)
+    check("orbx_parallax_stereo_cos",
+          load().orbx_parallax_stereo_cos(float(np.float32(mb)), ptr(d), len(d), ptr(out)))
+    return out
+
+
+def triangulate_matches(pose1, pose2, keys1, keys2, pairs, ratio_factor: float,
+                        mb: float = 0.0, u_right1=None, u_right2=None, depth1=None,
+                        depth2=None, keys_raw1=None, keys_raw2=None, cos_stereo1=None,
+                        cos_stereo2=None, x3d=None, device: int = 0):
+    """orbx_triangulate_matches: CreateNewMapPoints' loop body for the (idx1, idx2) pairs
+    SearchForTriangulation returned -> (status int32 [npairs] of TRI_* codes, x3d float32
+    [npairs, 3] written where status <= TRI_OK_STEREO2, nnew).  pose1 / pose2: frame_pose
+    records of mpCurrentKeyFrame / pKF2; keys: mvKeysUn, keys_raw: mvKeys (None: keys);
+    ratio_factor = 1.5f * mfScaleFactor.  x3d: an array to write into (rows of failed pairs
+    stay as they are)."""
+    from .features import FRAME_POSE_DTYPE
+    from ._lib import KEYPOINT_DTYPE
+    p1 = np.ascontiguousarray(pose1, FRAME_POSE_DTYPE).reshape(())
+    p2 = np.ascontiguousarray(pose2, FRAME_POSE_DTYPE).reshape(())
+    k1 = np.ascontiguousarray(keys1, KEYPOINT_DTYPE)
+    k2 = np.ascontiguousarray(keys2, KEYPOINT_DTYPE)
+
+    def opt(a, dtype, n):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        if len(a) != n:
+            raise ValueError("per-feature arrays have one entry per keypoint")
+        return a
+
+    ur1, ur2 = opt(u_right1, np.float32, len(k1)), opt(u_right2, np.float32, len(k2))
+    d1, d2 = opt(depth1, np.float32, len(k1)), opt(depth2, np.float32, len(k2))
+    r1, r2 = opt(keys_raw1, KEYPOINT_DTYPE, len(k1)), opt(keys_raw2, KEYPOINT_DTYPE, len(k2))
+    c1, c2 = opt(cos_stereo1, np.float32, len(k1)), opt(cos_stereo2, np.float32, len(k2))
+    pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    status = np.full(max(len(pr), 1), TRI_NO_MATCH, np.int32)
+    if x3d is None:
+        x3d = np.zeros((max(len(pr), 1), 3), np.float32)
+    elif not (isinstance(x3d, np.ndarray) and x3d.dtype == np.float32 and
+              x3d.flags.c_contiguous and x3d.size >= 3 * len(pr)):
+        raise TypeError("x3d must be a C-contiguous float32 array [npairs, 3]")
+    nnew = ctypes.c_int32(0)
+    check("orbx_triangulate_matches", load().orbx_triangulate_matches(
+        ptr(p1), ptr(p2), ptr(k1), ptr(r1), ptr(ur1), ptr(d1), ptr(c1), len(k1), ptr(k2),
+        ptr(r2), ptr(ur2), ptr(d2), ptr(c2), len(k2), float(mb), float(ratio_factor), ptr(pr),
+        len(pr), ptr(status), ptr(x3d), ctypes.byref(nnew), int(device)))
+    return status[:len(pr)], x3d.reshape(-1, 3)[:len(pr)], nnew.value
+
+
 # orbx_matcher_variant kinds (include/orbx_match.h)
 VK_BOW_KF_FRAME = 0
 VK_BOW_KF_KF = 1
@@ -306,6 +368,40 @@ class ORBmatcher:
                   self._h, ctypes.byref(db), int(kf1.numel()), ptr(kf1), ptr(kf2), ptr(F12),
                   ptr(epi), ptr(s2), ptr(sc), len(s2), int(only_stereo), ptr(job_off),
                   ptr(d_match), ptr(d_nmatches), ctypes.c_void_p(stream)))
+
+    # ---- the per-match loop behind SearchForTriangulation (LocalMapping.cc:356-507) ----------
+    def triangulate_matches(self, pose1, pose2, keys1, keys2, pairs, ratio_factor: float, **kw):
+        """triangulate_matches (this module) on the matcher's device."""
+        return triangulate_matches(pose1, pose2, keys1, keys2, pairs, ratio_factor,
+                                   device=self.device, **kw)
+
+    def triangulate_matches_batch_device(self, db: KfDbC, kf1, kf2, d_poses, d_depth,
+                                         d_cos_stereo, ratio_factor: float, job_off, d_match12,
+                                         d_status, d_x3d, d_nnew, d_keys_raw=None,
+                                         mb: float = 0.0, stream=0):
+        """orbx_triangulate_matches_batch_device: the same loop for every job of a device
+        database, on what search_for_triangulation_batch_device wrote (d_match12 / job_off);
+        d_status [slots] int32, d_x3d [slots, 3] float32, d_nnew [njobs] int32 (device
+        tensors)."""
+        check("orbx_triangulate_matches_batch_device",
+              self._lib.orbx_triangulate_matches_batch_device(
+                  self._h, ctypes.byref(db), int(kf1.numel()), ptr(kf1), ptr(kf2), ptr(d_poses),
+                  ptr(d_depth), ptr(d_cos_stereo), ptr(d_keys_raw), float(mb),
+                  float(ratio_factor), ptr(job_off), ptr(d_match12), ptr(d_status), ptr(d_x3d),
+                  ptr(d_nnew), ctypes.c_void_p(stream)))
+
+    def search_and_triangulate_batch_device(self, db: KfDbC, kf1, kf2, F12, epi, sigma2, scale,
+                                            job_off, d_match, d_nmatches, d_poses, d_depth,
+                                            d_cos_stereo, ratio_factor: float, d_status, d_x3d,
+                                            d_nnew, d_keys_raw=None, mb: float = 0.0,
+                                            only_stereo=False, stream=0):
+        """SearchForTriangulation and the loop behind it for a job list, back to back on one
+        stream: no host step between the two launches."""
+        self.search_for_triangulation_batch_device(db, kf1, kf2, F12, epi, sigma2, scale, job_off,
+                                                   d_match, d_nmatches, only_stereo, stream)
+        self.triangulate_matches_batch_device(db, kf1, kf2, d_poses, d_depth, d_cos_stereo,
+                                              ratio_factor, job_off, d_match, d_status, d_x3d,
+                                              d_nnew, d_keys_raw, mb, stream)
 
     def search_by_projection_batch_device(self, mode: int, frames: "DeviceFrameBatch", d_qdesc,
                                           d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
