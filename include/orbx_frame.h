@@ -168,6 +168,79 @@ orbx_status orbx_project_map_points(int32_t mode, const orbx_proj_job* job,
                                     const orbx_keypoint* src_keys, const uint8_t* skip,
                                     orbx_proj_query* q, int32_t* nactive, int device);
 
+/* ---- Optimizer::PoseOptimization (src/Optimizer.cc:245-457; called at Tracking.cc:823, :953,
+ * :1001 and :1564-1603): the pose-only fit of a frame to its MapPoints ----
+ *
+ * One edge per feature i with a MapPoint (d_mp_of_feat[i] >= 0, an index into the frame's block
+ * [d_mp_off[f], d_mp_off[f+1]) of d_mps), in feature order: mono when d_u_right is NULL or
+ * d_u_right[i] < 0, else stereo; observation d_keys_un[i].x / .y (and d_u_right[i]) widened to
+ * double, information 1.0f / (scale[octave] * scale[octave]) of the pose record's scale table,
+ * Huber deltas (float)sqrt(5.991) / (float)sqrt(7.815), camera fx fy cx cy mbf of the record.
+ * g2o's single-vertex Levenberg-Marquardt is restated as it runs there (four rounds of
+ * optimize(10) from the input pose, at most 10 trials per iteration, the 1e-5 tau, the 1/3..2/3
+ * crop, the three-in-a-row stop; errors are not recomputed after a rejected trial; edges classified
+ * by `(float)chi2 > 5.991f / 7.815f`; the kernel dropped for the fourth round; a frame with fewer
+ * than 10 edges runs one round).  H, b and chi2 are summed edge by edge in edge order.  Forms
+ * evaluated inside Eigen (Quaterniond(Matrix3d), quaternion * vector, the pivoted LDLT) are
+ * restated from the published algorithms [unverified-Eigen]; sin / cos are the library's own
+ * fdlibm-style routine, defined for theta <= 2^20: no bit-equality with a g2o build is claimed,
+ * the GPU equals the two CPU restatements of tests/ bit for bit.
+ *
+ * Per frame f: d_outlier[i] (mvbOutlier, indexed like the features) is written for every feature
+ * with a MapPoint and for no other; d_ngood[f] = nInitialCorrespondences - nBad (0 with fewer than
+ * 3 edges, the pose then copied through); d_poses_out[f] = d_poses[f] with Rcw, tcw (the optimised
+ * SE3Quat's matrix rounded to float, Converter.cc:49-71) and Ow (-Rcw^T tcw as cv::gemm's
+ * small-matrix form: float products summed left to right) replaced.  d_poses_out may be d_poses.
+ * d_info[f]: */
+#define ORBX_POSEOPT_ROUNDS_MASK 0x7u            /* bits 0-2: rounds run (0-4) */
+#define ORBX_POSEOPT_ITERS_SHIFT 3               /* bits 3-9: Levenberg iterations (solve calls), <= 40 */
+#define ORBX_POSEOPT_ITERS_MASK 0x7fu
+#define ORBX_POSEOPT_TRIALS_SHIFT 10             /* bits 10-18: Levenberg trials (linear solves), <= 400 */
+#define ORBX_POSEOPT_TRIALS_MASK 0x1ffu
+#define ORBX_POSEOPT_REFUSED_MP_INDEX (1u << 24) /* a MapPoint index < -1 or outside the block */
+#define ORBX_POSEOPT_REFUSED_OCTAVE (1u << 25)   /* a matched feature's octave outside [0, nlevels) */
+#define ORBX_POSEOPT_REFUSED_NLEVELS (1u << 26)  /* nlevels outside [1, 16] */
+#define ORBX_POSEOPT_REFUSED_COUNT (1u << 27)    /* more than max_feat features (or a negative count) */
+#define ORBX_POSEOPT_THETA_LIMIT (1u << 28)      /* an update's |omega| above 2^20 or not finite: that trial failed */
+#define ORBX_POSEOPT_NONPOSITIVE_SOLVE (1u << 29) /* LDLT::isPositive() was false in some trial */
+#define ORBX_POSEOPT_FEW_EDGES (1u << 30)        /* fewer than 3 edges: returned 0 */
+#define ORBX_POSEOPT_REFUSED_ANY (0xfu << 24)
+/* A refused frame (what only the device can see): nothing of it is read further, d_ngood[f] = 0,
+ * the pose is copied through and the flags are untouched.  A frame's features: [d_feat_off[f],
+ * d_feat_off[f+1]) of d_keys_un / d_u_right / d_mp_of_feat / d_outlier.
+ * ORBX_ERR_INVALID: a NULL required pointer when nframes > 0; nframes < 0 or > 65535; max_feat
+ * outside [0, 32768].  nframes == 0: ORBX_OK, nothing touched.  Without a GPU: ORBX_ERR_DEVICE. */
+orbx_status orbx_pose_optimization_batch_device(
+    const orbx_frame_pose* d_poses, int32_t nframes, const orbx_keypoint* d_keys_un,
+    const float* d_u_right, const int32_t* d_feat_off, int32_t max_feat,
+    const int32_t* d_mp_of_feat, const orbx_map_point* d_mps, const int32_t* d_mp_off,
+    orbx_frame_pose* d_poses_out, uint8_t* d_outlier, int32_t* d_ngood, uint32_t* d_info,
+    void* stream);
+/* One frame, host arrays (copied to the device for the call): n features, nmp MapPoints.
+ * outlier is read (the flags before the call) and written; info may be NULL.  The argument checks
+ * run before the device is touched (ORBX_ERR_INVALID: a NULL pose, pose_out or ngood, n outside
+ * [0, 32768], nmp < 0, a NULL array that n or nmp makes required); without a GPU: ORBX_ERR_DEVICE. */
+orbx_status orbx_pose_optimization(const orbx_frame_pose* pose, const orbx_keypoint* keys_un,
+                                   const float* u_right, int32_t n, const int32_t* mp_of_feat,
+                                   const orbx_map_point* mps, int32_t nmp,
+                                   orbx_frame_pose* pose_out, uint8_t* outlier, int32_t* ngood,
+                                   uint32_t* info, int device);
+
+/* A batched projection search's d_match (per query / MapPoint q of job j, the job-local feature
+ * or -1; queries [d_q_off[j], d_q_off[j+1])) turned into mvpMapPoints: d_mp_of_feat (per feature
+ * of job j, [d_feat_off[j], d_feat_off[j+1]), the job-local query index or -1).  Two queries
+ * naming one feature: the highest query index wins, the "later match overwrites" of
+ * ORBmatcher.cc:91, :1472.  d_prior (optional, laid out like d_mp_of_feat, not the same memory):
+ * a feature no query names keeps d_prior's entry, i.e. d_prior is copied in and the scatter
+ * overwrites it (TrackLocalMap sees the MapPoints of both searches when both index one block).
+ * A feature index outside the job's features is skipped and *d_flagged (one device word, zeroed
+ * by the call) becomes 1.  max_q / max_feat: at least every job's query / feature count. */
+orbx_status orbx_matches_to_features_batch_device(const int32_t* d_match, const int32_t* d_q_off,
+                                                  const int32_t* d_feat_off, int32_t njobs,
+                                                  int32_t max_q, int32_t max_feat,
+                                                  const int32_t* d_prior, int32_t* d_mp_of_feat,
+                                                  uint32_t* d_flagged, void* stream);
+
 /* Tracking's colour input (src/Tracking.cc:189-214): cv::cvtColor(*2GRAY) for 3- or 4-channel
  * 8-bit images, OpenCV 3.2's integer path RGB2Gray<uchar> (Y = (R*4899 + G*9617 + B*1868 +
  * 8192) >> 14).  rgb = 1 for RGB/RGBA order (mbRGB), 0 for BGR/BGRA.  OpenCV builds with IPP

@@ -7,6 +7,8 @@ Host-side mirror of the reference's operator interface for this path:
 * ``ORBmatcher`` — ORB_SLAM2::ORBmatcher descriptor matching (include/ORBmatcher.h)
 * ``triangulate_matches`` / ``ORBmatcher.triangulate_matches_batch_device`` — the per-match loop of
   LocalMapping::CreateNewMapPoints behind SearchForTriangulation (src/LocalMapping.cc:356-507)
+* ``pose_optimization`` / ``MonoTrackBatch.pose_optimization`` — Optimizer::PoseOptimization, the
+  pose-only fit of a frame to its MapPoints (src/Optimizer.cc:245-457)
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
@@ -26,8 +28,9 @@ from .matcher import (ORBmatcher, TRI_CODES, descriptor_distance, parallax_stere
 from .vocabulary import Vocabulary, bow_score_l1
 from .kfdb import KeyFrameDatabase
 from .tracking import MonoTrackBatch, RGBDTrackBatch
-from .features import (PROJ_JOB_DTYPE, PROJ_SIM3, proj_job, project_map_points,
-                       project_map_points_batch_device)
+from .features import (PROJ_JOB_DTYPE, PROJ_SIM3, matches_to_features_batch_device,
+                       pose_optimization, pose_optimization_batch_device, proj_job,
+                       project_map_points, project_map_points_batch_device)
 from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
                       load_stereo_settings, remap_fixed_point, remap_stereo_batch_device)
 
@@ -38,4 +41,5 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "remap_fixed_point", "remap_stereo_batch_device",
            "PROJ_JOB_DTYPE", "PROJ_SIM3", "proj_job", "project_map_points",
            "project_map_points_batch_device", "TRI_CODES", "parallax_stereo_cos",
-           "triangulate_matches"]
+           "triangulate_matches", "pose_optimization", "pose_optimization_batch_device",
+           "matches_to_features_batch_device"]

@@ -203,6 +203,10 @@ SIGNATURES = {
                                             _vp]),
     "orbx_remap": (_i, [_vp, _vp, _sz, _vp, _sz]),
     "orbx_remap_images_per_chunk": (_i, []),
+    "orbx_pose_optimization_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp]),
+    "orbx_pose_optimization": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
+    "orbx_matches_to_features_batch_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -23,7 +23,8 @@ CSRC = PKG / "csrc"
 LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
-           "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip"]
+           "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
+           "orbx_poseopt.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_kernels.h", "orbx_host.h",
            "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
            "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
@@ -304,3 +305,28 @@ def build_triangulate_ref(force: bool = False, verbose: bool = False) -> pathlib
     subprocess.run(cmd, check=True)
     os.replace(str(TRIANGULATE_REF_BIN) + ".tmp", TRIANGULATE_REF_BIN)
     return TRIANGULATE_REF_BIN
+
+
+# ---- PoseOptimization restated in plain C++ doubles (tests/native/poseopt_ref.cpp) ---------------
+POSEOPT_REF_SRC = PKG.parent / "tests" / "native" / "poseopt_ref.cpp"
+POSEOPT_REF_BIN = PKG.parent / "tests" / "native" / "poseopt_ref"
+
+
+def build_poseopt_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on the record layouts of include/ and csrc/orbx_math.h (orbx_sincos_f64) only: no
+    liborbx and no GPU (the CPU reference of orbx_pose_optimization*)."""
+    root = PKG.parent
+    deps = [POSEOPT_REF_SRC, CSRC / "orbx_math.h"] + sorted((root / "include").glob("*.h"))
+    newest = max(p.stat().st_mtime for p in deps)
+    if (not force and POSEOPT_REF_BIN.exists() and
+            POSEOPT_REF_BIN.stat().st_mtime >= newest):
+        return POSEOPT_REF_BIN
+    # -ffp-contract=off: every operation rounded on its own, as in the kernel
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(CSRC), str(POSEOPT_REF_SRC),
+           "-o", str(POSEOPT_REF_BIN) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(POSEOPT_REF_BIN) + ".tmp", POSEOPT_REF_BIN)
+    return POSEOPT_REF_BIN

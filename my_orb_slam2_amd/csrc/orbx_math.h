@@ -224,4 +224,69 @@ ORBX_HD float glibc_logf(float x) {
     return (float)y;
 }
 
+// sin and cos of a double for the pose optimisation (SE3Quat::exp, se3quat.h:249-254).  The
+// device's double sin / cos are not glibc's, so the kernel, the C++ reference and the numpy
+// restatement share this one routine instead: the fdlibm algorithm (e_rem_pio2.c
+// medium path: Cody-Waite reduction by pi/2 in up to three steps; k_sin.c, k_cos.c polynomials on
+// |r| <= pi/4), every operation rounded on its own.  Valid for finite |x| <= ORBX_SINCOS_F64_LIMIT
+// (2^20); outside it returns false and leaves *s, *c untouched.  Below 1 ulp from the true value.
+#define ORBX_SINCOS_F64_LIMIT 1048576.0
+
+ORBX_HD int f64_exponent(double v) {
+    uint64_t u;
+    memcpy(&u, &v, 8);
+    return (int)((u >> 52) & 0x7ff);
+}
+
+ORBX_HD bool orbx_sincos_f64(double x, double* s, double* c) {
+    if (!(fabs(x) <= ORBX_SINCOS_F64_LIMIT)) return false;
+    const double invpio2 = 6.36619772367581382433e-01;
+    const double pio2_1 = 1.57079632673412561417e+00, pio2_1t = 6.07710050650619224932e-11;
+    const double pio2_2 = 6.07710050630396597660e-11, pio2_2t = 2.02226624879595063154e-21;
+    const double pio2_3 = 2.02226624871116645580e-21, pio2_3t = 8.47842766036889956997e-32;
+    const double fn = rint(x * invpio2);
+    const int n = (int)fn;
+    double r = x - fn * pio2_1;
+    double w = fn * pio2_1t;
+    double y0 = r - w;
+    const int ex = f64_exponent(x);
+    if (ex - f64_exponent(y0) > 16) {
+        double t = r;
+        w = fn * pio2_2;
+        r = t - w;
+        w = fn * pio2_2t - ((t - r) - w);
+        y0 = r - w;
+        if (ex - f64_exponent(y0) > 49) {
+            t = r;
+            w = fn * pio2_3;
+            r = t - w;
+            w = fn * pio2_3t - ((t - r) - w);
+            y0 = r - w;
+        }
+    }
+    const double y1 = (r - y0) - w;
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03,
+                 S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
+                 S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03,
+                 C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
+                 C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    const double z = y0 * y0;
+    const double v = z * y0;
+    const double rs = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+    const double ks = y0 - ((z * (0.5 * y1 - v * rs) - y1) - v * S1);
+    const double z2 = z * z;
+    const double rc = z * (C1 + z * (C2 + z * C3)) + (z2 * z2) * (C4 + z * (C5 + z * C6));
+    const double hz = 0.5 * z;
+    const double wc = 1.0 - hz;
+    const double kc = wc + (((1.0 - wc) - hz) + (z * rc - y0 * y1));
+    switch (n & 3) {
+        case 0: *s = ks; *c = kc; break;
+        case 1: *s = kc; *c = -ks; break;
+        case 2: *s = -ks; *c = -kc; break;
+        default: *s = -kc; *c = ks; break;
+    }
+    return true;
+}
+
 }  // namespace orbx

@@ -366,6 +366,77 @@ def project_map_points_batch_device(mode: int, d_jobs, njobs: int, d_mps, d_mp_o
         ptr(d_src_keys), ptr(d_skip), ptr(d_q), ptr(d_nactive), ctypes.c_void_p(stream)))
 
 
+# ---- Optimizer::PoseOptimization (include/orbx_frame.h) ----------------------------------------
+
+# the info word of orbx_pose_optimization* (ORBX_POSEOPT_*)
+POSEOPT_ROUNDS_MASK = 0x7
+POSEOPT_ITERS_SHIFT, POSEOPT_ITERS_MASK = 3, 0x7f
+POSEOPT_TRIALS_SHIFT, POSEOPT_TRIALS_MASK = 10, 0x1ff
+POSEOPT_REFUSED_MP_INDEX = 1 << 24
+POSEOPT_REFUSED_OCTAVE = 1 << 25
+POSEOPT_REFUSED_NLEVELS = 1 << 26
+POSEOPT_REFUSED_COUNT = 1 << 27
+POSEOPT_THETA_LIMIT = 1 << 28
+POSEOPT_NONPOSITIVE_SOLVE = 1 << 29
+POSEOPT_FEW_EDGES = 1 << 30
+POSEOPT_REFUSED_ANY = 0xf << 24
+
+
+def pose_optimization(pose: np.ndarray, keys_un: np.ndarray, mp_of_feat, mps: np.ndarray,
+                      u_right=None, outlier=None, device: int = 0):
+    """Optimizer::PoseOptimization(&frame) on the GPU for one frame (Optimizer.cc:245-457):
+    pose is the frame's FRAME_POSE_DTYPE record (mTcw, the camera, the scale table), keys_un
+    mvKeysUn, mp_of_feat[i] the index into mps (MAP_POINT_DTYPE; pos is read) of feature i's
+    MapPoint or -1, u_right mvuRight (None: every edge is mono), outlier mvbOutlier before the
+    call (None: zeros).  Returns (pose_out, outlier, ngood, info): the record with Rcw, tcw, Ow
+    replaced, mvbOutlier (written where a MapPoint is), the reference's return value and the
+    POSEOPT_* info word."""
+    from ._lib import check, load, ptr
+    p = np.ascontiguousarray(pose, FRAME_POSE_DTYPE).reshape(())
+    k = np.ascontiguousarray(keys_un, KEYPOINT_DTYPE)
+    m = np.ascontiguousarray(mp_of_feat, np.int32)
+    mp = np.ascontiguousarray(mps, MAP_POINT_DTYPE)
+    ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+    out = np.zeros(len(k), np.uint8) if outlier is None else \
+        np.array(outlier, np.uint8, copy=True, order="C")
+    if len(m) != len(k) or len(out) != len(k) or (ur is not None and len(ur) != len(k)):
+        raise ValueError("per-feature arrays have one entry per keypoint")
+    po = np.zeros((), FRAME_POSE_DTYPE)
+    ngood, info = ctypes.c_int32(0), ctypes.c_uint32(0)
+    check("orbx_pose_optimization", load().orbx_pose_optimization(
+        ptr(p), ptr(k), ptr(ur), len(k), ptr(m), ptr(mp), len(mp), ptr(po), ptr(out),
+        ctypes.byref(ngood), ctypes.byref(info), int(device)))
+    return po, out, ngood.value, info.value
+
+
+def pose_optimization_batch_device(d_poses, nframes: int, d_keys_un, d_u_right, d_feat_off,
+                                   max_feat: int, d_mp_of_feat, d_mps, d_mp_off, d_poses_out,
+                                   d_outlier, d_ngood, d_info, stream: int = 0):
+    """The same for `nframes` frames on device arrays (torch tensors), one launch: frame f's
+    features at [d_feat_off[f], d_feat_off[f+1]) of d_keys_un / d_u_right (None: mono) /
+    d_mp_of_feat / d_outlier, its MapPoints at [d_mp_off[f], d_mp_off[f+1]) of d_mps;
+    d_poses_out (may be d_poses), d_ngood [nframes] int32 and d_info [nframes] uint32 (int32
+    tensors hold the same bits)."""
+    from ._lib import check, load, ptr
+    check("orbx_pose_optimization_batch_device", load().orbx_pose_optimization_batch_device(
+        ptr(d_poses), int(nframes), ptr(d_keys_un), ptr(d_u_right), ptr(d_feat_off),
+        int(max_feat), ptr(d_mp_of_feat), ptr(d_mps), ptr(d_mp_off), ptr(d_poses_out),
+        ptr(d_outlier), ptr(d_ngood), ptr(d_info), ctypes.c_void_p(stream)))
+
+
+def matches_to_features_batch_device(d_match, d_q_off, d_feat_off, njobs: int, max_q: int,
+                                     max_feat: int, d_mp_of_feat, d_flagged, d_prior=None,
+                                     stream: int = 0):
+    """A batched projection search's d_match (the job-local feature of each query, or -1) as
+    mvpMapPoints: d_mp_of_feat (the job-local query of each feature, or -1); the highest query
+    wins a feature, d_prior (optional) fills the features no query names, d_flagged (one
+    int32) becomes 1 when a feature index lies outside its job."""
+    from ._lib import check, load, ptr
+    check("orbx_matches_to_features_batch_device", load().orbx_matches_to_features_batch_device(
+        ptr(d_match), ptr(d_q_off), ptr(d_feat_off), int(njobs), int(max_q), int(max_feat),
+        ptr(d_prior), ptr(d_mp_of_feat), ptr(d_flagged), ctypes.c_void_p(stream)))
+
+
 # ---- RGB-D frames (include/orbx_frame.h) -----------------------------------------------------
 
 # orbx_depth_type

@@ -27,7 +27,8 @@ from .extractor import ORBextractor
 from .features import (CLOSE_MAX_FEATURES, FRAME_GRID_COLS, FRAME_GRID_ROWS, PROJ_FRAME_MAPPOINTS,
                        PROJ_LAST_FRAME, PROJ_QUERY_DTYPE, FeatureSetC, _depth_type,
                        assign_grid_batch_device, close_points_batch_device, image_bounds,
-                       is_in_frustum_batch_device, project_map_points_batch_device,
+                       is_in_frustum_batch_device, matches_to_features_batch_device,
+                       pose_optimization_batch_device, project_map_points_batch_device,
                        rgbd_frame_geometry_batch_device, undistort_keypoints_batch_device)
 from .matcher import ORBmatcher
 
@@ -137,6 +138,48 @@ class MonoTrackBatch:
             PROJ_LAST_FRAME, self, d_qdesc, d_q, d_mp_off, d_match, d_nmatches, d_claimed,
             stream=stream)
 
+    _u_right = None     # the mono frames have no mvuRight: every PoseOptimization edge is mono
+
+    def matches_to_features(self, d_match, d_q_off, max_q: int, d_mp_of_feat, d_flagged,
+                            d_prior=None, stream: int = 0):
+        """A batched search's d_match (frame-local feature of each MapPoint) as mvpMapPoints:
+        d_mp_of_feat [B, kp_cap] int32, the index into the frame's MapPoint block of each
+        feature's MapPoint or -1 (the highest query wins a feature, ORBmatcher.cc:91, :1472);
+        d_prior: the MapPoints of an earlier search over the same block, kept where this one
+        names none."""
+        matches_to_features_batch_device(d_match, d_q_off, self.feat_off, self.batch, max_q,
+                                         self.max_feat, d_mp_of_feat, d_flagged, d_prior, stream)
+
+    def pose_optimization(self, d_poses, d_mp_of_feat, d_mps, d_mp_off, d_poses_out, d_outlier,
+                          d_ngood, d_info, stream: int = 0):
+        """Optimizer::PoseOptimization(&mCurrentFrame) for every frame of the last ``frames``
+        call (Tracking.cc:823, :953, :1001): d_poses [B] FRAME_POSE_DTYPE records (mTcw and the
+        camera), d_mp_of_feat [B, kp_cap] as ``matches_to_features`` writes it, frame j's
+        MapPoints at [d_mp_off[j], d_mp_off[j+1]) of d_mps.  Writes d_poses_out (the records
+        with the refined pose; may be d_poses), d_outlier [B, kp_cap] bytes (mvbOutlier, where a
+        MapPoint is), d_ngood [B] and the info words d_info [B].  RGBDTrackBatch's u_right makes
+        the edges of features with depth stereo."""
+        pose_optimization_batch_device(d_poses, self.batch, self.keys_un, self._u_right,
+                                       self.feat_off, self.max_feat, d_mp_of_feat, d_mps,
+                                       d_mp_off, d_poses_out, d_outlier, d_ngood, d_info, stream)
+
+    def track_with_motion_model_and_optimize(self, d_jobs, d_poses, d_mps, d_mp_off, max_mps: int,
+                                             d_src_keys, d_skip, d_q, d_qdesc, d_match,
+                                             d_nmatches, d_mp_of_feat, d_flagged, d_poses_out,
+                                             d_outlier, d_ngood, d_info, d_claimed=None,
+                                             d_nactive=None, stream: int = 0):
+        """TrackWithMotionModel up to and including its PoseOptimization (Tracking.cc:915-953)
+        on one stream with no host step: ``track_with_motion_model``, the scatter of d_match
+        into d_mp_of_feat, then ``pose_optimization`` from d_poses (the records d_jobs[j].cam
+        was built from).  d_poses_out is ready to be the d_frames of ``project_local_map``;
+        d_outlier masks the next d_skip / d_claimed (Tracking.cc:955-975 stays with the caller)."""
+        self.track_with_motion_model(d_jobs, d_mps, d_mp_off, max_mps, d_src_keys, d_skip, d_q,
+                                     d_qdesc, d_match, d_nmatches, d_claimed, d_nactive, stream)
+        self.matches_to_features(d_match, d_mp_off, max_mps, d_mp_of_feat, d_flagged,
+                                 stream=stream)
+        self.pose_optimization(d_poses, d_mp_of_feat, d_mps, d_mp_off, d_poses_out, d_outlier,
+                               d_ngood, d_info, stream)
+
     def __call__(self, images, d_qdesc, d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
                  stream: int = 0, local_map=None):
         """One tracking step of the B frames.  With `local_map` = (d_frames, d_mps, max_mps,
@@ -189,6 +232,7 @@ class RGBDTrackBatch(MonoTrackBatch):
         kc = self.kp_cap
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.u_right = torch.full((batch, kc), -1.0, **f32)
+        self._u_right = self.u_right
         self.depth = torch.full((batch, kc), -1.0, **f32)
         self.order = torch.zeros((batch, kc), dtype=torch.int32, device=self.dev)
         self.counts = torch.zeros((batch, 4), dtype=torch.int32, device=self.dev)
