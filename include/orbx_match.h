@@ -392,9 +392,12 @@ orbx_status orbx_hamming_bf_top2(orbx_matcher* m, const uint8_t* q, int32_t nq,
                                  int32_t* best_dist, int32_t* second_dist);
 /* The same on device arrays, on the caller's stream; best_idx is offset by idx_base (a shard
  * of a larger database reports global row numbers, so per-shard results merge in shard order
- * with distributed.merge_top2).  ndb < 2^31 - idx_base.  The partial results live in the
- * matcher's scratch: a call on another stream than the previous call's waits (on the device,
- * by an event) until that call's kernels are done with it. */
+ * with distributed.merge_top2; -1 stays -1).  idx_base >= 0 and ndb + idx_base < 2^31 - 1.
+ * d_q and d_db must be 4-byte aligned: the kernels read them as dwords, and the scalar loads
+ * of k_bf_top2 would drop the low address bits of a byte-offset view without a fault.  A call
+ * that breaks either rule returns ORBX_ERR_INVALID before anything is launched.  The partial
+ * results live in the matcher's scratch: a call on another stream than the previous call's
+ * waits (on the device, by an event) until that call's kernels are done with it. */
 orbx_status orbx_hamming_bf_top2_device(orbx_matcher* m, const uint8_t* d_q, int32_t nq,
                                         const uint8_t* d_db, int64_t ndb, int64_t idx_base,
                                         int32_t* d_best_idx, int32_t* d_best_dist,
@@ -409,6 +412,28 @@ orbx_status orbx_matcher_set_bf_kernel(orbx_matcher* m, int32_t kernel);
 const char* orbx_bf_kernel_name(int32_t kernel);
 /* The default's name ("k_bf_mfma"). */
 const char* orbx_bf_kernel(void);
+
+/* Rows per chunk of the brute-force top-2 (one workgroup per chunk and query block; the
+ * chunks' partial top-2 are folded by k_bf_merge).  A tuning and test knob: the results never
+ * depend on it.  0 (the default) = automatic, from the row and query counts and the device's
+ * CU count; any other value must be a multiple of 64 in [256, 2^23 - 64], else
+ * ORBX_ERR_INVALID and the setting stays as it was.  Launches nothing. */
+orbx_status orbx_matcher_set_bf_chunk(orbx_matcher* m, int64_t rows);
+
+/* The launch geometry a brute-force top-2 of nq queries against ndb rows would use with the
+ * handle's kernel, chunk setting and CU count (host only; the launcher evaluates the same
+ * functions).  The directed tests assert the regime they mean with it before they rely on it. */
+typedef struct {
+    int32_t chunk;          /* rows per chunk                                               */
+    int32_t nchunks;        /* ceil(ndb / chunk); 0 for an empty database                   */
+    int32_t query_blocks;   /* workgroups per chunk: 1024 (k_bf_mfma) / 256 (k_bf_top2)
+                               queries each                                                 */
+    int32_t nqpad;          /* query stride of the partial results (a multiple of 1024)     */
+    int32_t merge_slice;    /* chunks per thread slice of k_bf_merge: ceil(nchunks / 8)     */
+    int64_t partial_bytes;  /* scratch the partial results take                             */
+} orbx_bf_launch_info;
+orbx_status orbx_matcher_bf_launch_info(orbx_matcher* m, int32_t nq, int64_t ndb,
+                                        orbx_bf_launch_info* out);
 
 /* Waits for `stream` and returns ORBX_ERR_CAPACITY if a batched call on this matcher met a
  * keyframe above max_feat since the last sync (the flag is then cleared). */

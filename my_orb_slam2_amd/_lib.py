@@ -64,6 +64,13 @@ class RegimeInfo(ctypes.Structure):
                 ("nfeat", ctypes.c_int32 * 16)]
 
 
+class BfLaunchInfo(ctypes.Structure):
+    """orbx_bf_launch_info (include/orbx_match.h)."""
+    _fields_ = [("chunk", ctypes.c_int32), ("nchunks", ctypes.c_int32),
+                ("query_blocks", ctypes.c_int32), ("nqpad", ctypes.c_int32),
+                ("merge_slice", ctypes.c_int32), ("partial_bytes", ctypes.c_int64)]
+
+
 # name -> (restype, argtypes); the exported C ABI (include/orbx.h)
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -137,6 +144,8 @@ SIGNATURES = {
     "orbx_bf_kernel": (ctypes.c_char_p, []),
     "orbx_bf_kernel_name": (ctypes.c_char_p, [_i]),
     "orbx_matcher_set_bf_kernel": (_i, [_vp, _i]),
+    "orbx_matcher_set_bf_chunk": (_i, [_vp, ctypes.c_int64]),
+    "orbx_matcher_bf_launch_info": (_i, [_vp, _i, ctypes.c_int64, ctypes.POINTER(BfLaunchInfo)]),
     "orbx_hamming_bf_top2_device": (_i, [_vp, _vp, _i, _vp, ctypes.c_int64, ctypes.c_int64,
                                          _vp, _vp, _vp, _vp]),
     "orbx_matcher_profile_enable": (_i, [_vp, _i]),

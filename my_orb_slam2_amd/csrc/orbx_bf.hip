@@ -52,6 +52,9 @@ __device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
 
 static_assert(BF_ROW_BITS == 23, "the key's shift is written out in k_bf_top2");
 
+// Chunks per thread slice of k_bf_merge (8 slices); the kernel and bf_geometry share it.
+__host__ __device__ constexpr int bf_merge_slice(int nchunks) { return (nchunks + 7) / 8; }
+
 __global__ __launch_bounds__(256) void k_bf_top2(const uint32_t* __restrict__ q, int nq,
                                                   const uint32_t* __restrict__ db, long long ndb,
                                                   int chunk, int nqpad, uint2* __restrict__ part) {
@@ -320,7 +323,7 @@ __global__ __launch_bounds__(256) void k_bf_merge(const uint2* __restrict__ part
     __shared__ long long srow[8][32];
     const int ql = (int)threadIdx.x & 31, sl = (int)threadIdx.x >> 5;
     const int qi = blockIdx.x * 32 + ql;
-    const int L = (nchunks + 7) / 8;
+    const int L = bf_merge_slice(nchunks);
     const int c0 = sl * L, c1 = min(nchunks, c0 + L);
     uint32_t d1 = 256, d2 = 256;
     long long row = -1;
@@ -377,10 +380,23 @@ int bf_chunk_rows(long long ndb, int nq, int ncu, int kernel) {
     return (int)rows;
 }
 
+bool bf_chunk_valid(long long rows) {
+    return rows >= BF_BLK && rows <= (1ll << BF_ROW_BITS) - 64 && rows % 64 == 0;
+}
+
+BfGeometry bf_geometry(long long ndb, int nq, int chunk, int kernel) {
+    BfGeometry g{};
+    g.nchunks = ndb > 0 ? (ndb + chunk - 1) / chunk : 0;
+    // the partials' query stride: a multiple of both kernels' queries per workgroup
+    g.nqpad = ((nq + BF_MFMA_Q - 1) / BF_MFMA_Q) * BF_MFMA_Q;
+    g.query_blocks = g.nqpad / (kernel == ORBX_BF_VALU ? 256 : BF_MFMA_Q);
+    g.merge_slice = g.nchunks <= INT32_MAX / 2 ? bf_merge_slice((int)g.nchunks) : 0;
+    g.partial_bytes = (size_t)g.nchunks * (size_t)g.nqpad * sizeof(uint2);
+    return g;
+}
+
 size_t bf_partial_bytes(long long ndb, int nq, int chunk) {
-    const long long nchunks = (ndb + chunk - 1) / chunk;
-    const int nqpad = ((nq + BF_MFMA_Q - 1) / BF_MFMA_Q) * BF_MFMA_Q;
-    return (size_t)nchunks * (size_t)nqpad * sizeof(uint2);
+    return bf_geometry(ndb, nq, chunk, ORBX_BF_MFMA).partial_bytes;
 }
 
 const char* bf_kernel_name(int kernel) {
@@ -389,17 +405,17 @@ const char* bf_kernel_name(int kernel) {
 
 hipError_t launch_bf_top2(const BfLaunch& a, hipStream_t st, KernelTimer* timer) {
     if (a.nq <= 0) return hipSuccess;
-    // the partials' query stride: a multiple of both kernels' queries per workgroup
-    const int nqpad = ((a.nq + BF_MFMA_Q - 1) / BF_MFMA_Q) * BF_MFMA_Q;
-    const long long nchunks = a.ndb > 0 ? (a.ndb + a.chunk - 1) / a.chunk : 0;
+    const BfGeometry g = bf_geometry(a.ndb, a.nq, a.chunk, a.kernel);
+    const int nqpad = g.nqpad;
+    const long long nchunks = g.nchunks;
     if (nchunks > INT32_MAX / 2) return hipErrorInvalidValue;
     hipEvent_t e = timer ? timer->start(st) : nullptr;
     if (nchunks > 0 && a.kernel == ORBX_BF_VALU)
-        hipLaunchKernelGGL(k_bf_top2, dim3(nqpad / 256, (unsigned)nchunks), dim3(256), 0, st,
+        hipLaunchKernelGGL(k_bf_top2, dim3(g.query_blocks, (unsigned)nchunks), dim3(256), 0, st,
                            (const uint32_t*)a.q, a.nq, (const uint32_t*)a.db, a.ndb, a.chunk,
                            nqpad, (uint2*)a.part);
     else if (nchunks > 0)
-        hipLaunchKernelGGL(k_bf_mfma, dim3(nqpad / BF_MFMA_Q, (unsigned)nchunks),
+        hipLaunchKernelGGL(k_bf_mfma, dim3(g.query_blocks, (unsigned)nchunks),
                            dim3(BF_MFMA_Q), 0, st, (const uint32_t*)a.q, a.nq,
                            (const uint32_t*)a.db, a.ndb, a.chunk, nqpad, (uint2*)a.part);
     hipLaunchKernelGGL(k_bf_merge, dim3((a.nq + 31) / 32), dim3(256), 0, st, (const uint2*)a.part,

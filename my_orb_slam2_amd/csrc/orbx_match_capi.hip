@@ -37,6 +37,7 @@ struct orbx_matcher {
     hipStream_t bf_stream = nullptr;
     bool have_bf = false;
     int bf_kernel = ORBX_BF_MFMA;
+    int bf_chunk = 0;               // orbx_matcher_set_bf_chunk: 0 = bf_chunk_rows
 };
 
 namespace {
@@ -835,6 +836,11 @@ orbx_status orbx_compute_distinctive_descriptors_device(orbx_matcher* m, const u
 }
 
 namespace {
+// Rows per chunk of a call on this handle: the caller's override, else bf_chunk_rows
+int bf_chunk_of(const orbx_matcher* m, long long ndb, int nq) {
+    return m->bf_chunk ? m->bf_chunk : bf_chunk_rows(ndb, nq, m->ncu, m->bf_kernel);
+}
+
 orbx_status bf_run(orbx_matcher* m, const uint8_t* d_q, int nq, const uint8_t* d_db,
                    long long ndb, long long idx_base, int32_t* bi, int32_t* bd, int32_t* sd,
                    hipStream_t st) {
@@ -844,7 +850,7 @@ orbx_status bf_run(orbx_matcher* m, const uint8_t* d_q, int nq, const uint8_t* d
     a.db = d_db;
     a.ndb = ndb;
     a.idx_base = idx_base;
-    a.chunk = bf_chunk_rows(ndb, nq, m->ncu, m->bf_kernel);
+    a.chunk = bf_chunk_of(m, ndb, nq);
     const size_t need = bf_partial_bytes(ndb, nq, a.chunk);
     // growing frees the scratch an earlier launch (any stream) may still use
     if (need > m->d_bf.n && m->have_bf && !HIPOK(hipEventSynchronize(m->bf_done)))
@@ -906,12 +912,37 @@ orbx_status orbx_matcher_set_bf_kernel(orbx_matcher* m, int32_t kernel) {
     return ORBX_OK;
 }
 
+orbx_status orbx_matcher_set_bf_chunk(orbx_matcher* m, int64_t rows) {
+    if (!m || (rows != 0 && !orbx::bf_chunk_valid(rows))) return ORBX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(m->mu);
+    m->bf_chunk = (int)rows;
+    return ORBX_OK;
+}
+
+orbx_status orbx_matcher_bf_launch_info(orbx_matcher* m, int32_t nq, int64_t ndb,
+                                        orbx_bf_launch_info* out) {
+    if (!m || !out || nq < 0 || ndb < 0 || ndb >= INT32_MAX) return ORBX_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(m->mu);
+    const int chunk = bf_chunk_of(m, ndb, nq);
+    const orbx::BfGeometry g = orbx::bf_geometry(ndb, nq, chunk, m->bf_kernel);
+    out->chunk = chunk;
+    out->nchunks = (int32_t)g.nchunks;
+    out->query_blocks = g.query_blocks;
+    out->nqpad = g.nqpad;
+    out->merge_slice = g.merge_slice;
+    out->partial_bytes = (int64_t)g.partial_bytes;
+    return ORBX_OK;
+}
+
 orbx_status orbx_hamming_bf_top2_device(orbx_matcher* m, const uint8_t* d_q, int32_t nq,
                                         const uint8_t* d_db, int64_t ndb, int64_t idx_base,
                                         int32_t* d_best_idx, int32_t* d_best_dist,
                                         int32_t* d_second_dist, void* stream) {
     if (!m || nq < 0 || ndb < 0 || idx_base < 0 || ndb + idx_base >= INT32_MAX)
         return ORBX_ERR_INVALID;
+    // the kernels read both arrays as dwords (k_bf_top2 by scalar loads, which drop the
+    // address's low two bits without a fault)
+    if ((((uintptr_t)d_q) | ((uintptr_t)d_db)) & 3u) return ORBX_ERR_INVALID;
     if (nq == 0) return ORBX_OK;
     if (!d_q || !d_best_idx || !d_best_dist || !d_second_dist || (ndb > 0 && !d_db))
         return ORBX_ERR_INVALID;

@@ -139,6 +139,19 @@ struct BfLaunch {
     int kernel;            // ORBX_BF_MFMA / ORBX_BF_VALU
 };
 int bf_chunk_rows(long long ndb, int nq, int ncu, int kernel);
+// A caller's chunk (orbx_matcher_set_bf_chunk): a multiple of 64 in [256, 2^23 - 64]
+bool bf_chunk_valid(long long rows);
+// The launch geometry of (ndb, nq, chunk, kernel): launch_bf_top2 sizes its grids, the
+// partials' stride and k_bf_merge's slices from it, bf_partial_bytes the scratch, and
+// orbx_matcher_bf_launch_info reports it.
+struct BfGeometry {
+    long long nchunks;     // ceil(ndb / chunk): the grids' y
+    int query_blocks;      // the distance kernel's grid x (256 / 1024 queries per workgroup)
+    int nqpad;             // the partials' query stride
+    int merge_slice;       // chunks per thread slice of k_bf_merge (its L)
+    size_t partial_bytes;
+};
+BfGeometry bf_geometry(long long ndb, int nq, int chunk, int kernel);
 size_t bf_partial_bytes(long long ndb, int nq, int chunk);
 struct KernelTimer;
 hipError_t launch_bf_top2(const BfLaunch& a, hipStream_t st, KernelTimer* timer);

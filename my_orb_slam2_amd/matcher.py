@@ -322,6 +322,21 @@ class ORBmatcher:
         (k_bf_top2: v_xor + v_bcnt); the results are identical."""
         check("orbx_matcher_set_bf_kernel", self._lib.orbx_matcher_set_bf_kernel(self._h, int(kernel)))
 
+    def set_bf_chunk(self, rows):
+        """Rows per chunk of the brute-force top-2 (a tuning and test knob; the results never
+        depend on it): 0 = automatic, else a multiple of 64 in [256, 2^23 - 64]."""
+        check("orbx_matcher_set_bf_chunk", self._lib.orbx_matcher_set_bf_chunk(self._h, int(rows)))
+
+    def bf_launch_info(self, nq, ndb) -> dict:
+        """The launch geometry of a brute-force top-2 of nq queries against ndb rows on this
+        handle (include/orbx_match.h orbx_matcher_bf_launch_info): chunk, nchunks,
+        query_blocks, nqpad, merge_slice, partial_bytes."""
+        from ._lib import BfLaunchInfo
+        r = BfLaunchInfo()
+        check("orbx_matcher_bf_launch_info", self._lib.orbx_matcher_bf_launch_info(
+            self._h, int(nq), int(ndb), ctypes.byref(r)))
+        return {k: int(getattr(r, k)) for k, _ in BfLaunchInfo._fields_}
+
     def hamming_bf_top2(self, q, db):
         """Brute-force Hamming top-2 of every query row against every database row, with the
         best / second loop of the ORBmatcher searches (src/ORBmatcher.cc:232-256): returns
