@@ -467,6 +467,113 @@ orbx_status orbx_compute_distinctive_descriptors_device(orbx_matcher* m, const u
 enum { ORBX_VK_BOW_KF_FRAME = 0, ORBX_VK_BOW_KF_KF = 1, ORBX_VK_INIT = 2, ORBX_VK_PROJ = 16 };
 int32_t orbx_matcher_variant(int32_t kind, int32_t n_a, int32_t n_b, int32_t nq);
 
+/* ---- Sim3Solver (src/Sim3Solver.cc; LoopClosing::ComputeSim3, LoopClosing.cc:285-413) -------
+ * Horn's closed-form similarity from three correspondences inside the reference's RANSAC loop,
+ * between SearchByBoW(KF, KF) and SearchBySim3.  What stays with the caller: the object tests of
+ * the constructor (isBad, GetIndexInKeyFrame, :64-79), the rand() stream (the library never calls
+ * rand(): orbx_sim3_sample_triples turns the caller's raw rand() values into the minimal sets of
+ * :163-177), and OptimizeSim3.  The arithmetic is the reference's statement by statement; the
+ * forms evaluated inside OpenCV 3.2 are restated and PARITY UNPINNED. */
+
+/* One kept correspondence (:81-100): i1 = the slot in vpMatched12, the two world positions
+ * (pMP1 / pMP2 ->GetWorldPos()) and the octaves of the two undistorted keypoints. */
+typedef struct {
+    int32_t i1;
+    float X1w[3];
+    float X2w[3];
+    int32_t octave1, octave2;
+} orbx_sim3_corr;
+
+/* One solver.  kf1 / kf2 index the pose array (read: Rcw, tcw, fx, fy, cx, cy); sigma2_1 / _2 are
+ * the keyframes' mvLevelSigma2 with nlevels1 / nlevels2 entries in [1, 16].  The N correspondences
+ * are corr[corr_off .. corr_off + N); the inlier bytes are inliers[inlier_off .. + mN1); the
+ * minimal set of iteration k (0-based, counted from SetRansacParameters on) is
+ * triples[3 * (triple_off + k) ..], k < max_its.  max_its is mRansacMaxIts as
+ * orbx_sim3_ransac_iterations returns it; n_iterations is the argument of iterate(). */
+typedef struct {
+    int32_t kf1, kf2;
+    float sigma2_1[16], sigma2_2[16];
+    int32_t nlevels1, nlevels2;
+    int32_t mN1, N, corr_off, inlier_off, triple_off;
+    int32_t fix_scale, min_inliers, max_its, n_iterations;
+} orbx_sim3_job;
+
+/* mnIterations and mnBestInliers, kept across calls of iterate() (in / out). */
+typedef struct {
+    int32_t iterations, best_inliers;
+} orbx_sim3_state;
+
+#define ORBX_SIM3_REFUSED_OCTAVE (1u << 24)  /* an octave outside [0, nlevels), or nlevels outside [1, 16] */
+#define ORBX_SIM3_REFUSED_TRIPLE (1u << 25)  /* a minimal-set index outside [0, N) or repeated            */
+#define ORBX_SIM3_REFUSED_I1 (1u << 26)      /* an i1 outside [0, mN1)                                     */
+#define ORBX_SIM3_REFUSED_LIMIT (1u << 27)   /* N above max_n, the call's iterations above max_call_its,
+                                                max_its outside [1, limit], a negative count or state    */
+#define ORBX_SIM3_REFUSED_RANGE (1u << 28)   /* kf1 / kf2 or an offset outside the arrays of the call      */
+#define ORBX_SIM3_REFUSED_ANY (0x1fu << 24)
+
+/* What one iterate() call gives.  found: a model was returned (:192-199) at the 1-based iteration
+ * `iteration` with n_inliers inliers, and the job's inlier bytes are set through i1.  no_more:
+ * bNoMore.  best_updated: `mnInliersi >= mnBestInliers` held at least once in this call; R12
+ * (mBestRotation, row-major), t12, s12, T12 (mBestT12) and best_inliers then hold the last such
+ * iteration's model, which is the returned one when found; otherwise they are not written, and
+ * iteration / n_inliers are 0.  info: ORBX_SIM3_REFUSED_* bits; a refused job gets found = 0 and
+ * info, and nothing else of its outputs, its state or its inlier bytes is touched. */
+typedef struct {
+    int32_t found, iteration, n_inliers, no_more;
+    uint32_t info;
+    int32_t best_updated, best_inliers;
+    float R12[9], t12[3], s12, T12[16];
+} orbx_sim3_result;
+
+/* SetRansacParameters (:114-138), host only: epsilon = (float)min_inliers / N, nIterations =
+ * ceil(log(1 - prob) / log(1 - pow(epsilon, 3))) in double with the host's libm (1 when
+ * min_inliers == N), converted to int as x86-64 does (out of range or NaN: INT_MIN), and
+ * max(1, min(nIterations, max_its)) returned. */
+int32_t orbx_sim3_ransac_iterations(double prob, int32_t min_inliers, int32_t max_its, int32_t N);
+
+/* The minimal sets of n_its iterations (:163-177) from 3 * n_its raw rand() values in
+ * [0, RAND_MAX]: three draws without replacement by swap-with-last over 0 .. N-1, each draw
+ * DUtils::Random::RandomInt(0, size - 1) = int(((double)r / ((double)RAND_MAX + 1.0)) * size).
+ * ORBX_ERR_INVALID: N < 3, n_its < 0, a NULL array with n_its > 0, a value outside [0, RAND_MAX]. */
+orbx_status orbx_sim3_sample_triples(int32_t N, int32_t n_its, const int32_t* rand_values,
+                                     int32_t* triples);
+
+/* The largest N (max_n), iterations per call (max_call_its, also the largest max_its) and jobs a
+ * call takes, and the scratch bytes a call may need at most (host only; the launcher evaluates
+ * the same expressions).  NULL outputs are skipped. */
+orbx_status orbx_sim3_limits(int32_t* max_n, int32_t* max_its, int32_t* max_jobs,
+                             int64_t* max_scratch_bytes);
+
+/* iterate(n_iterations) of njobs solvers at once, every array on the device, on `stream` with no
+ * host step: k_sim3_prepare (camera-frame points, image points, the two size_t bounds),
+ * k_sim3_hypotheses (one wave per iteration of the call: the model, then the inlier count) and
+ * k_sim3_select (the first returning iteration in order, the last `>=` record, the inlier bytes,
+ * the state).  max_n >= every job's N and max_call_its >= every job's iterations in this call
+ * (min(max_its - iterations, n_iterations)) size the grids and the matcher's scratch; ncorr,
+ * ntriples (triples, i.e. 3 ints each), ninlier_bytes and nposes are the lengths of the arrays,
+ * and a job that points outside them is refused.  d_state is in / out, d_results and d_inliers out.
+ * ORBX_ERR_INVALID: m NULL, a NULL array with njobs > 0, a negative count.  max_n, max_call_its or
+ * njobs above orbx_sim3_limits, or their scratch above its bound: ORBX_ERR_UNSUPPORTED.
+ * njobs == 0: ORBX_OK, nothing touched.  Calls on one matcher share its scratch: one stream, or
+ * serialised. */
+orbx_status orbx_sim3_iterate_batch_device(
+    orbx_matcher* m, const orbx_sim3_job* d_jobs, int32_t njobs, int32_t max_n,
+    int32_t max_call_its, const orbx_frame_pose* d_poses, int32_t nposes,
+    const orbx_sim3_corr* d_corr, int64_t ncorr, const int32_t* d_triples, int64_t ntriples,
+    orbx_sim3_state* d_state, orbx_sim3_result* d_results, uint8_t* d_inliers,
+    int64_t ninlier_bytes, void* stream);
+
+/* One solver from host arrays (copied to the device for the call).  job->kf1, kf2 and the three
+ * offsets are ignored: corr holds job->N records, triples 3 * job->max_its ints, inliers job->mN1
+ * bytes.  ORBX_ERR_INVALID: a NULL argument, N, mN1 or n_iterations negative, max_its < 1; N or
+ * max_its above orbx_sim3_limits: ORBX_ERR_UNSUPPORTED; the checks run before the device is
+ * touched, and without a GPU the call returns ORBX_ERR_DEVICE.  What the batched form refuses per
+ * job comes back the same way, in res->info.  Calls are serialised inside the library. */
+orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pose* pose2,
+                              const orbx_sim3_job* job, const orbx_sim3_corr* corr,
+                              const int32_t* triples, orbx_sim3_state* state,
+                              orbx_sim3_result* res, uint8_t* inliers, int device);
+
 /* ---- per-kernel timing for the matcher handle ------------------------------------------ */
 typedef enum {
     ORBX_MK_BOW = 0, ORBX_MK_TRIANGULATE, ORBX_MK_PROJ_SEARCH, ORBX_MK_PROJ_RESOLVE,

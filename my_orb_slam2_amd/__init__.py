@@ -9,6 +9,8 @@ Host-side mirror of the reference's operator interface for this path:
   LocalMapping::CreateNewMapPoints behind SearchForTriangulation (src/LocalMapping.cc:356-507)
 * ``pose_optimization`` / ``MonoTrackBatch.pose_optimization`` — Optimizer::PoseOptimization, the
   pose-only fit of a frame to its MapPoints (src/Optimizer.cc:245-457)
+* ``Sim3Solver`` / ``ORBmatcher.sim3_iterate_batch_device`` — Horn's closed form inside the
+  reference's RANSAC loop for loop-closure candidates (src/Sim3Solver.cc)
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
@@ -31,6 +33,8 @@ from .tracking import MonoTrackBatch, RGBDTrackBatch
 from .features import (PROJ_JOB_DTYPE, PROJ_SIM3, matches_to_features_batch_device,
                        pose_optimization, pose_optimization_batch_device, proj_job,
                        project_map_points, project_map_points_batch_device)
+from .sim3 import (Sim3Solver, sim3_iterate, sim3_job, sim3_limits, sim3_ransac_iterations,
+                   sim3_sample_triples)
 from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
                       load_stereo_settings, remap_fixed_point, remap_stereo_batch_device)
 
@@ -42,4 +46,5 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "PROJ_JOB_DTYPE", "PROJ_SIM3", "proj_job", "project_map_points",
            "project_map_points_batch_device", "TRI_CODES", "parallax_stereo_cos",
            "triangulate_matches", "pose_optimization", "pose_optimization_batch_device",
-           "matches_to_features_batch_device"]
+           "matches_to_features_batch_device", "Sim3Solver", "sim3_iterate", "sim3_job",
+           "sim3_limits", "sim3_ransac_iterations", "sim3_sample_triples"]

@@ -152,6 +152,13 @@ SIGNATURES = {
     "orbx_matcher_profile_collect": (_i, [_vp, _vp, _vp]),
     "orbx_match_kernel_name": (ctypes.c_char_p, [_i]),
     "orbx_matcher_variant": (_i, [_i, _i, _i, _i]),
+    "orbx_sim3_ransac_iterations": (_i, [ctypes.c_double, _i, _i, _i]),
+    "orbx_sim3_sample_triples": (_i, [_i, _i, _vp, _vp]),
+    "orbx_sim3_limits": (_i, [_vp, _vp, _vp, _vp]),
+    "orbx_sim3_iterate_batch_device": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, ctypes.c_int64,
+                                            _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
+                                            _vp]),
+    "orbx_sim3_iterate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     # include/orbx_vocab.h
     "orbx_vocabulary_load_text": (_i, [ctypes.c_char_p, _i, ctypes.POINTER(_vp)]),
     "orbx_vocabulary_destroy": (_i, [_vp]),

@@ -24,7 +24,7 @@ LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
            "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
-           "orbx_poseopt.hip"]
+           "orbx_poseopt.hip", "orbx_sim3.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_kernels.h", "orbx_host.h",
            "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
            "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
@@ -330,3 +330,30 @@ def build_poseopt_ref(force: bool = False, verbose: bool = False) -> pathlib.Pat
     subprocess.run(cmd, check=True)
     os.replace(str(POSEOPT_REF_BIN) + ".tmp", POSEOPT_REF_BIN)
     return POSEOPT_REF_BIN
+
+
+# ---- Sim3Solver restated over the cv stand-in (tests/native/sim3_ref.cpp) -------------------------
+SIM3_REF_SRC = PKG.parent / "tests" / "native" / "sim3_ref.cpp"
+SIM3_REF_BIN = PKG.parent / "tests" / "native" / "sim3_ref"
+
+
+def build_sim3_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on the cv stand-in, tests/native/cv_sim3_standin.hpp, the record layouts of include/ and
+    csrc/orbx_math.h (orbx_atan2_f64, orbx_sincos_f64) only: no liborbx and no GPU (the CPU
+    reference of orbx_sim3_iterate*)."""
+    root = PKG.parent
+    native = root / "tests" / "native"
+    deps = ([SIM3_REF_SRC, native / "cv_sim3_standin.hpp", CSRC / "orbx_math.h"] +
+            sorted((root / "include").glob("*.h")) + sorted((native / "cv_standin").rglob("*.hpp")))
+    newest = max(p.stat().st_mtime for p in deps)
+    if not force and SIM3_REF_BIN.exists() and SIM3_REF_BIN.stat().st_mtime >= newest:
+        return SIM3_REF_BIN
+    # -ffp-contract=off: every operation rounded on its own, as in the kernels
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(CSRC), "-I" + str(native / "cv_standin"),
+           "-I" + str(native), str(SIM3_REF_SRC), "-o", str(SIM3_REF_BIN) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(SIM3_REF_BIN) + ".tmp", SIM3_REF_BIN)
+    return SIM3_REF_BIN

@@ -26,7 +26,7 @@ struct orbx_matcher {
     orbx_matcher_params prm;
     hipStream_t stream = nullptr;
     int ncu = 256;                     // compute units of the device (BF chunk sizing)
-    DevBuf d_in, d_out, d_aux, d_proj, d_bf;
+    DevBuf d_in, d_out, d_aux, d_proj, d_bf, d_sim3;
     int* d_err = nullptr;
     std::vector<uint8_t> staging;
     KernelTimer timer;
@@ -384,6 +384,7 @@ orbx_status orbx_matcher_destroy(orbx_matcher* m) {
     m->d_aux.release();
     m->d_proj.release();
     m->d_bf.release();
+    m->d_sim3.release();
     if (m->d_err) (void)hipFree(m->d_err);
     m->timer.destroy();
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -717,6 +718,44 @@ orbx_status orbx_triangulate_matches_batch_device(
     L.err = m->d_err;
     if (!HIPOK(launch_triangulate_points(L, db->max_feat, njobs, (hipStream_t)stream)))
         return ORBX_ERR_DEVICE;
+    return ORBX_OK;
+}
+
+orbx_status orbx_sim3_iterate_batch_device(
+    orbx_matcher* m, const orbx_sim3_job* d_jobs, int32_t njobs, int32_t max_n,
+    int32_t max_call_its, const orbx_frame_pose* d_poses, int32_t nposes,
+    const orbx_sim3_corr* d_corr, int64_t ncorr, const int32_t* d_triples, int64_t ntriples,
+    orbx_sim3_state* d_state, orbx_sim3_result* d_results, uint8_t* d_inliers,
+    int64_t ninlier_bytes, void* stream) {
+    if (!m || njobs < 0 || max_n < 0 || max_call_its < 0 || nposes < 0 || ncorr < 0 ||
+        ntriples < 0 || ninlier_bytes < 0)
+        return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_jobs || !d_poses || !d_triples || !d_state || !d_results || (ncorr > 0 && !d_corr) ||
+        (ninlier_bytes > 0 && !d_inliers))
+        return ORBX_ERR_INVALID;
+    if (njobs > SIM3_MAX_JOBS || max_n > SIM3_MAX_N || max_call_its > SIM3_MAX_ITS)
+        return ORBX_ERR_UNSUPPORTED;
+    const size_t bytes = sim3_scratch_bytes(njobs, max_n, max_call_its);
+    if (bytes > SIM3_MAX_SCRATCH) return ORBX_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
+    if (!m->d_sim3.ensure(bytes)) return ORBX_ERR_DEVICE;
+    Sim3Launch L{};
+    L.jobs = d_jobs;
+    L.njobs = njobs, L.max_n = max_n, L.max_call = max_call_its;
+    L.poses = d_poses;
+    L.nposes = nposes;
+    L.corr = d_corr;
+    L.ncorr = ncorr;
+    L.triples = d_triples;
+    L.ntriples = ntriples;
+    L.state = d_state;
+    L.res = d_results;
+    L.inliers = d_inliers;
+    L.ninliers = ninlier_bytes;
+    L.scratch = m->d_sim3.p;
+    if (!HIPOK(launch_sim3(L, (hipStream_t)stream))) return ORBX_ERR_DEVICE;
     return ORBX_OK;
 }
 

@@ -74,6 +74,28 @@ struct TriPointsLaunch {
 hipError_t launch_triangulate_points(const TriPointsLaunch& a, int max_feat, int njobs,
                                      hipStream_t st);
 
+// Sim3Solver::iterate over njobs solvers (orbx_sim3.hip).  The array lengths bound what a job may
+// point at; scratch holds sim3_scratch_bytes(njobs, max_n, max_call) bytes.
+struct Sim3Launch {
+    const orbx_sim3_job* jobs;
+    int njobs, max_n, max_call;
+    const orbx_frame_pose* poses;
+    int nposes;
+    const orbx_sim3_corr* corr;
+    long long ncorr;
+    const int32_t* triples;
+    long long ntriples;
+    orbx_sim3_state* state;
+    orbx_sim3_result* res;
+    uint8_t* inliers;
+    long long ninliers;
+    void* scratch;
+};
+constexpr int SIM3_MAX_N = 8192, SIM3_MAX_ITS = 4096, SIM3_MAX_JOBS = 65535;
+constexpr size_t SIM3_MAX_SCRATCH = (size_t)1 << 30;
+size_t sim3_scratch_bytes(int njobs, int max_n, int max_call);
+hipError_t launch_sim3(const Sim3Launch& a, hipStream_t st);
+
 // Projection searches (modes of orbx_proj_mode plus PROJ_INIT) over njobs independent jobs
 // (frames).  With t_off == nullptr there is one job: target T, queries [0, nq).  Otherwise
 // job j's target is T's arrays offset by t_off[j] features (keys/desc/u_right/claimed) and

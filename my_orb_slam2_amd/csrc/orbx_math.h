@@ -230,6 +230,8 @@ ORBX_HD float glibc_logf(float x) {
 // medium path: Cody-Waite reduction by pi/2 in up to three steps; k_sin.c, k_cos.c polynomials on
 // |r| <= pi/4), every operation rounded on its own.  Valid for finite |x| <= ORBX_SINCOS_F64_LIMIT
 // (2^20); outside it returns false and leaves *s, *c untouched.  Below 1 ulp from the true value.
+// A NaN x is outside the limit too: a caller that wants libm's sin(NaN) = cos(NaN) = NaN sets them
+// itself on false, as the Sim3 solver's Rodrigues step does (theta = 2 * ang <= 2 * pi otherwise).
 #define ORBX_SINCOS_F64_LIMIT 1048576.0
 
 ORBX_HD int f64_exponent(double v) {
@@ -287,6 +289,98 @@ ORBX_HD bool orbx_sincos_f64(double x, double* s, double* c) {
         default: *s = -kc; *c = ks; break;
     }
     return true;
+}
+
+// atan2 of two doubles for the Sim3 solver's rotation angle (Sim3Solver.cc:278).  As with
+// orbx_sincos_f64 the kernel, the C++ reference and the numpy restatement share this routine: the
+// fdlibm algorithm (e_atan2.c over s_atan.c: argument reduction to one of four intervals, an odd
+// polynomial of degree 23), every operation rounded on its own, with fdlibm's NaN, infinity and
+// signed-zero cases.  Below 1 ulp from the true value.
+// The quotients of the reduction in one place: an IEEE division on the host and on the device
+// (the double `/` of device code is the correctly rounded expansion, as __ddiv_rn is).
+ORBX_HD double orbx_div_f64(double a, double b) { return a / b; }
+
+ORBX_HD double orbx_atan_f64(double x) {
+    const double hi0 = 4.63647609000806093515e-01, hi1 = 7.85398163397448278999e-01,
+                 hi2 = 9.82793723247329054082e-01, hi3 = 1.57079632679489655800e+00;
+    const double lo0 = 2.26987774529616870924e-17, lo1 = 3.06161699786838301793e-17,
+                 lo2 = 1.39033110312309984516e-17, lo3 = 6.12323399573676603587e-17;
+    const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01,
+                 aT2 = 1.42857142725034663711e-01, aT3 = -1.11111104054623557880e-01,
+                 aT4 = 9.09088713343650656196e-02, aT5 = -7.69187620504482999495e-02,
+                 aT6 = 6.66107313738753120669e-02, aT7 = -5.83357013379057348645e-02,
+                 aT8 = 4.97687799461593236017e-02, aT9 = -3.65315727442169155270e-02,
+                 aT10 = 1.62858201153657823623e-02;
+    uint64_t u;
+    memcpy(&u, &x, 8);
+    const int32_t hx = (int32_t)(u >> 32);
+    const uint32_t lx = (uint32_t)u;
+    const int32_t ix = hx & 0x7fffffff;
+    if (ix >= 0x44100000) {                      // |x| >= 2^66
+        if (ix > 0x7ff00000 || (ix == 0x7ff00000 && lx != 0)) return x + x;   // NaN
+        return hx > 0 ? hi3 + lo3 : -hi3 - lo3;
+    }
+    int id;
+    double hi = 0.0, lo = 0.0;
+    if (ix < 0x3fdc0000) {                       // |x| < 0.4375
+        if (ix < 0x3e200000) return x;           // |x| < 2^-29
+        id = -1;
+    } else {
+        x = fabs(x);
+        if (ix < 0x3ff30000) {
+            if (ix < 0x3fe60000) { id = 0; hi = hi0; lo = lo0; x = orbx_div_f64(2.0 * x - 1.0, 2.0 + x); }
+            else { id = 1; hi = hi1; lo = lo1; x = orbx_div_f64(x - 1.0, x + 1.0); }
+        } else {
+            if (ix < 0x40038000) { id = 2; hi = hi2; lo = lo2; x = orbx_div_f64(x - 1.5, 1.0 + 1.5 * x); }
+            else { id = 3; hi = hi3; lo = lo3; x = orbx_div_f64(-1.0, x); }
+        }
+    }
+    const double z = x * x;
+    const double w = z * z;
+    const double s1 = z * (aT0 + w * (aT2 + w * (aT4 + w * (aT6 + w * (aT8 + w * aT10)))));
+    const double s2 = w * (aT1 + w * (aT3 + w * (aT5 + w * (aT7 + w * aT9))));
+    if (id < 0) return x - x * (s1 + s2);
+    const double r = hi - ((x * (s1 + s2) - lo) - x);
+    return hx < 0 ? -r : r;
+}
+
+ORBX_HD double orbx_atan2_f64(double y, double x) {
+    const double tiny = 1.0e-300, pi_o_4 = 7.8539816339744827900E-01,
+                 pi_o_2 = 1.5707963267948965580E+00, pi = 3.1415926535897931160E+00,
+                 pi_lo = 1.2246467991473531772E-16;
+    uint64_t ux, uy;
+    memcpy(&ux, &x, 8);
+    memcpy(&uy, &y, 8);
+    const int32_t hx = (int32_t)(ux >> 32), hy = (int32_t)(uy >> 32);
+    const uint32_t lx = (uint32_t)ux, ly = (uint32_t)uy;
+    const int32_t ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
+    if ((uint32_t)ix + (lx != 0) > 0x7ff00000u || (uint32_t)iy + (ly != 0) > 0x7ff00000u)
+        return x + y;                            // NaN
+    if (hx == 0x3ff00000 && lx == 0) return orbx_atan_f64(y);   // x = 1.0
+    const int m = ((hy >> 31) & 1) | ((hx >> 30) & 2);          // 2 * sign(x) + sign(y)
+    if ((iy | ly) == 0) {                        // y = 0
+        if (m < 2) return y;
+        return m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if ((ix | lx) == 0) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;   // x = 0
+    if (ix == 0x7ff00000) {                      // x infinite
+        if (iy == 0x7ff00000)
+            return m == 0 ? pi_o_4 + tiny : m == 1 ? -pi_o_4 - tiny
+                 : m == 2 ? 3.0 * pi_o_4 + tiny : -3.0 * pi_o_4 - tiny;
+        return m == 0 ? 0.0 : m == 1 ? -0.0 : m == 2 ? pi + tiny : -pi - tiny;
+    }
+    if (iy == 0x7ff00000) return hy < 0 ? -pi_o_2 - tiny : pi_o_2 + tiny;
+    const int32_t k = (iy - ix) >> 20;
+    double z;
+    if (k > 60) z = pi_o_2 + 0.5 * pi_lo;        // |y / x| > 2^60
+    else if (hx < 0 && k < -60) z = 0.0;         // |y| / x < -2^60
+    else z = orbx_atan_f64(fabs(orbx_div_f64(y, x)));
+    switch (m) {
+        case 0: return z;
+        case 1: return -z;
+        case 2: return pi - (z - pi_lo);
+        default: return (z - pi_lo) - pi;
+    }
 }
 
 }  // namespace orbx

@@ -418,6 +418,28 @@ class ORBmatcher:
                                               ratio_factor, job_off, d_match, d_status, d_x3d,
                                               d_nnew, d_keys_raw, mb, stream)
 
+    # ---- Sim3Solver::iterate for many solvers (Sim3Solver.cc:140-207) ------------------------
+    def sim3_iterate_batch_device(self, d_jobs, njobs: int, max_n: int, max_call_its: int,
+                                  d_poses, d_corr, d_triples, d_state, d_results, d_inliers,
+                                  stream=0):
+        """orbx_sim3_iterate_batch_device: one iterate() call of every job (device tensors of
+        bytes or of the records' words: SIM3_JOB_DTYPE jobs, FRAME_POSE_DTYPE poses,
+        SIM3_CORR_DTYPE correspondences, int32 triples [n, 3], SIM3_STATE_DTYPE states in / out,
+        SIM3_RESULT_DTYPE results and the inlier bytes out).  The arrays' lengths are taken from
+        the tensors; a job that points outside them is refused in its info word."""
+        from .features import FRAME_POSE_DTYPE
+        from .sim3 import SIM3_CORR_DTYPE
+
+        def nbytes(t):
+            return 0 if t is None else int(t.numel() * t.element_size())
+        check("orbx_sim3_iterate_batch_device",
+              self._lib.orbx_sim3_iterate_batch_device(
+                  self._h, ptr(d_jobs), int(njobs), int(max_n), int(max_call_its), ptr(d_poses),
+                  nbytes(d_poses) // FRAME_POSE_DTYPE.itemsize, ptr(d_corr),
+                  nbytes(d_corr) // SIM3_CORR_DTYPE.itemsize, ptr(d_triples),
+                  nbytes(d_triples) // 12, ptr(d_state), ptr(d_results), ptr(d_inliers),
+                  nbytes(d_inliers), ctypes.c_void_p(stream)))
+
     def search_by_projection_batch_device(self, mode: int, frames: "DeviceFrameBatch", d_qdesc,
                                           d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
                                           inv_sigma2=None, orb_dist: int = 0, stream=0):
