@@ -472,8 +472,9 @@ int32_t orbx_matcher_variant(int32_t kind, int32_t n_a, int32_t n_b, int32_t nq)
  * between SearchByBoW(KF, KF) and SearchBySim3.  What stays with the caller: the object tests of
  * the constructor (isBad, GetIndexInKeyFrame, :64-79), the rand() stream (the library never calls
  * rand(): orbx_sim3_sample_triples turns the caller's raw rand() values into the minimal sets of
- * :163-177), and OptimizeSim3.  The arithmetic is the reference's statement by statement; the
- * forms evaluated inside OpenCV 3.2 are restated and PARITY UNPINNED. */
+ * :163-177).  OptimizeSim3 is orbx_sim3_optimize* below.  The arithmetic is the reference's
+ * statement by statement; the forms evaluated inside OpenCV 3.2 are restated and PARITY UNPINNED
+ * (DESIGN.md §2). */
 
 /* One kept correspondence (:81-100): i1 = the slot in vpMatched12, the two world positions
  * (pMP1 / pMP2 ->GetWorldPos()) and the octaves of the two undistorted keypoints. */
@@ -573,6 +574,109 @@ orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pos
                               const orbx_sim3_job* job, const orbx_sim3_corr* corr,
                               const int32_t* triples, orbx_sim3_state* state,
                               orbx_sim3_result* res, uint8_t* inliers, int device);
+
+/* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1070-1265; LoopClosing.cc:376) ---------------
+ * The refinement of the solver's Sim3 over the matches SearchBySim3 added: one VertexSim3Expmap,
+ * an EdgeSim3ProjectXYZ and an EdgeInverseSim3ProjectXYZ per correspondence with numerically
+ * differentiated Jacobians and Huber kernels, Levenberg over the dense 7x7 solver: optimize(5),
+ * the chi2 > th2 classification, optimize(10 or 5).  k_sim3_opt restates g2o decision for
+ * decision (csrc/orbx_sim3opt.hip); the forms evaluated inside Eigen are restated from the
+ * published algorithms [unverified-Eigen].  What stays with the caller: the
+ * object tests that decide the correspondence list (isBad, GetIndexInKeyFrame >= 0, both
+ * MapPoints present), gScm * gSmw, and the nInliers >= 20 decision. */
+
+/* One kept correspondence (:1123-1202), in increasing i1: i1 = the slot in vpMatches1, the two
+ * world positions, the undistorted keypoints mvKeysUn[i1].pt of KF1 and mvKeysUn[i2].pt of KF2,
+ * and their octaves. */
+typedef struct {
+    int32_t i1;
+    float X1w[3];
+    float X2w[3];
+    float kp1[2];
+    float kp2[2];
+    int32_t octave1, octave2;
+} orbx_sim3opt_corr;
+
+/* One call.  kf1 / kf2 index the pose array (read: Rcw, tcw, fx, fy, cx, cy); sigma2_1 / _2 are
+ * the keyframes' mvLevelSigma2 (the information is 1.0f / sigma2[octave]) with nlevels1 / nlevels2
+ * entries in [1, 16].  The N correspondences are corr[corr_off .. corr_off + N); the keep bytes
+ * (vpMatches1 after the call) are keep[flag_off .. flag_off + mN1).  th2 is the reference's th2
+ * (10 at its call site), fix_scale its bFixScale. */
+typedef struct {
+    int32_t kf1, kf2;
+    float sigma2_1[16], sigma2_2[16];
+    int32_t nlevels1, nlevels2;
+    int32_t mN1, N, corr_off, flag_off;
+    float th2;
+    int32_t fix_scale;
+} orbx_sim3opt_job;
+
+/* The Sim3 a call starts from: the solver's mBestRotation, mBestTranslation and mBestScale, i.e.
+ * g2o::Sim3(toMatrix3d(R12), toVector3d(t12), s12).  These are the fields R12 .. s12 of
+ * orbx_sim3_result in its order, so a batch call may point d_sim3_in at &d_results[0].R12 of
+ * orbx_sim3_iterate_batch_device with sim3_in_stride = sizeof(orbx_sim3_result). */
+typedef struct {
+    float R12[9], t12[3], s12;
+} orbx_sim3opt_in;
+
+/* info: bits 0-2 optimize() calls that ran (0-2), bits 3-9 Levenberg iterations (<= 15), bits
+ * 10-18 trials (<= 150), then the flags. */
+#define ORBX_SIM3OPT_ROUNDS_MASK 0x7u
+#define ORBX_SIM3OPT_ITERS_SHIFT 3
+#define ORBX_SIM3OPT_ITERS_MASK 0x7fu
+#define ORBX_SIM3OPT_TRIALS_SHIFT 10
+#define ORBX_SIM3OPT_TRIALS_MASK 0x1ffu
+#define ORBX_SIM3OPT_REFUSED_OCTAVE (1u << 23)  /* an octave outside [0, nlevels), or nlevels outside [1, 16] */
+#define ORBX_SIM3OPT_REFUSED_I1 (1u << 24)      /* an i1 outside [0, mN1), or not increasing                 */
+#define ORBX_SIM3OPT_REFUSED_LIMIT (1u << 25)   /* N above max_n or negative, mN1 negative                    */
+#define ORBX_SIM3OPT_REFUSED_RANGE (1u << 26)   /* kf1 / kf2 or an offset outside the arrays of the call      */
+#define ORBX_SIM3OPT_REFUSED_ANY (0xfu << 23)
+#define ORBX_SIM3OPT_THETA_LIMIT (1u << 27)     /* an update's |omega| outside orbx_sincos_f64: that trial failed */
+#define ORBX_SIM3OPT_EXP_LIMIT (1u << 28)       /* an update's sigma outside orbx_exp_f64: that trial failed  */
+#define ORBX_SIM3OPT_NONPOSITIVE_SOLVE (1u << 29) /* LDLT::isPositive() was false in some trial              */
+#define ORBX_SIM3OPT_FEW_INLIERS (1u << 30)     /* nCorrespondences - nBad < 10: returned 0, Sim3 unchanged   */
+#define ORBX_SIM3OPT_DROPPED (1u << 31)         /* nBad > 0 after the first stage (nMoreIterations = 10)      */
+
+/* What one call gives.  n_inliers is the reference's return value; n_bad the pairs dropped after
+ * the first stage.  q (x, y, z, w; not normalised, as g2o keeps it), t and s are g2oS12 after the
+ * call; T12 is Converter::toCvMat(g2oS12) (s * R, t, rounded to float; row-major 4x4).  When the
+ * call returns 0 early (FEW_INLIERS) and for a refused job, n_inliers = 0 and q, t, s, T12 are
+ * the input Sim3; a refused job's keep bytes are not touched. */
+typedef struct {
+    int32_t n_inliers, n_correspondences, n_bad;
+    uint32_t info;
+    double q[4], t[3], s;
+    float T12[16];
+} orbx_sim3opt_result;
+
+/* The largest N and the most jobs a call takes (host only).  NULL outputs are skipped. */
+orbx_status orbx_sim3opt_limits(int32_t* max_n, int32_t* max_jobs);
+
+/* OptimizeSim3 of njobs candidates at once, every array on the device, on `stream` with no host
+ * step and no scratch: k_sim3_opt, one wave per job.  max_n >= every job's N; nposes, ncorr and
+ * nkeep_bytes are the lengths of the arrays, and a job that points outside them is refused in its
+ * info word.  Job j starts from the record at (const char*)d_sim3_in + j * sim3_in_stride
+ * (sim3_in_stride >= sizeof(orbx_sim3opt_in), a multiple of 4).  d_keep: entry i1 becomes 0 when
+ * the pair is dropped in either classification; entries that name no correspondence, and kept
+ * pairs, are not written.
+ * ORBX_ERR_INVALID: m NULL, a NULL array with njobs > 0, a negative count, a bad stride.  max_n or
+ * njobs above orbx_sim3opt_limits: ORBX_ERR_UNSUPPORTED.  njobs == 0: ORBX_OK, nothing touched. */
+orbx_status orbx_sim3_optimize_batch_device(
+    orbx_matcher* m, const orbx_sim3opt_job* d_jobs, int32_t njobs, int32_t max_n,
+    const orbx_frame_pose* d_poses, int32_t nposes, const orbx_sim3opt_corr* d_corr, int64_t ncorr,
+    const void* d_sim3_in, int64_t sim3_in_stride, orbx_sim3opt_result* d_results,
+    uint8_t* d_keep, int64_t nkeep_bytes, void* stream);
+
+/* One call from host arrays (copied to the device for the call).  job->kf1, kf2 and the two
+ * offsets are ignored: corr holds job->N records, keep job->mN1 bytes (in / out).
+ * ORBX_ERR_INVALID: a NULL argument, N or mN1 negative; N above orbx_sim3opt_limits:
+ * ORBX_ERR_UNSUPPORTED; the checks run before the device is touched, and without a GPU the call
+ * returns ORBX_ERR_DEVICE.  What the batched form refuses per job comes back the same way, in
+ * res->info.  Calls are serialised inside the library. */
+orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_pose* pose2,
+                               const orbx_sim3opt_job* job, const orbx_sim3opt_corr* corr,
+                               const orbx_sim3opt_in* sim3_in, orbx_sim3opt_result* res,
+                               uint8_t* keep, int device);
 
 /* ---- per-kernel timing for the matcher handle ------------------------------------------ */
 typedef enum {

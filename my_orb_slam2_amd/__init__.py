@@ -11,6 +11,8 @@ Host-side mirror of the reference's operator interface for this path:
   pose-only fit of a frame to its MapPoints (src/Optimizer.cc:245-457)
 * ``Sim3Solver`` / ``ORBmatcher.sim3_iterate_batch_device`` — Horn's closed form inside the
   reference's RANSAC loop for loop-closure candidates (src/Sim3Solver.cc)
+* ``OptimizeSim3`` / ``ORBmatcher.sim3_optimize_batch_device`` — Optimizer::OptimizeSim3, the
+  refinement of the candidate's Sim3 over its matches (src/Optimizer.cc:1070-1265)
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
@@ -33,8 +35,8 @@ from .tracking import MonoTrackBatch, RGBDTrackBatch
 from .features import (PROJ_JOB_DTYPE, PROJ_SIM3, matches_to_features_batch_device,
                        pose_optimization, pose_optimization_batch_device, proj_job,
                        project_map_points, project_map_points_batch_device)
-from .sim3 import (Sim3Solver, sim3_iterate, sim3_job, sim3_limits, sim3_ransac_iterations,
-                   sim3_sample_triples)
+from .sim3 import (OptimizeSim3, Sim3Solver, sim3_iterate, sim3_job, sim3_limits, sim3_optimize,
+                   sim3_ransac_iterations, sim3_sample_triples, sim3opt_job, sim3opt_limits)
 from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
                       load_stereo_settings, remap_fixed_point, remap_stereo_batch_device)
 
@@ -47,4 +49,5 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "project_map_points_batch_device", "TRI_CODES", "parallax_stereo_cos",
            "triangulate_matches", "pose_optimization", "pose_optimization_batch_device",
            "matches_to_features_batch_device", "Sim3Solver", "sim3_iterate", "sim3_job",
-           "sim3_limits", "sim3_ransac_iterations", "sim3_sample_triples"]
+           "sim3_limits", "sim3_ransac_iterations", "sim3_sample_triples", "OptimizeSim3",
+           "sim3_optimize", "sim3opt_job", "sim3opt_limits"]

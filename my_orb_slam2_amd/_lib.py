@@ -159,6 +159,10 @@ SIGNATURES = {
                                             _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
                                             _vp]),
     "orbx_sim3_iterate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orbx_sim3opt_limits": (_i, [_vp, _vp]),
+    "orbx_sim3_optimize_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, ctypes.c_int64, _vp,
+                                             ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp]),
+    "orbx_sim3_optimize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     # include/orbx_vocab.h
     "orbx_vocabulary_load_text": (_i, [ctypes.c_char_p, _i, ctypes.POINTER(_vp)]),
     "orbx_vocabulary_destroy": (_i, [_vp]),

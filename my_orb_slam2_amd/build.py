@@ -24,7 +24,7 @@ LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
            "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
-           "orbx_poseopt.hip", "orbx_sim3.hip"]
+           "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_kernels.h", "orbx_host.h",
            "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
            "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
@@ -357,3 +357,34 @@ def build_sim3_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
     subprocess.run(cmd, check=True)
     os.replace(str(SIM3_REF_BIN) + ".tmp", SIM3_REF_BIN)
     return SIM3_REF_BIN
+
+
+# ---- OptimizeSim3 restated in plain C++ doubles (tests/native/sim3opt_ref.cpp) --------------------
+SIM3OPT_REF_SRC = PKG.parent / "tests" / "native" / "sim3opt_ref.cpp"
+SIM3OPT_REF_BIN = PKG.parent / "tests" / "native" / "sim3opt_ref"
+
+
+def build_sim3opt_ref(force: bool = False, verbose: bool = False, sanitize: bool = False,
+                      out: pathlib.Path | None = None) -> pathlib.Path:
+    """g++ on the record layouts of include/ and csrc/orbx_math.h (orbx_sincos_f64, orbx_exp_f64)
+    only: no liborbx and no GPU (the CPU reference of orbx_sim3_optimize*).  sanitize: the
+    stand-alone program with -fsanitize=address,undefined, to `out`."""
+    root = PKG.parent
+    target = pathlib.Path(out) if out else SIM3OPT_REF_BIN
+    if sanitize and target.resolve() == SIM3OPT_REF_BIN.resolve():
+        raise ValueError("the sanitized program goes to a path of its own")
+    deps = [SIM3OPT_REF_SRC, CSRC / "orbx_math.h"] + sorted((root / "include").glob("*.h"))
+    newest = max(p.stat().st_mtime for p in deps)
+    if not force and target.exists() and target.stat().st_mtime >= newest:
+        return target
+    # -ffp-contract=off: every operation rounded on its own, as in the kernel
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), "-I" + str(CSRC), str(SIM3OPT_REF_SRC)]
+    if sanitize:
+        cmd += ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    cmd += ["-o", str(target) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(target) + ".tmp", target)
+    return target

@@ -96,6 +96,24 @@ constexpr size_t SIM3_MAX_SCRATCH = (size_t)1 << 30;
 size_t sim3_scratch_bytes(int njobs, int max_n, int max_call);
 hipError_t launch_sim3(const Sim3Launch& a, hipStream_t st);
 
+// Optimizer::OptimizeSim3 over njobs candidates (orbx_sim3opt.hip): one wave per job, no scratch.
+// The array lengths bound what a job may point at.
+struct Sim3OptLaunch {
+    const orbx_sim3opt_job* jobs;
+    int njobs, max_n;
+    const orbx_frame_pose* poses;
+    int nposes;
+    const orbx_sim3opt_corr* corr;
+    long long ncorr;
+    const uint8_t* sim3_in;
+    long long in_stride;
+    orbx_sim3opt_result* res;
+    uint8_t* keep;
+    long long nkeep;
+};
+constexpr int SIM3OPT_MAX_N = 4096, SIM3OPT_MAX_JOBS = 65535;
+hipError_t launch_sim3_opt(const Sim3OptLaunch& a, hipStream_t st);
+
 // Projection searches (modes of orbx_proj_mode plus PROJ_INIT) over njobs independent jobs
 // (frames).  With t_off == nullptr there is one job: target T, queries [0, nq).  Otherwise
 // job j's target is T's arrays offset by t_off[j] features (keys/desc/u_right/claimed) and

@@ -291,6 +291,60 @@ ORBX_HD bool orbx_sincos_f64(double x, double* s, double* c) {
     return true;
 }
 
+// exp of a double for the Sim3 refinement (Sim3(update), sim3.h:84: s = std::exp(sigma)).  As with
+// orbx_sincos_f64 the kernel, the C++ reference and the numpy restatement share this routine: the
+// fdlibm algorithm (e_exp.c: x = k ln2 + r with ln2 in two parts, the rational form of
+// exp(r) on |r| <= 0.5 ln2, the scaling by 2^k on the exponent field), every operation rounded on
+// its own.  exp(0) = 1 exactly (|x| < 2^-28 returns 1 + x).  Valid for |x| <= ORBX_EXP_F64_LIMIT
+// (700: the result is a normal double); outside it, and for a NaN, returns false and leaves *e
+// untouched.  Below 1 ulp from the true value.
+#define ORBX_EXP_F64_LIMIT 700.0
+
+ORBX_HD double orbx_div_f64(double a, double b);   // below: an IEEE division on host and device
+
+ORBX_HD bool orbx_exp_f64(double x, double* e) {
+    if (!(fabs(x) <= ORBX_EXP_F64_LIMIT)) return false;
+    const double ln2HI = 6.93147180369123816490e-01, ln2LO = 1.90821492927058770002e-10,
+                 invln2 = 1.44269504088896338700e+00;
+    const double P1 = 1.66666666666666019037e-01, P2 = -2.77777777770155933842e-03,
+                 P3 = 6.61375632143793436117e-05, P4 = -1.65339022054652515390e-06,
+                 P5 = 4.13813679705723846039e-08;
+    uint64_t u;
+    memcpy(&u, &x, 8);
+    const uint32_t hx = (uint32_t)(u >> 32) & 0x7fffffffu;
+    const bool neg = (u >> 63) != 0;
+    double hi = 0.0, lo = 0.0;
+    int k = 0;
+    if (hx > 0x3fd62e42u) {                      // |x| > 0.5 ln2
+        if (hx < 0x3ff0a2b2u) {                  // and |x| < 1.5 ln2
+            hi = neg ? x + ln2HI : x - ln2HI;
+            lo = neg ? -ln2LO : ln2LO;
+            k = neg ? -1 : 1;
+        } else {
+            k = (int)(invln2 * x + (neg ? -0.5 : 0.5));
+            const double t = (double)k;
+            hi = x - t * ln2HI;
+            lo = t * ln2LO;
+        }
+        x = hi - lo;
+    } else if (hx < 0x3e300000u) {               // |x| < 2^-28
+        *e = 1.0 + x;
+        return true;
+    }
+    const double t = x * x;
+    const double c = x - t * (P1 + t * (P2 + t * (P3 + t * (P4 + t * P5))));
+    if (k == 0) {
+        *e = 1.0 - (orbx_div_f64(x * c, c - 2.0) - x);
+        return true;
+    }
+    const double y = 1.0 - ((lo - orbx_div_f64(x * c, 2.0 - c)) - hi);
+    uint64_t v;
+    memcpy(&v, &y, 8);
+    v += (uint64_t)(int64_t)k << 52;             // |k| <= 1010 and y in [0.5, 2]: a normal double
+    memcpy(e, &v, 8);
+    return true;
+}
+
 // atan2 of two doubles for the Sim3 solver's rotation angle (Sim3Solver.cc:278).  As with
 // orbx_sincos_f64 the kernel, the C++ reference and the numpy restatement share this routine: the
 // fdlibm algorithm (e_atan2.c over s_atan.c: argument reduction to one of four intervals, an odd

@@ -440,6 +440,38 @@ class ORBmatcher:
                   nbytes(d_triples) // 12, ptr(d_state), ptr(d_results), ptr(d_inliers),
                   nbytes(d_inliers), ctypes.c_void_p(stream)))
 
+    # ---- Optimizer::OptimizeSim3 for many candidates (Optimizer.cc:1070-1265) -----------------
+    def sim3_optimize_batch_device(self, d_jobs, njobs: int, max_n: int, d_poses, d_corr,
+                                   d_sim3_in, d_results, d_keep, sim3_in_stride: int | None = None,
+                                   sim3_in_offset: int = 0, stream=0):
+        """orbx_sim3_optimize_batch_device: one OptimizeSim3 call of every job (device tensors of
+        bytes or of the records' words: SIM3OPT_JOB_DTYPE jobs, FRAME_POSE_DTYPE poses,
+        SIM3OPT_CORR_DTYPE correspondences, SIM3OPT_RESULT_DTYPE results out, the keep bytes in /
+        out).  d_sim3_in holds a SIM3OPT_IN_DTYPE record per job, sim3_in_stride bytes apart from
+        byte sim3_in_offset on: pass the result tensor of sim3_iterate_batch_device with
+        sim3_in_stride = SIM3_RESULT_DTYPE.itemsize and sim3_in_offset = SIM3_RESULT_IN_OFFSET to
+        start from the solver's models where they are.  The arrays' lengths are taken from the
+        tensors; a job that points outside them is refused in its info word."""
+        from .features import FRAME_POSE_DTYPE
+        from .sim3 import SIM3OPT_CORR_DTYPE, SIM3OPT_IN_DTYPE
+
+        def nbytes(t):
+            return 0 if t is None else int(t.numel() * t.element_size())
+        stride = SIM3OPT_IN_DTYPE.itemsize if sim3_in_stride is None else int(sim3_in_stride)
+        if njobs > 0 and d_sim3_in is not None and (
+                sim3_in_offset < 0 or stride < SIM3OPT_IN_DTYPE.itemsize or
+                sim3_in_offset + (njobs - 1) * stride + SIM3OPT_IN_DTYPE.itemsize > nbytes(d_sim3_in)):
+            raise ValueError("d_sim3_in is too short for njobs records of this stride and offset")
+        p_in = ptr(d_sim3_in)
+        if p_in is not None and sim3_in_offset:
+            p_in = ctypes.c_void_p((p_in.value or 0) + int(sim3_in_offset))
+        check("orbx_sim3_optimize_batch_device",
+              self._lib.orbx_sim3_optimize_batch_device(
+                  self._h, ptr(d_jobs), int(njobs), int(max_n), ptr(d_poses),
+                  nbytes(d_poses) // FRAME_POSE_DTYPE.itemsize, ptr(d_corr),
+                  nbytes(d_corr) // SIM3OPT_CORR_DTYPE.itemsize, p_in, stride, ptr(d_results),
+                  ptr(d_keep), nbytes(d_keep), ctypes.c_void_p(stream)))
+
     def search_by_projection_batch_device(self, mode: int, frames: "DeviceFrameBatch", d_qdesc,
                                           d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
                                           inv_sigma2=None, orb_dist: int = 0, stream=0):

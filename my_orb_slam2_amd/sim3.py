@@ -3,8 +3,10 @@
 ``Sim3Solver`` takes host arrays and follows the reference's names (SetRansacParameters, iterate,
 find, GetEstimatedRotation / Translation / Scale); ``ORBmatcher.sim3_iterate_batch_device`` runs
 many solvers from device arrays on the matcher's stream.  The caller keeps the object tests of the
-reference's constructor (isBad, GetIndexInKeyFrame), the rand() stream (pass the raw values to
-``sim3_sample_triples``) and OptimizeSim3.
+reference's constructor (isBad, GetIndexInKeyFrame) and the rand() stream (pass the raw values to
+``sim3_sample_triples``).  ``OptimizeSim3`` / ``sim3_optimize`` (Optimizer::OptimizeSim3) refine
+the solver's model over the matches; ``ORBmatcher.sim3_optimize_batch_device`` does so for many
+candidates from device arrays, reading the solver's result records in place.
 """
 from __future__ import annotations
 
@@ -167,3 +169,93 @@ class Sim3Solver:
 
     def GetEstimatedScale(self) -> float:
         return float(self._need_best()["s12"])
+
+
+# ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1070-1265): include/orbx_match.h, orbx_sim3_optimize* ----
+
+SIM3OPT_CORR_DTYPE = np.dtype([("i1", "<i4"), ("X1w", "<f4", 3), ("X2w", "<f4", 3),
+                               ("kp1", "<f4", 2), ("kp2", "<f4", 2), ("octave1", "<i4"),
+                               ("octave2", "<i4")])
+SIM3OPT_JOB_DTYPE = np.dtype([("kf1", "<i4"), ("kf2", "<i4"), ("sigma2_1", "<f4", 16),
+                              ("sigma2_2", "<f4", 16), ("nlevels1", "<i4"), ("nlevels2", "<i4"),
+                              ("mN1", "<i4"), ("N", "<i4"), ("corr_off", "<i4"),
+                              ("flag_off", "<i4"), ("th2", "<f4"), ("fix_scale", "<i4")])
+SIM3OPT_IN_DTYPE = np.dtype([("R12", "<f4", 9), ("t12", "<f4", 3), ("s12", "<f4")])
+SIM3OPT_RESULT_DTYPE = np.dtype([("n_inliers", "<i4"), ("n_correspondences", "<i4"),
+                                 ("n_bad", "<i4"), ("info", "<u4"), ("q", "<f8", 4),
+                                 ("t", "<f8", 3), ("s", "<f8"), ("T12", "<f4", 16)])
+# where an orbx_sim3_result holds an orbx_sim3opt_in (R12, t12, s12)
+SIM3_RESULT_IN_OFFSET = SIM3_RESULT_DTYPE.fields["R12"][1]
+
+SIM3OPT_REFUSED_OCTAVE = 1 << 23
+SIM3OPT_REFUSED_I1 = 1 << 24
+SIM3OPT_REFUSED_LIMIT = 1 << 25
+SIM3OPT_REFUSED_RANGE = 1 << 26
+SIM3OPT_REFUSED_ANY = 0xf << 23
+SIM3OPT_THETA_LIMIT = 1 << 27
+SIM3OPT_EXP_LIMIT = 1 << 28
+SIM3OPT_NONPOSITIVE_SOLVE = 1 << 29
+SIM3OPT_FEW_INLIERS = 1 << 30
+SIM3OPT_DROPPED = 1 << 31
+
+
+def sim3opt_limits() -> dict:
+    """The largest N and the most jobs a call of sim3_optimize* takes."""
+    a, b = ctypes.c_int32(), ctypes.c_int32()
+    check("orbx_sim3opt_limits", load().orbx_sim3opt_limits(ctypes.byref(a), ctypes.byref(b)))
+    return dict(max_n=a.value, max_jobs=b.value)
+
+
+def sim3opt_job(sigma2_1, sigma2_2, mN1: int, N: int, th2: float = 10.0, fix_scale: bool = False,
+                kf1: int = 0, kf2: int = 1, corr_off: int = 0, flag_off: int = 0) -> np.ndarray:
+    """One orbx_sim3opt_job record."""
+    j = np.zeros((), SIM3OPT_JOB_DTYPE)
+    s1, s2 = np.asarray(sigma2_1, np.float32), np.asarray(sigma2_2, np.float32)
+    j["nlevels1"], j["nlevels2"] = len(s1), len(s2)
+    j["sigma2_1"][:min(len(s1), 16)] = s1[:16]
+    j["sigma2_2"][:min(len(s2), 16)] = s2[:16]
+    j["kf1"], j["kf2"], j["mN1"], j["N"] = kf1, kf2, mN1, N
+    j["corr_off"], j["flag_off"] = corr_off, flag_off
+    j["th2"], j["fix_scale"] = th2, int(bool(fix_scale))
+    return j
+
+
+def sim3_optimize(pose1, pose2, job, corr, sim3_in, keep=None, device: int = 0):
+    """orbx_sim3_optimize: one OptimizeSim3 call from host arrays.  `sim3_in`: a SIM3OPT_IN_DTYPE
+    record (the solver's R12, t12, s12); `keep`: mN1 bytes (vpMatches1 != NULL going in; ones when
+    omitted), returned with the dropped pairs' entries zeroed.  Returns (result, keep)."""
+    p1 = np.ascontiguousarray(pose1, FRAME_POSE_DTYPE).reshape(())
+    p2 = np.ascontiguousarray(pose2, FRAME_POSE_DTYPE).reshape(())
+    jb = np.ascontiguousarray(job, SIM3OPT_JOB_DTYPE).reshape(())
+    c = np.ascontiguousarray(corr, SIM3OPT_CORR_DTYPE)
+    s = np.ascontiguousarray(sim3_in, SIM3OPT_IN_DTYPE).reshape(())
+    if c.size != int(jb["N"]):
+        raise ValueError("corr holds N records")
+    mN1 = int(jb["mN1"])
+    k = np.ones(max(mN1, 0), np.uint8) if keep is None else np.array(keep, np.uint8)
+    if k.size != max(mN1, 0):
+        raise ValueError("keep: mN1 bytes")
+    res = np.zeros((), SIM3OPT_RESULT_DTYPE)
+    check("orbx_sim3_optimize", load().orbx_sim3_optimize(ptr(p1), ptr(p2), ptr(jb), ptr(c), ptr(s),
+                                                          ptr(res), ptr(k), device))
+    return res, k
+
+
+def OptimizeSim3(pose1, pose2, corr, sigma2_1, sigma2_2, mN1: int, R12, t12, s12: float,
+                 th2: float = 10.0, bFixScale: bool = False, keep=None, device: int = 0):
+    """Optimizer::OptimizeSim3 by the reference's name over host arrays.  corr: SIM3OPT_CORR_DTYPE,
+    the correspondences the reference's loop keeps, in increasing i1; R12, t12, s12: the solver's
+    model (g2oS12 going in).  Returns (nInliers, S12, keep): S12 = dict(q (x, y, z, w), t, s, T12
+    (4x4 float32, Converter::toCvMat(g2oS12))) and keep = vpMatches1 != NULL after the call."""
+    c = np.ascontiguousarray(corr, SIM3OPT_CORR_DTYPE)
+    s_in = np.zeros((), SIM3OPT_IN_DTYPE)
+    s_in["R12"] = np.asarray(R12, np.float32).reshape(9)
+    s_in["t12"] = np.asarray(t12, np.float32).reshape(3)
+    s_in["s12"] = s12
+    job = sim3opt_job(sigma2_1, sigma2_2, int(mN1), int(c.size), th2, bFixScale)
+    res, k = sim3_optimize(pose1, pose2, job, c, s_in, keep, device)
+    if int(res["info"]) & SIM3OPT_REFUSED_ANY:
+        raise ValueError(f"OptimizeSim3: the job was refused, info = {int(res['info']):#x}")
+    S12 = dict(q=res["q"].copy(), t=res["t"].copy(), s=float(res["s"]),
+               T12=res["T12"].reshape(4, 4).copy(), info=int(res["info"]))
+    return int(res["n_inliers"]), S12, k
