@@ -395,6 +395,36 @@ orbx_status orbx_remap(const orbx_rectifier* r, const uint8_t* src, size_t src_s
 /* Images a lane of the remap kernel handles with one read of its map entries. */
 int32_t orbx_remap_images_per_chunk(void);
 
+/* ---- PnPsolver's neighbours in Tracking::Relocalization (orbx_match.h, orbx_pnp_*) ---------- */
+
+/* The solvers' correspondences from the matches of orbx_search_by_bow_kf_frame_batch_device, one
+ * workgroup per job, an ordered compaction: for every frame feature i < n_feat (ascending) with
+ * m = d_match[j * match_stride + i] >= 0, the record {i, d_mps[d_mp_off[j] + m].pos, d_kp[i].x,
+ * d_kp[i].y, d_kp[i].octave} is appended to d_corr[j * corr_stride ..], and d_N[j] receives their
+ * number.  A match outside job j's block [0, d_mp_off[j + 1] - d_mp_off[j]) is dropped and sets
+ * bit 0 of d_N_flags[j] when d_N_flags is not NULL.  n_feat <= corr_stride.
+ * ORBX_ERR_INVALID: m NULL, a NULL array with njobs > 0, a negative count, n_feat above a stride.
+ * njobs == 0: ORBX_OK, nothing touched. */
+orbx_status orbx_pnp_correspondences_batch_device(
+    orbx_matcher* m, int32_t njobs, const int32_t* d_match, int64_t match_stride,
+    const orbx_keypoint* d_kp, int32_t n_feat, const orbx_map_point* d_mps,
+    const int32_t* d_mp_off, orbx_pnp_corr* d_corr, int64_t corr_stride, int32_t* d_N,
+    int32_t* d_N_flags, void* stream);
+
+/* Tracking.cc:1546-1562 for njobs candidates: for a found job j (d_results[j].found),
+ * d_poses[j] = *d_template with Rcw / tcw from Tcw and Ow = -Rcw.t() * tcw in PoseOptimization's
+ * form, and d_mp_of_feat[j * feat_stride + i] = inlier[i] ? d_match[j * match_stride + i] : -1
+ * for i < n_feat with inlier = d_inliers[d_jobs[j].inlier_off ..]; otherwise d_poses[j] =
+ * *d_template and every entry is -1.  A job whose inlier block lies outside [0, ninlier_bytes) or
+ * whose n_matches differs from n_feat is treated as not found.
+ * ORBX_ERR_INVALID: m NULL, a NULL array with njobs > 0, a negative count, n_feat above a stride.
+ * njobs == 0: ORBX_OK, nothing touched. */
+orbx_status orbx_pnp_apply_batch_device(
+    orbx_matcher* m, int32_t njobs, const orbx_pnp_job* d_jobs, const orbx_pnp_result* d_results,
+    const uint8_t* d_inliers, int64_t ninlier_bytes, const int32_t* d_match, int64_t match_stride,
+    int32_t n_feat, const orbx_frame_pose* d_template, orbx_frame_pose* d_poses,
+    int32_t* d_mp_of_feat, int64_t feat_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

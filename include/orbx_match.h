@@ -678,6 +678,143 @@ orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_po
                                const orbx_sim3opt_in* sim3_in, orbx_sim3opt_result* res,
                                uint8_t* keep, int device);
 
+/* ---- PnPsolver (src/PnPsolver.cc; Tracking::Relocalization, Tracking.cc:1444-1635) ----------
+ * EPnP inside the reference's RANSAC loop, between SearchByBoW(KF, Frame) and PoseOptimization:
+ * four sampled correspondences per iteration (compute_pose, :477-525), CheckInliers over all of
+ * them (:308-339), Refine over the best inlier set (:260-305).  What stays with the caller: the
+ * object tests of the constructor (isBad, :79-101; orbx_pnp_correspondences_batch_device keeps
+ * every matched slot), the rand() stream (the library never calls rand(): orbx_pnp_sample_quads
+ * turns the caller's raw rand() values into the minimal sets of :188-201), and every decision
+ * between the calls (nmatches < 15, nGood < 10, < 50, ...).  The arithmetic is the reference's
+ * statement by statement in its own types; the forms evaluated inside OpenCV 3.2
+ * (cvMulTransposed, cvSVD, cvInvert, cvSolve, convertTo) are restated and PARITY UNPINNED
+ * (DESIGN.md §2). */
+
+/* One kept correspondence (:79-101), in increasing i: i = the slot in vpMapPointMatches
+ * (mvKeyPointIndices), the MapPoint's world position, the undistorted keypoint mvKeysUn[i].pt
+ * and its octave. */
+typedef struct {
+    int32_t i;
+    float X[3];
+    float u, v;
+    int32_t octave;
+} orbx_pnp_corr;
+
+/* One solver.  sigma2 is the frame's mvLevelSigma2 with nlevels entries in [1, 16]; th2 the th2 of
+ * SetRansacParameters (mvMaxError[i] = sigma2[octave] * th2, a float product).  The N
+ * correspondences are corr[corr_off .. corr_off + N); the inlier bytes are inliers[inlier_off ..
+ * inlier_off + n_matches); the best inlier bytes are best[best_off .. best_off + N); the minimal
+ * set of iteration k (0-based, counted from the solver's construction on) is
+ * quads[4 * (quad_off + k) ..].  min_inliers (>= 1) and max_its are mRansacMinInliers and
+ * mRansacMaxIts as orbx_pnp_ransac_parameters gives them; n_iterations is the argument of
+ * iterate().  A call runs the iterations [state.iterations, state.iterations + window) with
+ * window = max(max_its - state.iterations, n_iterations, 0) (`||` at :182) unless it returns
+ * early. */
+typedef struct {
+    float fx, fy, cx, cy;
+    float sigma2[16];
+    int32_t nlevels;
+    float th2;
+    int32_t n_matches, N, corr_off, inlier_off, quad_off, best_off;
+    int32_t min_inliers, max_its, n_iterations;
+} orbx_pnp_job;
+
+/* mnIterations, mnBestInliers and mBestTcw (row-major), kept across calls of iterate() (in /
+ * out) together with the job's best inlier bytes (mvbBestInliers): a later call may Refine on a
+ * set an earlier call found.  When best_inliers > 0 the best bytes hold exactly best_inliers
+ * non-zero entries (anything else is refused). */
+typedef struct {
+    int32_t iterations, best_inliers;
+    float best_Tcw[16];
+} orbx_pnp_state;
+
+#define ORBX_PNP_REFINES_MASK 0xffffu        /* Refine() calls of this iterate()                           */
+#define ORBX_PNP_REFUSED_OCTAVE (1u << 24)  /* an octave outside [0, nlevels), or nlevels outside [1, 16] */
+#define ORBX_PNP_REFUSED_QUAD (1u << 25)    /* a minimal-set index outside [0, N) or repeated             */
+#define ORBX_PNP_REFUSED_I (1u << 26)       /* an i outside [0, n_matches), or not increasing             */
+#define ORBX_PNP_REFUSED_LIMIT (1u << 27)   /* N above max_n, the call's window above max_call_its,
+                                               max_its outside [1, limit], min_inliers < 1, a negative
+                                               count, a state that contradicts its best bytes          */
+#define ORBX_PNP_REFUSED_RANGE (1u << 28)   /* an offset outside the arrays of the call                   */
+#define ORBX_PNP_REFUSED_ANY (0x1fu << 24)
+#define ORBX_PNP_QR_SINGULAR (1u << 29)     /* qr_solve left through its singular exit (:887-890)         */
+#define ORBX_PNP_SVD_COMPLETED (1u << 30)   /* a singular vector came from cv::SVD's completion path      */
+
+/* What one iterate() call gives.  found: a pose was returned, source 1 = mRefinedTcw (:235) at
+ * the 1-based iteration `iteration`, source 2 = mBestTcw when the loop ended (:253, iteration =
+ * mnIterations); n_inliers and Tcw (row-major 4x4) are that pose's, and all n_matches inlier bytes
+ * of the job are written (vbInliers).  Not found: source, iteration, n_inliers and Tcw are 0 and
+ * the inlier bytes are not touched.  n_run: the iterations this call executed (the reference
+ * consumed 4 * n_run rand() values).  no_more: bNoMore.  best_inliers: mnBestInliers after the
+ * call.  info: the ORBX_PNP_REFUSED_* bits; a refused job gets found = 0 and info, and nothing
+ * else of its outputs, its state, its best bytes or its inlier bytes is touched.  Otherwise info
+ * holds the number of Refine() calls and the two diagnostics, over the iterations the call
+ * executed. */
+typedef struct {
+    int32_t found, source, iteration, n_run, n_inliers, no_more;
+    uint32_t info;
+    int32_t best_inliers;
+    float Tcw[16];
+} orbx_pnp_result;
+
+/* SetRansacParameters (:121-152) in its types, host only: nMinInliers = (int)(N * epsilon) through
+ * float, raised to min_inliers and to min_set; epsilon raised to (float)nMinInliers / N;
+ * nIterations = 1 when nMinInliers == N, else ceil(log(1 - prob) / log(1 - pow(epsilon, 3))) in
+ * double with the host's libm; both conversions to int as x86-64 does them (out of range or NaN:
+ * INT_MIN); *max_its_out = max(1, min(nIterations, max_its)).  N = 0 included.
+ * ORBX_ERR_INVALID: N < 0 or a NULL output; min_set != 4: ORBX_ERR_UNSUPPORTED. */
+orbx_status orbx_pnp_ransac_parameters(double prob, int32_t min_inliers, int32_t max_its,
+                                       int32_t min_set, float epsilon, int32_t N,
+                                       int32_t* min_inliers_out, int32_t* max_its_out);
+
+/* The minimal sets of n_its iterations (:188-201) from 4 * n_its raw rand() values in
+ * [0, RAND_MAX]: four draws without replacement by swap-with-last over 0 .. N-1, restarted every
+ * iteration, each draw DUtils::Random::RandomInt(0, size - 1) = int(((double)r / ((double)RAND_MAX
+ * + 1.0)) * size).  ORBX_ERR_INVALID: N < 4, n_its < 0, a NULL array with n_its > 0, a value
+ * outside [0, RAND_MAX]. */
+orbx_status orbx_pnp_sample_quads(int32_t N, int32_t n_its, const int32_t* rand_values,
+                                  int32_t* quads);
+
+/* The largest N (max_n), iterations per call (max_call_its, also the largest max_its) and jobs a
+ * call takes, and the scratch bytes a call may need at most (host only; the launcher evaluates
+ * the same expressions).  NULL outputs are skipped. */
+orbx_status orbx_pnp_limits(int32_t* max_n, int32_t* max_its, int32_t* max_jobs,
+                            int64_t* max_scratch_bytes);
+
+/* iterate(n_iterations) of njobs solvers at once, every array on the device, on `stream` with no
+ * host step: k_pnp_hypotheses (one wave per iteration of the call: EPnP on the four sampled
+ * points, then the inlier count and mask) and k_pnp_select (one wave per job: the iterations
+ * walked in order against the carried best, Refine where the reference runs it, the result, the
+ * inlier bytes, the state and the best bytes).  max_n >= every job's N and max_call_its >= every
+ * job's window size the grids and the matcher's scratch; ncorr, nquads (quads, i.e. 4 ints each),
+ * nbest_bytes and ninlier_bytes are the lengths of the arrays, and a job that points outside them
+ * is refused.  d_state and d_best are in / out, d_results and d_inliers out.
+ * ORBX_ERR_INVALID: m NULL, a NULL array with njobs > 0, a negative count.  max_n, max_call_its or
+ * njobs above orbx_pnp_limits, or their scratch above its bound: ORBX_ERR_UNSUPPORTED.
+ * njobs == 0: ORBX_OK, nothing touched.  Calls on one matcher share its scratch: one stream, or
+ * serialised. */
+orbx_status orbx_pnp_iterate_batch_device(
+    orbx_matcher* m, const orbx_pnp_job* d_jobs, int32_t njobs, int32_t max_n,
+    int32_t max_call_its, const orbx_pnp_corr* d_corr, int64_t ncorr, const int32_t* d_quads,
+    int64_t nquads, orbx_pnp_state* d_state, uint8_t* d_best, int64_t nbest_bytes,
+    orbx_pnp_result* d_results, uint8_t* d_inliers, int64_t ninlier_bytes, void* stream);
+
+/* One solver from host arrays (copied to the device for the call).  The four offsets of the job
+ * are ignored: corr holds job->N records, best job->N bytes (in / out), inliers job->n_matches
+ * bytes, quads 4 * (state->iterations + window) ints (the call reads the window's).
+ * ORBX_ERR_INVALID: a NULL argument, N, n_matches or state->iterations negative, max_its < 1; N,
+ * max_its or the window above orbx_pnp_limits: ORBX_ERR_UNSUPPORTED; the checks run before the
+ * device is touched, and without a GPU the call returns ORBX_ERR_DEVICE.  What the batched form
+ * refuses per job comes back the same way, in res->info.  Calls are serialised inside the
+ * library. */
+orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
+                             const int32_t* quads, orbx_pnp_state* state, uint8_t* best,
+                             orbx_pnp_result* res, uint8_t* inliers, int device);
+
+/* orbx_pnp_correspondences_batch_device and orbx_pnp_apply_batch_device, the two small kernels that
+ * tie the solver to the searches around it, are declared in orbx_frame.h next to the records
+ * they read and write. */
+
 /* ---- per-kernel timing for the matcher handle ------------------------------------------ */
 typedef enum {
     ORBX_MK_BOW = 0, ORBX_MK_TRIANGULATE, ORBX_MK_PROJ_SEARCH, ORBX_MK_PROJ_RESOLVE,

@@ -13,6 +13,9 @@ Host-side mirror of the reference's operator interface for this path:
   reference's RANSAC loop for loop-closure candidates (src/Sim3Solver.cc)
 * ``OptimizeSim3`` / ``ORBmatcher.sim3_optimize_batch_device`` — Optimizer::OptimizeSim3, the
   refinement of the candidate's Sim3 over its matches (src/Optimizer.cc:1070-1265)
+* ``PnPsolver`` / ``ORBmatcher.pnp_iterate_batch_device`` — EPnP inside the reference's RANSAC
+  loop for relocalisation candidates (src/PnPsolver.cc), with
+  ``pnp_correspondences_batch_device`` / ``pnp_apply_batch_device`` around it
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
@@ -35,6 +38,8 @@ from .tracking import MonoTrackBatch, RGBDTrackBatch
 from .features import (PROJ_JOB_DTYPE, PROJ_SIM3, matches_to_features_batch_device,
                        pose_optimization, pose_optimization_batch_device, proj_job,
                        project_map_points, project_map_points_batch_device)
+from .pnp import (PnPsolver, pnp_iterate, pnp_job, pnp_limits, pnp_ransac_parameters,
+                  pnp_sample_quads, pnp_window)
 from .sim3 import (OptimizeSim3, Sim3Solver, sim3_iterate, sim3_job, sim3_limits, sim3_optimize,
                    sim3_ransac_iterations, sim3_sample_triples, sim3opt_job, sim3opt_limits)
 from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
@@ -50,4 +55,5 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "triangulate_matches", "pose_optimization", "pose_optimization_batch_device",
            "matches_to_features_batch_device", "Sim3Solver", "sim3_iterate", "sim3_job",
            "sim3_limits", "sim3_ransac_iterations", "sim3_sample_triples", "OptimizeSim3",
-           "sim3_optimize", "sim3opt_job", "sim3opt_limits"]
+           "sim3_optimize", "sim3opt_job", "sim3opt_limits", "PnPsolver", "pnp_iterate", "pnp_job",
+           "pnp_limits", "pnp_ransac_parameters", "pnp_sample_quads", "pnp_window"]

@@ -163,6 +163,17 @@ SIGNATURES = {
     "orbx_sim3_optimize_batch_device": (_i, [_vp, _vp, _i, _i, _vp, _i, _vp, ctypes.c_int64, _vp,
                                              ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp]),
     "orbx_sim3_optimize": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orbx_pnp_ransac_parameters": (_i, [ctypes.c_double, _i, _i, _i, ctypes.c_float, _i, _vp, _vp]),
+    "orbx_pnp_sample_quads": (_i, [_i, _i, _vp, _vp]),
+    "orbx_pnp_limits": (_i, [_vp, _vp, _vp, _vp]),
+    "orbx_pnp_iterate_batch_device": (_i, [_vp, _vp, _i, _i, _i, _vp, ctypes.c_int64, _vp,
+                                           ctypes.c_int64, _vp, _vp, ctypes.c_int64, _vp, _vp,
+                                           ctypes.c_int64, _vp]),
+    "orbx_pnp_iterate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orbx_pnp_correspondences_batch_device": (_i, [_vp, _i, _vp, ctypes.c_int64, _vp, _i, _vp, _vp,
+                                                   _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    "orbx_pnp_apply_batch_device": (_i, [_vp, _i, _vp, _vp, _vp, ctypes.c_int64, _vp,
+                                         ctypes.c_int64, _i, _vp, _vp, _vp, ctypes.c_int64, _vp]),
     # include/orbx_vocab.h
     "orbx_vocabulary_load_text": (_i, [ctypes.c_char_p, _i, ctypes.POINTER(_vp)]),
     "orbx_vocabulary_destroy": (_i, [_vp]),

@@ -24,9 +24,9 @@ LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
            "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
-           "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip"]
-HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_kernels.h", "orbx_host.h",
-           "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
+           "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip", "orbx_pnp.hip"]
+HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
+           "orbx_host.h", "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
            "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
            "../../include/orbx_kfdb.h"]
 HASH_TAG = b"orbx-src:"
@@ -380,6 +380,37 @@ def build_sim3opt_ref(force: bool = False, verbose: bool = False, sanitize: bool
     # -ffp-contract=off: every operation rounded on its own, as in the kernel
     cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
            "-I" + str(root / "include"), "-I" + str(CSRC), str(SIM3OPT_REF_SRC)]
+    if sanitize:
+        cmd += ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    cmd += ["-o", str(target) + ".tmp"]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(target) + ".tmp", target)
+    return target
+
+
+# ---- PnPsolver restated in plain C++ (tests/native/pnp_ref.cpp) -------------------------------------
+PNP_REF_SRC = PKG.parent / "tests" / "native" / "pnp_ref.cpp"
+PNP_REF_BIN = PKG.parent / "tests" / "native" / "pnp_ref"
+
+
+def build_pnp_ref(force: bool = False, verbose: bool = False, sanitize: bool = False,
+                  out: pathlib.Path | None = None) -> pathlib.Path:
+    """g++ on the record layouts of include/ only: no liborbx and no GPU (the CPU reference of
+    orbx_pnp_iterate*).  sanitize: the stand-alone program with -fsanitize=address,undefined, to
+    `out`."""
+    root = PKG.parent
+    target = pathlib.Path(out) if out else PNP_REF_BIN
+    if sanitize and target.resolve() == PNP_REF_BIN.resolve():
+        raise ValueError("the sanitized program goes to a path of its own")
+    deps = [PNP_REF_SRC] + sorted((root / "include").glob("*.h"))
+    newest = max(p.stat().st_mtime for p in deps)
+    if not force and target.exists() and target.stat().st_mtime >= newest:
+        return target
+    # -ffp-contract=off: every operation rounded on its own, as in the kernels
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
+           "-I" + str(root / "include"), str(PNP_REF_SRC)]
     if sanitize:
         cmd += ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
     cmd += ["-o", str(target) + ".tmp"]

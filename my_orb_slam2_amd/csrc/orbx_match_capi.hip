@@ -26,7 +26,7 @@ struct orbx_matcher {
     orbx_matcher_params prm;
     hipStream_t stream = nullptr;
     int ncu = 256;                     // compute units of the device (BF chunk sizing)
-    DevBuf d_in, d_out, d_aux, d_proj, d_bf, d_sim3;
+    DevBuf d_in, d_out, d_aux, d_proj, d_bf, d_sim3, d_pnp;
     int* d_err = nullptr;
     std::vector<uint8_t> staging;
     KernelTimer timer;
@@ -385,6 +385,7 @@ orbx_status orbx_matcher_destroy(orbx_matcher* m) {
     m->d_proj.release();
     m->d_bf.release();
     m->d_sim3.release();
+    m->d_pnp.release();
     if (m->d_err) (void)hipFree(m->d_err);
     m->timer.destroy();
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -756,6 +757,43 @@ orbx_status orbx_sim3_iterate_batch_device(
     L.ninliers = ninlier_bytes;
     L.scratch = m->d_sim3.p;
     if (!HIPOK(launch_sim3(L, (hipStream_t)stream))) return ORBX_ERR_DEVICE;
+    return ORBX_OK;
+}
+
+orbx_status orbx_pnp_iterate_batch_device(
+    orbx_matcher* m, const orbx_pnp_job* d_jobs, int32_t njobs, int32_t max_n,
+    int32_t max_call_its, const orbx_pnp_corr* d_corr, int64_t ncorr, const int32_t* d_quads,
+    int64_t nquads, orbx_pnp_state* d_state, uint8_t* d_best, int64_t nbest_bytes,
+    orbx_pnp_result* d_results, uint8_t* d_inliers, int64_t ninlier_bytes, void* stream) {
+    if (!m || njobs < 0 || max_n < 0 || max_call_its < 0 || ncorr < 0 || nquads < 0 ||
+        nbest_bytes < 0 || ninlier_bytes < 0)
+        return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_jobs || !d_state || !d_results || (ncorr > 0 && !d_corr) || (nquads > 0 && !d_quads) ||
+        (nbest_bytes > 0 && !d_best) || (ninlier_bytes > 0 && !d_inliers))
+        return ORBX_ERR_INVALID;
+    if (njobs > PNP_MAX_JOBS || max_n > PNP_MAX_N || max_call_its > PNP_MAX_ITS)
+        return ORBX_ERR_UNSUPPORTED;
+    const size_t bytes = pnp_scratch_bytes(njobs, max_n, max_call_its);
+    if (bytes > PNP_MAX_SCRATCH) return ORBX_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
+    if (!m->d_pnp.ensure(bytes)) return ORBX_ERR_DEVICE;
+    PnpLaunch L{};
+    L.jobs = d_jobs;
+    L.njobs = njobs, L.max_n = max_n, L.max_call = max_call_its;
+    L.corr = d_corr;
+    L.ncorr = ncorr;
+    L.quads = d_quads;
+    L.nquads = nquads;
+    L.state = d_state;
+    L.best = d_best;
+    L.nbest = nbest_bytes;
+    L.res = d_results;
+    L.inliers = d_inliers;
+    L.ninliers = ninlier_bytes;
+    L.scratch = m->d_pnp.p;
+    if (!HIPOK(launch_pnp(L, (hipStream_t)stream))) return ORBX_ERR_DEVICE;
     return ORBX_OK;
 }
 

@@ -114,6 +114,28 @@ struct Sim3OptLaunch {
 constexpr int SIM3OPT_MAX_N = 4096, SIM3OPT_MAX_JOBS = 65535;
 hipError_t launch_sim3_opt(const Sim3OptLaunch& a, hipStream_t st);
 
+// PnPsolver::iterate over njobs solvers (orbx_pnp.hip).  The array lengths bound what a job may
+// point at; scratch holds pnp_scratch_bytes(njobs, max_n, max_call) bytes.
+struct PnpLaunch {
+    const orbx_pnp_job* jobs;
+    int njobs, max_n, max_call;
+    const orbx_pnp_corr* corr;
+    long long ncorr;
+    const int32_t* quads;
+    long long nquads;
+    orbx_pnp_state* state;
+    uint8_t* best;
+    long long nbest;
+    orbx_pnp_result* res;
+    uint8_t* inliers;
+    long long ninliers;
+    void* scratch;
+};
+constexpr int PNP_MAX_N = 4096, PNP_MAX_ITS = 1024, PNP_MAX_JOBS = 4096;
+constexpr size_t PNP_MAX_SCRATCH = (size_t)1 << 30;
+size_t pnp_scratch_bytes(int njobs, int max_n, int max_call);
+hipError_t launch_pnp(const PnpLaunch& a, hipStream_t st);
+
 // Projection searches (modes of orbx_proj_mode plus PROJ_INIT) over njobs independent jobs
 // (frames).  With t_off == nullptr there is one job: target T, queries [0, nq).  Otherwise
 // job j's target is T's arrays offset by t_off[j] features (keys/desc/u_right/claimed) and

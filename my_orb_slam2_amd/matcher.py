@@ -472,6 +472,53 @@ class ORBmatcher:
                   nbytes(d_corr) // SIM3OPT_CORR_DTYPE.itemsize, p_in, stride, ptr(d_results),
                   ptr(d_keep), nbytes(d_keep), ctypes.c_void_p(stream)))
 
+    # ---- PnPsolver::iterate for many solvers (PnPsolver.cc:165-258) ----------------------------
+    def pnp_iterate_batch_device(self, d_jobs, njobs: int, max_n: int, max_call_its: int, d_corr,
+                                 d_quads, d_state, d_best, d_results, d_inliers, stream=0):
+        """orbx_pnp_iterate_batch_device: one iterate() call of every job (device tensors of bytes
+        or of the records' words: PNP_JOB_DTYPE jobs, PNP_CORR_DTYPE correspondences, int32 quads
+        [n, 4], PNP_STATE_DTYPE states and the best inlier bytes in / out, PNP_RESULT_DTYPE results
+        and the inlier bytes out).  The arrays' lengths are taken from the tensors; a job that
+        points outside them is refused in its info word."""
+        from .pnp import PNP_CORR_DTYPE
+
+        def nbytes(t):
+            return 0 if t is None else int(t.numel() * t.element_size())
+        check("orbx_pnp_iterate_batch_device",
+              self._lib.orbx_pnp_iterate_batch_device(
+                  self._h, ptr(d_jobs), int(njobs), int(max_n), int(max_call_its), ptr(d_corr),
+                  nbytes(d_corr) // PNP_CORR_DTYPE.itemsize, ptr(d_quads), nbytes(d_quads) // 16,
+                  ptr(d_state), ptr(d_best), nbytes(d_best), ptr(d_results), ptr(d_inliers),
+                  nbytes(d_inliers), ctypes.c_void_p(stream)))
+
+    def pnp_correspondences_batch_device(self, njobs: int, d_match, match_stride: int, d_keys_un,
+                                         n_feat: int, d_mps, d_mp_off, d_corr, corr_stride: int,
+                                         d_N, d_N_flags=None, stream=0):
+        """orbx_pnp_correspondences_batch_device: job j's PNP_CORR_DTYPE records (at d_corr[j *
+        corr_stride ..], d_N[j] of them) from row j of the batched SearchByBoW(KF, Frame) matches,
+        the frame's mvKeysUn and the candidate's block of map_point records."""
+        check("orbx_pnp_correspondences_batch_device",
+              self._lib.orbx_pnp_correspondences_batch_device(
+                  self._h, int(njobs), ptr(d_match), int(match_stride), ptr(d_keys_un), int(n_feat),
+                  ptr(d_mps), ptr(d_mp_off), ptr(d_corr), int(corr_stride), ptr(d_N),
+                  ptr(d_N_flags), ctypes.c_void_p(stream)))
+
+    def pnp_apply_batch_device(self, njobs: int, d_jobs, d_results, d_inliers, d_match,
+                               match_stride: int, n_feat: int, d_template, d_poses, d_mp_of_feat,
+                               feat_stride: int, stream=0):
+        """orbx_pnp_apply_batch_device (Tracking.cc:1546-1562): per job the frame_pose record
+        (the template's camera half, Rcw / tcw / Ow from the result's Tcw) and the MapPoint of
+        every feature (the match where the solver kept it, else -1), as PoseOptimization reads
+        them; a job without a pose gets the template and -1."""
+        def nbytes(t):
+            return 0 if t is None else int(t.numel() * t.element_size())
+        check("orbx_pnp_apply_batch_device",
+              self._lib.orbx_pnp_apply_batch_device(
+                  self._h, int(njobs), ptr(d_jobs), ptr(d_results), ptr(d_inliers),
+                  nbytes(d_inliers), ptr(d_match), int(match_stride), int(n_feat),
+                  ptr(d_template), ptr(d_poses), ptr(d_mp_of_feat), int(feat_stride),
+                  ctypes.c_void_p(stream)))
+
     def search_by_projection_batch_device(self, mode: int, frames: "DeviceFrameBatch", d_qdesc,
                                           d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
                                           inv_sigma2=None, orb_dist: int = 0, stream=0):
