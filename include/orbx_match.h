@@ -346,8 +346,8 @@ orbx_status orbx_triangulate_matches_batch_device(
  * status or x3d (with npairs > 0), a negative count, depth NULL with u_right given, mb negative or
  * NaN, a pair index outside its keyframe, an idx1 that occurs twice, an octave of a paired
  * feature outside [0, nlevels), nlevels < 1.  nlevels > 16 or a keyframe above 32768 features:
- * ORBX_ERR_UNSUPPORTED.  npairs == 0: ORBX_OK.  Without a GPU: ORBX_ERR_DEVICE.  Calls are
- * serialised inside the library. */
+ * ORBX_ERR_UNSUPPORTED.  npairs == 0: ORBX_OK.  Without a GPU: ORBX_ERR_DEVICE.  Calls from
+ * several threads run beside each other, each on a device stream and staging buffer of its own. */
 orbx_status orbx_triangulate_matches(
     const orbx_frame_pose* pose1, const orbx_frame_pose* pose2, const orbx_keypoint* keys1,
     const orbx_keypoint* keys_raw1, const float* u_right1, const float* depth1,
@@ -569,7 +569,8 @@ orbx_status orbx_sim3_iterate_batch_device(
  * bytes.  ORBX_ERR_INVALID: a NULL argument, N, mN1 or n_iterations negative, max_its < 1; N or
  * max_its above orbx_sim3_limits: ORBX_ERR_UNSUPPORTED; the checks run before the device is
  * touched, and without a GPU the call returns ORBX_ERR_DEVICE.  What the batched form refuses per
- * job comes back the same way, in res->info.  Calls are serialised inside the library. */
+ * job comes back the same way, in res->info.  Calls from several threads run beside each other,
+ * each on a device stream and staging buffer of its own. */
 orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pose* pose2,
                               const orbx_sim3_job* job, const orbx_sim3_corr* corr,
                               const int32_t* triples, orbx_sim3_state* state,
@@ -672,7 +673,8 @@ orbx_status orbx_sim3_optimize_batch_device(
  * ORBX_ERR_INVALID: a NULL argument, N or mN1 negative; N above orbx_sim3opt_limits:
  * ORBX_ERR_UNSUPPORTED; the checks run before the device is touched, and without a GPU the call
  * returns ORBX_ERR_DEVICE.  What the batched form refuses per job comes back the same way, in
- * res->info.  Calls are serialised inside the library. */
+ * res->info.  Calls from several threads run beside each other, each on a device stream and
+ * staging buffer of its own. */
 orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_pose* pose2,
                                const orbx_sim3opt_job* job, const orbx_sim3opt_corr* corr,
                                const orbx_sim3opt_in* sim3_in, orbx_sim3opt_result* res,
@@ -805,8 +807,8 @@ orbx_status orbx_pnp_iterate_batch_device(
  * ORBX_ERR_INVALID: a NULL argument, N, n_matches or state->iterations negative, max_its < 1; N,
  * max_its or the window above orbx_pnp_limits: ORBX_ERR_UNSUPPORTED; the checks run before the
  * device is touched, and without a GPU the call returns ORBX_ERR_DEVICE.  What the batched form
- * refuses per job comes back the same way, in res->info.  Calls are serialised inside the
- * library. */
+ * refuses per job comes back the same way, in res->info.  Calls from several threads run beside
+ * each other, each on a device stream and staging buffer of its own. */
 orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
                              const int32_t* quads, orbx_pnp_state* state, uint8_t* best,
                              orbx_pnp_result* res, uint8_t* inliers, int device);

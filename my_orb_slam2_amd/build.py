@@ -26,9 +26,9 @@ SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_matc
            "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
            "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip", "orbx_pnp.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
-           "orbx_host.h", "orbx_match_kernels.h", "orbx_pattern.inc", "../../include/orbx.h",
-           "../../include/orbx_match.h", "../../include/orbx_vocab.h", "../../include/orbx_frame.h",
-           "../../include/orbx_kfdb.h"]
+           "orbx_host.h", "orbx_lm.h", "orbx_match_kernels.h", "orbx_pattern.inc",
+           "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
+           "../../include/orbx_frame.h", "../../include/orbx_kfdb.h"]
 HASH_TAG = b"orbx-src:"
 
 # -ffp-contract=off: every float a*b+c in the path is two roundings, as in the x86 reference
@@ -101,267 +101,181 @@ if __name__ == "__main__":
     print(LIB, source_hash())
 
 
-# ---- the C++ boundary consumer (tests/native/boundary_test.cpp) -------------------------------
-BOUNDARY_SRC = PKG.parent / "tests" / "native" / "boundary_test.cpp"
-BOUNDARY_BIN = PKG.parent / "tests" / "native" / "boundary_test"
+# ---- the native test programs (tests/native/*.cpp) ----------------------------------------------
+ROOT = PKG.parent
+NATIVE = ROOT / "tests" / "native"
+INCLUDE, INTEGRATION, CV_STANDIN = ROOT / "include", ROOT / "integration", NATIVE / "cv_standin"
+# found at run time through the binary's RUNPATH, $ORIGIN-relative, so the tree can move
+LINK_LIB = ["-L" + str(PKG), "-lorbx", "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
+            "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd"]
+# -ffp-contract=off: the float statements restated in a program as written, every operation
+# rounded on its own as in the kernels
+REF_FLAGS = ("-Wextra", "-ffp-contract=off")
+SANITIZE = ("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")
+
+
+def _headers(*dirs) -> list:
+    """The *.h of each directory; the *.hpp below the cv stand-in."""
+    return [h for d in dirs for h in sorted(d.rglob("*.hpp") if d == CV_STANDIN else d.glob("*.h"))]
+
+
+def _build_native(src, target, deps, includes, *, flags=REF_FLAGS, link_lib=False, extra=(),
+                  force, verbose) -> pathlib.Path:
+    """g++ `src` into `target` when the target is older than the source or its newest dependency
+    (or always with force).  link_lib: against the in-tree liborbx.so, built first.  `extra`
+    follows the source on the command line."""
+    newest = max(p.stat().st_mtime for p in [src, *deps])
+    if not force and target.exists() and target.stat().st_mtime >= newest:
+        return target
+    if link_lib:
+        build(verbose=verbose)
+    cmd = (["g++", "-std=c++17", "-O2", "-Wall", *flags] + ["-I" + str(d) for d in includes] +
+           [str(src)] + (LINK_LIB if link_lib else []) + list(extra) +
+           ["-o", str(target) + ".tmp"])
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(str(target) + ".tmp", target)
+    return target
+
+
+def _sanitized(sanitize, out, plain) -> pathlib.Path:
+    """Where a reference program goes: `out` or `plain`; never a sanitised build over `plain`."""
+    target = pathlib.Path(out) if out else plain
+    if sanitize and target.resolve() == plain.resolve():
+        raise ValueError("the sanitized program goes to a path of its own")
+    return target
+
+
+# the C++ boundary consumer
+BOUNDARY_SRC = NATIVE / "boundary_test.cpp"
+BOUNDARY_BIN = NATIVE / "boundary_test"
 
 
 def build_boundary_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ against include/orbx*.h only, linked to the in-tree liborbx.so (found at run time
     through the binary's RUNPATH, $ORIGIN-relative, so the tree can move)."""
-    hdrs = sorted((PKG.parent / "include").glob("*.h"))
-    newest = max([BOUNDARY_SRC.stat().st_mtime] + [h.stat().st_mtime for h in hdrs])
-    if not force and BOUNDARY_BIN.exists() and BOUNDARY_BIN.stat().st_mtime >= newest:
-        return BOUNDARY_BIN
-    build(verbose=verbose)
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I" + str(PKG.parent / "include"),
-           str(BOUNDARY_SRC), "-L" + str(PKG), "-lorbx", "-L/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd",
-           "-pthread", "-o", str(BOUNDARY_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(BOUNDARY_BIN) + ".tmp", BOUNDARY_BIN)
-    return BOUNDARY_BIN
+    return _build_native(BOUNDARY_SRC, BOUNDARY_BIN, _headers(INCLUDE), [INCLUDE], flags=(),
+                         link_lib=True, extra=("-pthread",), force=force, verbose=verbose)
 
 
-# ---- the drop-in facade compiled as ORB-SLAM2 would include it (tests/native/facade_test.cpp) --
-FACADE_SRC = PKG.parent / "tests" / "native" / "facade_test.cpp"
-FACADE_BIN = PKG.parent / "tests" / "native" / "facade_test"
+# the drop-in facade compiled as ORB-SLAM2 would include it
+FACADE_SRC = NATIVE / "facade_test.cpp"
+FACADE_BIN = NATIVE / "facade_test"
 
 
 def build_facade_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on integration/ORBextractor.h + integration/orbx_slam2_glue.h with the cv stand-in
     headers of tests/native/cv_standin, linked to the in-tree liborbx.so."""
-    root = PKG.parent
-    deps = ([FACADE_SRC] + sorted((root / "include").glob("*.h")) +
-            sorted((root / "integration").glob("*.h")) +
-            sorted((root / "tests" / "native" / "cv_standin").rglob("*.hpp")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and FACADE_BIN.exists() and FACADE_BIN.stat().st_mtime >= newest:
-        return FACADE_BIN
-    build(verbose=verbose)
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-I" + str(root / "include"),
-           "-I" + str(root / "integration"), "-I" + str(root / "tests" / "native" / "cv_standin"),
-           str(FACADE_SRC), "-L" + str(PKG), "-lorbx", "-L/opt/rocm/lib",
-           "-Wl,-rpath-link,/opt/rocm/lib", "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd",
-           "-pthread", "-o", str(FACADE_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(FACADE_BIN) + ".tmp", FACADE_BIN)
-    return FACADE_BIN
+    return _build_native(FACADE_SRC, FACADE_BIN, _headers(INCLUDE, INTEGRATION, CV_STANDIN),
+                         [INCLUDE, INTEGRATION, CV_STANDIN], flags=("-Wextra",), link_lib=True,
+                         extra=("-pthread",), force=force, verbose=verbose)
 
 
-# ---- the ORBmatcher drop-in compiled as ORB-SLAM2 would include it (tests/native/matcher_test.cpp)
-MATCHER_SRC = PKG.parent / "tests" / "native" / "matcher_test.cpp"
-MATCHER_BIN = PKG.parent / "tests" / "native" / "matcher_test"
-MATCHER_CPU_BIN = PKG.parent / "tests" / "native" / "matcher_test_cpu"
+# the ORBmatcher drop-in compiled as ORB-SLAM2 would include it
+MATCHER_SRC = NATIVE / "matcher_test.cpp"
+MATCHER_BIN = NATIVE / "matcher_test"
+MATCHER_CPU_BIN = NATIVE / "matcher_test_cpu"
 
 
-def build_matcher_test(force: bool = False, verbose: bool = False, cpu: bool = False) -> pathlib.Path:
+def build_matcher_test(force: bool = False, verbose: bool = False,
+                       cpu: bool = False) -> pathlib.Path:
     """g++ on integration/ORBmatcher.h with the ORB-SLAM2 stand-in classes
     (tests/native/slam2_standin) and the cv stand-in, plus the CPU restatement it is checked
     against (oracle/orb_matcher_objects.h).  cpu=False: linked to the in-tree liborbx.so (the
     searches run on the GPU).  cpu=True: matcher_test_cpu, linked instead to the C-ABI test
     double tests/native/oracle_abi.cpp over oracle/orb_matcher_oracle.cpp (no GPU, no liborbx),
     for the CPU test suite."""
-    root = PKG.parent
-    native = root / "tests" / "native"
-    out = MATCHER_CPU_BIN if cpu else MATCHER_BIN
-    deps = ([MATCHER_SRC, native / "oracle_abi.cpp", root / "oracle" / "orb_matcher_oracle.cpp",
-             root / "oracle" / "orb_matcher_objects.h"] + sorted((root / "include").glob("*.h")) +
-            sorted((root / "integration").glob("*.h")) +
-            sorted((native / "cv_standin").rglob("*.hpp")) + sorted((native / "slam2_standin").glob("*.h")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and out.exists() and out.stat().st_mtime >= newest:
-        return out
-    # -ffp-contract=off: the facade's and the restatement's float expressions as written
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(root / "integration"),
-           "-I" + str(root / "oracle"), "-I" + str(native / "cv_standin"),
-           "-I" + str(native / "slam2_standin"), str(MATCHER_SRC)]
-    if cpu:
-        cmd += [str(native / "oracle_abi.cpp"), str(root / "oracle" / "orb_matcher_oracle.cpp")]
-    else:
-        build(verbose=verbose)
-        cmd += ["-L" + str(PKG), "-lorbx", "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-                "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd"]
-    cmd += ["-pthread", "-o", str(out) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(out) + ".tmp", out)
-    return out
+    double = [NATIVE / "oracle_abi.cpp", ROOT / "oracle" / "orb_matcher_oracle.cpp"]
+    deps = (double + [ROOT / "oracle" / "orb_matcher_objects.h"] +
+            _headers(INCLUDE, INTEGRATION, CV_STANDIN, NATIVE / "slam2_standin"))
+    return _build_native(MATCHER_SRC, MATCHER_CPU_BIN if cpu else MATCHER_BIN, deps,
+                         [INCLUDE, INTEGRATION, ROOT / "oracle", CV_STANDIN,
+                          NATIVE / "slam2_standin"], link_lib=not cpu,
+                         extra=([str(p) for p in double] if cpu else []) + ["-pthread"],
+                         force=force, verbose=verbose)
 
 
-# ---- the RGB-D glue compiled as ORB-SLAM2 would include it (tests/native/rgbd_test.cpp) ---------
-RGBD_SRC = PKG.parent / "tests" / "native" / "rgbd_test.cpp"
-RGBD_BIN = PKG.parent / "tests" / "native" / "rgbd_test"
+# the RGB-D glue compiled as ORB-SLAM2 would include it
+RGBD_SRC = NATIVE / "rgbd_test.cpp"
+RGBD_BIN = NATIVE / "rgbd_test"
 
 
 def build_rgbd_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on integration/orbx_slam2_glue.h (ComputeStereoFromRGBD) with the cv stand-in and
     tests/native/rgbd_standin.h, linked to the in-tree liborbx.so."""
-    root = PKG.parent
-    native = root / "tests" / "native"
-    deps = ([RGBD_SRC, native / "rgbd_standin.h"] + sorted((root / "include").glob("*.h")) +
-            sorted((root / "integration").glob("*.h")) +
-            sorted((native / "cv_standin").rglob("*.hpp")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and RGBD_BIN.exists() and RGBD_BIN.stat().st_mtime >= newest:
-        return RGBD_BIN
-    build(verbose=verbose)
-    # -ffp-contract=off: the reference's float statements restated in the program, as written
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(root / "integration"),
-           "-I" + str(native / "cv_standin"), "-I" + str(native), str(RGBD_SRC), "-L" + str(PKG),
-           "-lorbx", "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-           "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd", "-pthread", "-o", str(RGBD_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(RGBD_BIN) + ".tmp", RGBD_BIN)
-    return RGBD_BIN
+    deps = [NATIVE / "rgbd_standin.h"] + _headers(INCLUDE, INTEGRATION, CV_STANDIN)
+    return _build_native(RGBD_SRC, RGBD_BIN, deps, [INCLUDE, INTEGRATION, CV_STANDIN, NATIVE],
+                         link_lib=True, extra=("-pthread",), force=force, verbose=verbose)
 
 
-# ---- the rectifier glue compiled as ORB-SLAM2 would include it (tests/native/remap_test.cpp) ----
-REMAP_SRC = PKG.parent / "tests" / "native" / "remap_test.cpp"
-REMAP_BIN = PKG.parent / "tests" / "native" / "remap_test"
+# the rectifier glue compiled as ORB-SLAM2 would include it
+REMAP_SRC = NATIVE / "remap_test.cpp"
+REMAP_BIN = NATIVE / "remap_test"
 
 
 def build_remap_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on integration/orbx_slam2_glue.h (orbx_glue::Rectifier) with the cv stand-in, linked to
     the in-tree liborbx.so."""
-    root = PKG.parent
-    native = root / "tests" / "native"
-    deps = ([REMAP_SRC] + sorted((root / "include").glob("*.h")) +
-            sorted((root / "integration").glob("*.h")) +
-            sorted((native / "cv_standin").rglob("*.hpp")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and REMAP_BIN.exists() and REMAP_BIN.stat().st_mtime >= newest:
-        return REMAP_BIN
-    build(verbose=verbose)
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(root / "integration"),
-           "-I" + str(native / "cv_standin"), str(REMAP_SRC), "-L" + str(PKG),
-           "-lorbx", "-L/opt/rocm/lib", "-Wl,-rpath-link,/opt/rocm/lib",
-           "-Wl,-rpath,$ORIGIN/../../my_orb_slam2_amd", "-pthread", "-o", str(REMAP_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(REMAP_BIN) + ".tmp", REMAP_BIN)
-    return REMAP_BIN
+    return _build_native(REMAP_SRC, REMAP_BIN, _headers(INCLUDE, INTEGRATION, CV_STANDIN),
+                         [INCLUDE, INTEGRATION, CV_STANDIN], link_lib=True, extra=("-pthread",),
+                         force=force, verbose=verbose)
 
 
-# ---- the projection loops restated over the cv stand-in (tests/native/project_ref.cpp) ----------
-PROJECT_REF_SRC = PKG.parent / "tests" / "native" / "project_ref.cpp"
-PROJECT_REF_BIN = PKG.parent / "tests" / "native" / "project_ref"
+# the projection loops restated over the cv stand-in
+PROJECT_REF_SRC = NATIVE / "project_ref.cpp"
+PROJECT_REF_BIN = NATIVE / "project_ref"
 
 
 def build_project_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on the cv stand-in and the record layouts of include/orbx_frame.h only: no liborbx and
     no GPU (the CPU reference of orbx_project_map_points*)."""
-    root = PKG.parent
-    native = root / "tests" / "native"
-    deps = ([PROJECT_REF_SRC] + sorted((root / "include").glob("*.h")) +
-            sorted((native / "cv_standin").rglob("*.hpp")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and PROJECT_REF_BIN.exists() and PROJECT_REF_BIN.stat().st_mtime >= newest:
-        return PROJECT_REF_BIN
-    # -ffp-contract=off: the reference's float statements as written
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(native / "cv_standin"),
-           str(PROJECT_REF_SRC), "-o", str(PROJECT_REF_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(PROJECT_REF_BIN) + ".tmp", PROJECT_REF_BIN)
-    return PROJECT_REF_BIN
+    return _build_native(PROJECT_REF_SRC, PROJECT_REF_BIN, _headers(INCLUDE, CV_STANDIN),
+                         [INCLUDE, CV_STANDIN], force=force, verbose=verbose)
 
 
-# ---- CreateNewMapPoints' loop restated over the cv stand-in (tests/native/triangulate_ref.cpp) ----
-TRIANGULATE_REF_SRC = PKG.parent / "tests" / "native" / "triangulate_ref.cpp"
-TRIANGULATE_REF_BIN = PKG.parent / "tests" / "native" / "triangulate_ref"
+# CreateNewMapPoints' loop restated over the cv stand-in
+TRIANGULATE_REF_SRC = NATIVE / "triangulate_ref.cpp"
+TRIANGULATE_REF_BIN = NATIVE / "triangulate_ref"
 
 
 def build_triangulate_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on the cv stand-in and the record layouts of include/ only: no liborbx and no GPU (the
     CPU reference of orbx_triangulate_matches*)."""
-    root = PKG.parent
-    native = root / "tests" / "native"
-    deps = ([TRIANGULATE_REF_SRC] + sorted((root / "include").glob("*.h")) +
-            sorted((native / "cv_standin").rglob("*.hpp")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if (not force and TRIANGULATE_REF_BIN.exists() and
-            TRIANGULATE_REF_BIN.stat().st_mtime >= newest):
-        return TRIANGULATE_REF_BIN
-    # -ffp-contract=off: the reference's float statements as written
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(native / "cv_standin"),
-           str(TRIANGULATE_REF_SRC), "-o", str(TRIANGULATE_REF_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(TRIANGULATE_REF_BIN) + ".tmp", TRIANGULATE_REF_BIN)
-    return TRIANGULATE_REF_BIN
+    return _build_native(TRIANGULATE_REF_SRC, TRIANGULATE_REF_BIN, _headers(INCLUDE, CV_STANDIN),
+                         [INCLUDE, CV_STANDIN], force=force, verbose=verbose)
 
 
-# ---- PoseOptimization restated in plain C++ doubles (tests/native/poseopt_ref.cpp) ---------------
-POSEOPT_REF_SRC = PKG.parent / "tests" / "native" / "poseopt_ref.cpp"
-POSEOPT_REF_BIN = PKG.parent / "tests" / "native" / "poseopt_ref"
+# PoseOptimization restated in plain C++ doubles
+POSEOPT_REF_SRC = NATIVE / "poseopt_ref.cpp"
+POSEOPT_REF_BIN = NATIVE / "poseopt_ref"
 
 
 def build_poseopt_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on the record layouts of include/ and csrc/orbx_math.h (orbx_sincos_f64) only: no
     liborbx and no GPU (the CPU reference of orbx_pose_optimization*)."""
-    root = PKG.parent
-    deps = [POSEOPT_REF_SRC, CSRC / "orbx_math.h"] + sorted((root / "include").glob("*.h"))
-    newest = max(p.stat().st_mtime for p in deps)
-    if (not force and POSEOPT_REF_BIN.exists() and
-            POSEOPT_REF_BIN.stat().st_mtime >= newest):
-        return POSEOPT_REF_BIN
-    # -ffp-contract=off: every operation rounded on its own, as in the kernel
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(CSRC), str(POSEOPT_REF_SRC),
-           "-o", str(POSEOPT_REF_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(POSEOPT_REF_BIN) + ".tmp", POSEOPT_REF_BIN)
-    return POSEOPT_REF_BIN
+    return _build_native(POSEOPT_REF_SRC, POSEOPT_REF_BIN,
+                         [CSRC / "orbx_math.h"] + _headers(INCLUDE), [INCLUDE, CSRC],
+                         force=force, verbose=verbose)
 
 
-# ---- Sim3Solver restated over the cv stand-in (tests/native/sim3_ref.cpp) -------------------------
-SIM3_REF_SRC = PKG.parent / "tests" / "native" / "sim3_ref.cpp"
-SIM3_REF_BIN = PKG.parent / "tests" / "native" / "sim3_ref"
+# Sim3Solver restated over the cv stand-in
+SIM3_REF_SRC = NATIVE / "sim3_ref.cpp"
+SIM3_REF_BIN = NATIVE / "sim3_ref"
 
 
 def build_sim3_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
     """g++ on the cv stand-in, tests/native/cv_sim3_standin.hpp, the record layouts of include/ and
     csrc/orbx_math.h (orbx_atan2_f64, orbx_sincos_f64) only: no liborbx and no GPU (the CPU
     reference of orbx_sim3_iterate*)."""
-    root = PKG.parent
-    native = root / "tests" / "native"
-    deps = ([SIM3_REF_SRC, native / "cv_sim3_standin.hpp", CSRC / "orbx_math.h"] +
-            sorted((root / "include").glob("*.h")) + sorted((native / "cv_standin").rglob("*.hpp")))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and SIM3_REF_BIN.exists() and SIM3_REF_BIN.stat().st_mtime >= newest:
-        return SIM3_REF_BIN
-    # -ffp-contract=off: every operation rounded on its own, as in the kernels
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(CSRC), "-I" + str(native / "cv_standin"),
-           "-I" + str(native), str(SIM3_REF_SRC), "-o", str(SIM3_REF_BIN) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(SIM3_REF_BIN) + ".tmp", SIM3_REF_BIN)
-    return SIM3_REF_BIN
+    deps = [NATIVE / "cv_sim3_standin.hpp", CSRC / "orbx_math.h"] + _headers(INCLUDE, CV_STANDIN)
+    return _build_native(SIM3_REF_SRC, SIM3_REF_BIN, deps, [INCLUDE, CSRC, CV_STANDIN, NATIVE],
+                         force=force, verbose=verbose)
 
 
-# ---- OptimizeSim3 restated in plain C++ doubles (tests/native/sim3opt_ref.cpp) --------------------
-SIM3OPT_REF_SRC = PKG.parent / "tests" / "native" / "sim3opt_ref.cpp"
-SIM3OPT_REF_BIN = PKG.parent / "tests" / "native" / "sim3opt_ref"
+# OptimizeSim3 restated in plain C++ doubles
+SIM3OPT_REF_SRC = NATIVE / "sim3opt_ref.cpp"
+SIM3OPT_REF_BIN = NATIVE / "sim3opt_ref"
 
 
 def build_sim3opt_ref(force: bool = False, verbose: bool = False, sanitize: bool = False,
@@ -369,30 +283,14 @@ def build_sim3opt_ref(force: bool = False, verbose: bool = False, sanitize: bool
     """g++ on the record layouts of include/ and csrc/orbx_math.h (orbx_sincos_f64, orbx_exp_f64)
     only: no liborbx and no GPU (the CPU reference of orbx_sim3_optimize*).  sanitize: the
     stand-alone program with -fsanitize=address,undefined, to `out`."""
-    root = PKG.parent
-    target = pathlib.Path(out) if out else SIM3OPT_REF_BIN
-    if sanitize and target.resolve() == SIM3OPT_REF_BIN.resolve():
-        raise ValueError("the sanitized program goes to a path of its own")
-    deps = [SIM3OPT_REF_SRC, CSRC / "orbx_math.h"] + sorted((root / "include").glob("*.h"))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and target.exists() and target.stat().st_mtime >= newest:
-        return target
-    # -ffp-contract=off: every operation rounded on its own, as in the kernel
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), "-I" + str(CSRC), str(SIM3OPT_REF_SRC)]
-    if sanitize:
-        cmd += ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    cmd += ["-o", str(target) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(target) + ".tmp", target)
-    return target
+    return _build_native(SIM3OPT_REF_SRC, _sanitized(sanitize, out, SIM3OPT_REF_BIN),
+                         [CSRC / "orbx_math.h"] + _headers(INCLUDE), [INCLUDE, CSRC],
+                         extra=SANITIZE if sanitize else (), force=force, verbose=verbose)
 
 
-# ---- PnPsolver restated in plain C++ (tests/native/pnp_ref.cpp) -------------------------------------
-PNP_REF_SRC = PKG.parent / "tests" / "native" / "pnp_ref.cpp"
-PNP_REF_BIN = PKG.parent / "tests" / "native" / "pnp_ref"
+# PnPsolver restated in plain C++
+PNP_REF_SRC = NATIVE / "pnp_ref.cpp"
+PNP_REF_BIN = NATIVE / "pnp_ref"
 
 
 def build_pnp_ref(force: bool = False, verbose: bool = False, sanitize: bool = False,
@@ -400,22 +298,6 @@ def build_pnp_ref(force: bool = False, verbose: bool = False, sanitize: bool = F
     """g++ on the record layouts of include/ only: no liborbx and no GPU (the CPU reference of
     orbx_pnp_iterate*).  sanitize: the stand-alone program with -fsanitize=address,undefined, to
     `out`."""
-    root = PKG.parent
-    target = pathlib.Path(out) if out else PNP_REF_BIN
-    if sanitize and target.resolve() == PNP_REF_BIN.resolve():
-        raise ValueError("the sanitized program goes to a path of its own")
-    deps = [PNP_REF_SRC] + sorted((root / "include").glob("*.h"))
-    newest = max(p.stat().st_mtime for p in deps)
-    if not force and target.exists() and target.stat().st_mtime >= newest:
-        return target
-    # -ffp-contract=off: every operation rounded on its own, as in the kernels
-    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-Wextra", "-ffp-contract=off",
-           "-I" + str(root / "include"), str(PNP_REF_SRC)]
-    if sanitize:
-        cmd += ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    cmd += ["-o", str(target) + ".tmp"]
-    if verbose:
-        print(" ".join(cmd), file=sys.stderr)
-    subprocess.run(cmd, check=True)
-    os.replace(str(target) + ".tmp", target)
-    return target
+    return _build_native(PNP_REF_SRC, _sanitized(sanitize, out, PNP_REF_BIN), _headers(INCLUDE),
+                         [INCLUDE], extra=SANITIZE if sanitize else (), force=force,
+                         verbose=verbose)

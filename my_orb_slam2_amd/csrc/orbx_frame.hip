@@ -660,48 +660,37 @@ int depth_scales(int type, float factor) {
     return type != ORBX_DEPTH_F32 || std::fabs(factor - 1.0f) > 1e-5;
 }
 
-// Device staging of the host-array entry points: a pool of (device, non-blocking stream,
-// growable buffer) slots taken for the length of one call.  After warm-up a call allocates
-// nothing, and it waits only for its own stream, never for the device (the reference calls
-// these from the Tracking thread while LocalMapping / LoopClosing run matchers).
-struct Scratch {
-    int device = -1;
-    hipStream_t st = nullptr;
-    DevBuf buf;
-};
+// The pool behind ScratchLease (orbx_host.h): the slots no call holds at the moment.
 std::mutex g_scratch_mu;
 std::vector<Scratch*> g_scratch_free;
 
-struct ScratchLease {
-    Scratch* s = nullptr;
-    explicit ScratchLease(int device) {
-        {
-            std::lock_guard<std::mutex> lk(g_scratch_mu);
-            for (size_t i = 0; i < g_scratch_free.size(); ++i)
-                if (g_scratch_free[i]->device == device) {
-                    s = g_scratch_free[i];
-                    g_scratch_free.erase(g_scratch_free.begin() + i);
-                    break;
-                }
-        }
-        if (!s) {
-            Scratch* n = new Scratch();
-            n->device = device;
-            if (!HIPOK(hipStreamCreateWithFlags(&n->st, hipStreamNonBlocking))) {
-                delete n;
-                return;
-            }
-            s = n;
-        }
-    }
-    ~ScratchLease() {
-        if (!s) return;
-        std::lock_guard<std::mutex> lk(g_scratch_mu);
-        g_scratch_free.push_back(s);   // slots live for the process (no teardown-order hazards)
-    }
-};
-
 }  // namespace
+
+orbx::ScratchLease::ScratchLease(int device) {
+    {
+        std::lock_guard<std::mutex> lk(g_scratch_mu);
+        for (size_t i = 0; i < g_scratch_free.size(); ++i)
+            if (g_scratch_free[i]->device == device) {
+                s = g_scratch_free[i];
+                g_scratch_free.erase(g_scratch_free.begin() + i);
+                break;
+            }
+    }
+    if (!s) {
+        Scratch* n = new Scratch();
+        n->device = device;
+        if (!HIPOK(hipStreamCreateWithFlags(&n->st, hipStreamNonBlocking))) {
+            delete n;
+            return;
+        }
+        s = n;
+    }
+}
+orbx::ScratchLease::~ScratchLease() {
+    if (!s) return;
+    std::lock_guard<std::mutex> lk(g_scratch_mu);
+    g_scratch_free.push_back(s);   // slots live for the process (no teardown-order hazards)
+}
 
 extern "C" {
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstddef>
 
 #define ORBX_MAX_DEVICES 64  // per-device kernel attribute caches (prepare_kernels, kfdb)
@@ -41,6 +42,39 @@ struct DevBuf {
         return true;
     }
     template <class T> T* as() const { return (T*)p; }
+};
+
+// Offsets inside one staging block: every part starts on a 256-byte boundary.
+__host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Layout {
+    size_t end = 0;
+    size_t add(size_t bytes) {   // the offset of a part of `bytes` bytes, put behind the last one
+        const size_t o = end;
+        end += al256(bytes);
+        return o;
+    }
+};
+
+// (int) of a double as x86-64 converts it (cvttsd2si; cvttss2si for a widened float): NaN and
+// everything outside int's range give INT_MIN
+inline int cvtt(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
+
+// Device staging of the host-array entry points: a pool of (device, non-blocking stream,
+// growable buffer) slots taken for the length of one call.  After warm-up a call allocates
+// nothing, and it waits only for its own stream, never for the device (the reference calls
+// these from the Tracking thread while LocalMapping / LoopClosing run matchers).  The pool is
+// defined in orbx_frame.hip; slots live for the process (no teardown-order hazards).
+struct Scratch {
+    int device = -1;
+    hipStream_t st = nullptr;
+    DevBuf buf;
+};
+struct ScratchLease {
+    Scratch* s = nullptr;                  // nullptr: no stream could be created
+    explicit ScratchLease(int device);     // the calling thread's current device is `device`
+    ~ScratchLease();
+    ScratchLease(const ScratchLease&) = delete;
+    ScratchLease& operator=(const ScratchLease&) = delete;
 };
 
 }  // namespace orbx

@@ -29,7 +29,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/orbx_frame.h"
@@ -615,7 +614,6 @@ struct PnpScratch {
     double* work;        // [njobs][7 * max_n]: Refine's alphas, then its pcs
     int words;
 };
-__host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 __host__ __device__ inline PnpScratch scratch_of(void* base, int njobs, int max_n, int max_call) {
     PnpScratch s;
     s.words = (max_n + 63) / 64;
@@ -998,9 +996,6 @@ hipError_t launch_pnp_apply(int njobs, const orbx_pnp_job* jobs, const orbx_pnp_
 
 extern "C" {
 
-// cvttss2si / cvttsd2si: NaN and everything outside int's range give INT_MIN
-static int cvtt(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
-
 orbx_status orbx_pnp_ransac_parameters(double prob, int32_t min_inliers, int32_t max_its,
                                        int32_t min_set, float epsilon, int32_t N,
                                        int32_t* min_inliers_out, int32_t* max_its_out) {
@@ -1082,12 +1077,13 @@ orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
     const int N = job->N, nm = job->n_matches, max_call = (int)window;
     // one staging block: the inputs, the in / out state and best bytes, then the outputs and the
     // scratch
-    const size_t o_job = 0, o_corr = al256(sizeof(orbx_pnp_job)),
-                 o_quad = o_corr + al256(sizeof(orbx_pnp_corr) * (size_t)N),
-                 o_state = o_quad + al256(16 * (size_t)nq), o_best = o_state + 256,
-                 o_res = o_best + al256((size_t)N), o_inl = o_res + al256(sizeof(orbx_pnp_result)),
-                 out_end = o_inl + al256((size_t)nm), o_scratch = out_end,
-                 end = o_scratch + pnp_scratch_bytes(1, N, max_call);
+    Layout lay;
+    const size_t o_job = lay.add(sizeof(orbx_pnp_job)),
+                 o_corr = lay.add(sizeof(orbx_pnp_corr) * (size_t)N),
+                 o_quad = lay.add(16 * (size_t)nq), o_state = lay.add(256),
+                 o_best = lay.add((size_t)N), o_res = lay.add(sizeof(orbx_pnp_result)),
+                 o_inl = lay.add((size_t)nm), out_end = lay.end,
+                 o_scratch = lay.add(pnp_scratch_bytes(1, N, max_call)), end = lay.end;
     std::vector<uint8_t> h(out_end, 0);
     orbx_pnp_job hj = *job;
     hj.corr_off = 0, hj.inlier_off = 0, hj.quad_off = 0, hj.best_off = 0;
@@ -1100,17 +1096,10 @@ orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
     std::memcpy(h.data() + o_res, res, sizeof(*res));
     if (nm) std::memcpy(h.data() + o_inl, inliers, (size_t)nm);
 
-    static std::mutex mu;
-    static DevBuf bufs[ORBX_MAX_DEVICES];          // live for the process, like its stream
-    static hipStream_t streams[ORBX_MAX_DEVICES];
-    std::lock_guard<std::mutex> lk(mu);
-    DevBuf& buf = bufs[device];
-    if (!streams[device] &&
-        !HIPOK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking)))
-        return ORBX_ERR_DEVICE;
-    if (!buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = buf.as<uint8_t>();
-    hipStream_t st = streams[device];
+    ScratchLease lease(device);
+    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    uint8_t* d = lease.s->buf.as<uint8_t>();
+    hipStream_t st = lease.s->st;
     if (!HIPOK(hipMemcpyAsync(d, h.data(), out_end, hipMemcpyHostToDevice, st)))
         return ORBX_ERR_DEVICE;
     PnpLaunch L{};

@@ -4,8 +4,8 @@
 //
 // k_pose_opt: one wave per frame, PO_WAVES frames per workgroup; the waves of a workgroup never
 // meet (no workgroup barrier).  The g2o graph of the call is one SE3 vertex with unary edges, so
-// the whole of OptimizationAlgorithmLevenberg::solve is restated here: every evaluation walks the
-// frame's features in chunks of 64, one lane per feature; the active edges of a chunk put their
+// the whole of OptimizationAlgorithmLevenberg::solve is restated (orbx_lm.h): every evaluation walks
+// the frame's features in chunks of 64, one lane per feature; the active edges of a chunk put their
 // per-edge terms (21 lower-triangle entries of H, 6 of b, the robust chi2) into LDS, compacted in
 // edge order, and 28 lanes then add one term each, edge by edge: the sums round exactly as g2o's
 // loop over _activeEdges does.  The 6x6 system, the pose and the Levenberg state are wave-uniform:
@@ -13,21 +13,21 @@
 // An edge's _error is never stored: it is a function of the pose it was last evaluated at, and
 // that pose is kept instead (g2o does not recompute errors after a rejected trial).
 //
-// Forms evaluated inside Eigen (quaternion from a matrix, rotation of a vector, small products,
-// LDLT) are restated from the published algorithms [unverified-Eigen].  sin / cos
-// are orbx_sincos_f64 (orbx_math.h).  Built with -ffp-contract=off like the rest of the library.
+// The Levenberg loop, the forms evaluated inside Eigen, the robust kernel and the LDLT are
+// orbx_lm.h's (all but the loop shared with k_sim3_opt); the edge model (pose_map, pose_update,
+// edge_error, the analytic Jacobian) is here.  sin / cos are orbx_sincos_f64 (orbx_math.h).  Built
+// with -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
-#include <cfloat>
 #include <cstddef>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "orbx_host.h"
+#include "orbx_lm.h"
 #include "orbx_math.h"
 
 using namespace orbx;
@@ -58,28 +58,6 @@ struct PoseOptLaunch {
 struct Pose7 { double qx, qy, qz, qw, tx, ty, tz; };
 struct Cam { double fx, fy, cx, cy, bf; };
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ bool uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-// IEEE division and square root whatever the compiler's defaults
-__device__ __forceinline__ double dv(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ double sq(double a) { return __dsqrt_rn(a); }
-
-// Eigen's Quaternion(Matrix3) for one position of the largest diagonal entry
-template <int I>
-__device__ __forceinline__ void quat_branch(const double (&R)[3][3], double (&c)[3], double& w) {
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double t = sq(((R[I][I] - R[J][J]) - R[K][K]) + 1.0);
-    c[I] = 0.5 * t;
-    t = dv(0.5, t);
-    w = (R[K][J] - R[J][K]) * t;
-    c[J] = (R[J][I] + R[I][J]) * t;
-    c[K] = (R[K][I] + R[I][K]) * t;
-}
-
 // normalizeRotation (se3quat.h:280-285)
 __device__ __forceinline__ void quat_normalize(double& x, double& y, double& z, double& w) {
     if (w < 0.0) x = -x, y = -y, z = -z, w = -w;
@@ -87,38 +65,11 @@ __device__ __forceinline__ void quat_normalize(double& x, double& y, double& z, 
     x = dv(x, n), y = dv(y, n), z = dv(z, n), w = dv(w, n);
 }
 
-__device__ __forceinline__ void quat_from_matrix(const double (&R)[3][3], double& x, double& y,
-                                                 double& z, double& w) {
-    double t = (R[0][0] + R[1][1]) + R[2][2];
-    if (t > 0.0) {
-        t = sq(t + 1.0);
-        w = 0.5 * t;
-        t = dv(0.5, t);
-        x = (R[2][1] - R[1][2]) * t;
-        y = (R[0][2] - R[2][0]) * t;
-        z = (R[1][0] - R[0][1]) * t;
-    } else {
-        double c[3];
-        const bool one = R[1][1] > R[0][0];
-        const bool two = R[2][2] > (one ? R[1][1] : R[0][0]);
-        if (two) quat_branch<2>(R, c, w);
-        else if (one) quat_branch<1>(R, c, w);
-        else quat_branch<0>(R, c, w);
-        x = c[0], y = c[1], z = c[2];
-    }
+// SE3Quat(R, t)'s rotation (se3quat.h:67-71): Quaterniond(R), then normalizeRotation
+__device__ __forceinline__ void se3_quat(const double (&R)[3][3], double& x, double& y, double& z,
+                                         double& w) {
+    quat_from_matrix(R, x, y, z, w);
     quat_normalize(x, y, z, w);
-}
-
-// Eigen's Quaternion * Vector3: v + w*(2 q x v) + q x (2 q x v)
-__device__ __forceinline__ void quat_rotate(double qx, double qy, double qz, double qw, double px,
-                                            double py, double pz, double& ox, double& oy,
-                                            double& oz) {
-    double ux = qy * pz - qz * py, uy = qz * px - qx * pz, uz = qx * py - qy * px;
-    ux = ux + ux, uy = uy + uy, uz = uz + uz;
-    const double cx = qy * uz - qz * uy, cy = qz * ux - qx * uz, cz = qx * uy - qy * ux;
-    ox = (px + qw * ux) + cx;
-    oy = (py + qw * uy) + cy;
-    oz = (pz + qw * uz) + cz;
 }
 
 // SE3Quat::map
@@ -159,7 +110,7 @@ __device__ __forceinline__ bool pose_update(const double (&u)[6], Pose7& T) {
             }
         }
     double ex, ey, ez, ew;
-    quat_from_matrix(R, ex, ey, ez, ew);
+    se3_quat(R, ex, ey, ez, ew);
     const double t0 = (V[0][0] * u[3] + V[0][1] * u[4]) + V[0][2] * u[5];
     const double t1 = (V[1][0] * u[3] + V[1][1] * u[4]) + V[1][2] * u[5];
     const double t2 = (V[2][0] * u[3] + V[2][1] * u[4]) + V[2][2] * u[5];
@@ -167,10 +118,7 @@ __device__ __forceinline__ bool pose_update(const double (&u)[6], Pose7& T) {
     quat_rotate(ex, ey, ez, ew, T.tx, T.ty, T.tz, rx, ry, rz);
     Pose7 N;
     N.tx = t0 + rx, N.ty = t1 + ry, N.tz = t2 + rz;
-    N.qw = ((ew * T.qw - ex * T.qx) - ey * T.qy) - ez * T.qz;
-    N.qx = ((ew * T.qx + ex * T.qw) + ey * T.qz) - ez * T.qy;
-    N.qy = ((ew * T.qy + ey * T.qw) + ez * T.qx) - ex * T.qz;
-    N.qz = ((ew * T.qz + ez * T.qw) + ex * T.qy) - ey * T.qx;
+    quat_mul(ex, ey, ez, ew, T.qx, T.qy, T.qz, T.qw, N.qx, N.qy, N.qz, N.qw);
     quat_normalize(N.qx, N.qy, N.qz, N.qw);
     T = N;
     return true;
@@ -204,110 +152,6 @@ __device__ __forceinline__ double edge_error(const EdgeIn& e, const Pose7& T, co
         chi = err[0] * (e.info * err[0]) + err[1] * (e.info * err[1]);
     }
     return chi;
-}
-
-// RobustKernelHuber::robustify: rho and rho'
-__device__ __forceinline__ void huber(double e2, double delta, double& rho0, double& rho1) {
-    const double dsqr = delta * delta;
-    if (e2 <= dsqr) {
-        rho0 = e2;
-        rho1 = 1.0;
-    } else {
-        const double se = sq(e2);
-        rho0 = (2.0 * se) * delta - dsqr;
-        rho1 = dv(delta, se);
-    }
-}
-
-// Eigen::LDLT<MatrixXd>::compute + solve on the lower triangle of the 6x6 at A (row-major, LDS),
-// b -> x [unverified-Eigen]; false: not positive (x is left as it is).  Runs on one lane.
-__device__ __forceinline__ bool ldlt_solve_lds(double* A, const double* b, double* x) {
-    int* trl = (int*)(x + 6);            // 6 ints behind x: the transpositions, indexed freely
-    int sign = 0;                         // 0 zero, 1 positive, -1 negative, 2 indefinite
-    for (int k = 0; k < 6; ++k) {
-        int idx = k;
-        double best = fabs(A[7 * k]);
-        for (int i = k + 1; i < 6; ++i) {
-            const double v = fabs(A[7 * i]);
-            if (v > best) best = v, idx = i;
-        }
-        trl[k] = idx;
-        if (idx != k) {
-            for (int j = 0; j < k; ++j) {
-                const double t = A[6 * k + j];
-                A[6 * k + j] = A[6 * idx + j];
-                A[6 * idx + j] = t;
-            }
-            for (int i = idx + 1; i < 6; ++i) {
-                const double t = A[6 * i + k];
-                A[6 * i + k] = A[6 * i + idx];
-                A[6 * i + idx] = t;
-            }
-            {
-                const double t = A[7 * k];
-                A[7 * k] = A[7 * idx];
-                A[7 * idx] = t;
-            }
-            for (int i = k + 1; i < idx; ++i) {
-                const double t = A[6 * i + k];
-                A[6 * i + k] = A[6 * idx + i];
-                A[6 * idx + i] = t;
-            }
-        }
-        if (k > 0) {
-            double* temp = A + 36;   // D * A10^T
-            for (int j = 0; j < k; ++j) temp[j] = A[7 * j] * A[6 * k + j];
-            double s = A[6 * k] * temp[0];
-            for (int j = 1; j < k; ++j) s = s + A[6 * k + j] * temp[j];
-            A[7 * k] = A[7 * k] - s;
-            for (int i = k + 1; i < 6; ++i) {
-                double si = A[6 * i] * temp[0];
-                for (int j = 1; j < k; ++j) si = si + A[6 * i + j] * temp[j];
-                A[6 * i + k] = A[6 * i + k] - si;
-            }
-        }
-        const double akk = A[7 * k];
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) {
-            for (int j = 0; j < 6; ++j) trl[j] = j;
-            break;
-        }
-        if (valid)
-            for (int i = k + 1; i < 6; ++i) A[6 * i + k] = dv(A[6 * i + k], akk);
-        if (sign == 1) {
-            if (akk < 0.0) sign = 2;
-        } else if (sign == -1) {
-            if (akk > 0.0) sign = 2;
-        } else if (sign == 0) {
-            if (akk > 0.0) sign = 1;
-            else if (akk < 0.0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double* y = A + 42;
-    for (int i = 0; i < 6; ++i) y[i] = b[i];
-    for (int k = 0; k < 6; ++k) {
-        const int o = trl[k];
-        const double t = y[k];
-        y[k] = y[o];
-        y[o] = t;
-    }
-    for (int j = 0; j < 6; ++j)
-        for (int i = j + 1; i < 6; ++i) y[i] = y[i] - A[6 * i + j] * y[j];
-    for (int i = 0; i < 6; ++i) y[i] = fabs(A[7 * i]) > DBL_MIN ? dv(y[i], A[7 * i]) : 0.0;
-    for (int i = 4; i >= 0; --i) {
-        double s = A[6 * (i + 1) + i] * y[i + 1];
-        for (int j = i + 2; j < 6; ++j) s = s + A[6 * j + i] * y[j];
-        y[i] = y[i] - s;
-    }
-    for (int k = 5; k >= 0; --k) {
-        const int o = trl[k];
-        const double t = y[k];
-        y[k] = y[o];
-        y[o] = t;
-    }
-    for (int i = 0; i < 6; ++i) x[i] = y[i];
-    return true;
 }
 
 // The frame as one wave sees it
@@ -527,11 +371,11 @@ __global__ __launch_bounds__(64 * PO_WAVES) void k_pose_opt(const PoseOptLaunch 
         for (int i = 0; i < 3; ++i)
 #pragma unroll
             for (int j = 0; j < 3; ++j) R[i][j] = (double)P->Rcw[3 * i + j];
-        quat_from_matrix(R, start.qx, start.qy, start.qz, start.qw);
+        se3_quat(R, start.qx, start.qy, start.qz, start.qw);
         start.tx = (double)P->tcw[0], start.ty = (double)P->tcw[1], start.tz = (double)P->tcw[2];
     }
 
-    double* sums = c.S;            // [28]
+    // behind the sums[28] at c.S:
     double* Am = c.S + 28;         // [36] + temp[6] + y[6]: the solver's copy
     double* xs = c.S + 28 + 48;    // [6] the solution (persists over the trials of an optimize) + 6 ints
 
@@ -542,92 +386,21 @@ __global__ __launch_bounds__(64 * PO_WAVES) void k_pose_opt(const PoseOptLaunch 
     int nactive = nedges;
     for (int it = 0; it < 4; ++it) {
         est = start;
-        // ---- optimize(10) (sparse_optimizer.cpp:354-419): nothing at level 0 -> returns at once
-        if (nactive > 0) {
-            if (lane < 6) xs[lane] = 0.0;
-            wave_sync();
-            double lambda = 0.0, ni = 2.0;
-            int nbad_lm = 0;
-            for (int iter = 0; iter < 10; ++iter) {
-                ++iters;
-                evaluate<true>(c, est, kernel);
-                err_pose = est;
-                double current = sums[27], temp = current;
-                const double ini = current;
-                double b[6];
-#pragma unroll
-                for (int j = 0; j < 6; ++j) b[j] = sums[21 + j];
-                if (iter == 0) {
-                    double m = 0.0;
-                    const int dg[6] = {0, 2, 5, 9, 14, 20};
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) {
-                        const double a = fabs(sums[dg[j]]);
-                        m = a < m ? m : a;
-                    }
-                    lambda = 1e-5 * m;
-                    ni = 2.0;
-                    nbad_lm = 0;
-                }
-                double rho = 0.0;
-                int qmax = 0;
-                bool again;
-                do {
-                    const Pose7 backup = est;
-                    // setLambda(lambda, true) + solve + restoreDiagonal: the sums stay untouched
-                    if (lane == 0) {
-                        int o = 0;
-                        for (int r = 0; r < 6; ++r)
-                            for (int q = 0; q < 6; ++q)
-                                Am[6 * r + q] = q < r ? sums[o++] : q == r ? sums[o++] + lambda : 0.0;
-                        const bool ok = ldlt_solve_lds(Am, sums + 21, xs);
-                        ((int*)(xs + 6))[6] = ok ? 1 : 0;
-                    }
-                    wave_sync();
-                    bool ok2 = ((const int*)(xs + 6))[6] != 0;
-                    if (!ok2) flags |= ORBX_POSEOPT_NONPOSITIVE_SOLVE;
-                    ++trials;
-                    double x[6];
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) x[j] = xs[j];
-                    wave_sync();
-                    if (uniform(pose_update(x, est))) {
-                        evaluate<false>(c, est, kernel);
-                        err_pose = est;
-                        temp = sums[27];
-                    } else {
-                        flags |= ORBX_POSEOPT_THETA_LIMIT;
-                        ok2 = false;
-                    }
-                    if (!ok2) temp = DBL_MAX;
-                    rho = current - temp;
-                    double scale = 0.0;
-#pragma unroll
-                    for (int j = 0; j < 6; ++j) scale = scale + x[j] * (lambda * x[j] + b[j]);
-                    scale = scale + 1e-3;
-                    rho = dv(rho, scale);
-                    if (uniform(rho > 0.0 && isfinite(temp))) {
-                        const double t = 2.0 * rho - 1.0;
-                        double alpha = 1.0 - (t * t) * t;
-                        const double up = 2.0 / 3.0, lo = 1.0 / 3.0;
-                        alpha = up < alpha ? up : alpha;
-                        lambda = lambda * (lo < alpha ? alpha : lo);
-                        ni = 2.0;
-                        current = temp;
-                    } else {
-                        lambda = lambda * ni;
-                        ni = ni * 2.0;
-                        est = backup;
-                    }
-                    ++qmax;
-                    again = uniform(rho < 0.0 && qmax < 10);
-                } while (again);
-                if (uniform(qmax == 10 || rho == 0.0)) break;
-                if ((ini - current) * 1e3 < ini) ++nbad_lm;
-                else nbad_lm = 0;
-                if (uniform(nbad_lm >= 3)) break;
-            }
-        }
+        // ---- optimize(10): nothing at level 0 -> returns at once
+        if (nactive > 0)
+            lm_optimize<6>(
+                c.S, Am, xs, lane, 10, iters, trials, flags, ORBX_POSEOPT_NONPOSITIVE_SOLVE, est,
+                [&](const Pose7& T) {
+                    evaluate<true>(c, T, kernel);
+                    err_pose = T;
+                },
+                [&](const Pose7& T) {
+                    evaluate<false>(c, T, kernel);
+                    err_pose = T;
+                },
+                [&](const double (&x)[6], Pose7& T) -> uint32_t {
+                    return uniform(pose_update(x, T)) ? 0u : (uint32_t)ORBX_POSEOPT_THETA_LIMIT;
+                });
         ++rounds;
         // ---- classification (Optimizer.cc:387-444): outliers are re-evaluated at the estimate,
         // the others keep the error of the last evaluated trial
@@ -753,14 +526,14 @@ orbx_status orbx_pose_optimization(const orbx_frame_pose* pose, const orbx_keypo
         return ORBX_ERR_INVALID;
     if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
         return ORBX_ERR_DEVICE;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_pose = 0, o_idx = al(sizeof(orbx_frame_pose)), o_keys = o_idx + 256,
-                 o_ur = o_keys + al(sizeof(orbx_keypoint) * (size_t)n),
-                 o_mpf = o_ur + (u_right ? al(4 * (size_t)n) : 0),
-                 o_mps = o_mpf + al(4 * (size_t)n),
-                 o_out = o_mps + al(sizeof(orbx_map_point) * (size_t)nmp) + 256,
-                 in_end = o_out + al((size_t)n), o_res = in_end,
-                 end = o_res + al(sizeof(orbx_frame_pose)) + 256;
+    // one staging block: the inputs, the in / out outlier bytes, then the outputs
+    Layout lay;
+    const size_t o_pose = lay.add(sizeof(orbx_frame_pose)), o_idx = lay.add(256),
+                 o_keys = lay.add(sizeof(orbx_keypoint) * (size_t)n),
+                 o_ur = lay.add(u_right ? 4 * (size_t)n : 0), o_mpf = lay.add(4 * (size_t)n),
+                 o_mps = lay.add(sizeof(orbx_map_point) * (size_t)nmp + 256),
+                 o_out = lay.add((size_t)n), o_res = lay.add(sizeof(orbx_frame_pose)),
+                 o_cnt = lay.add(256), end = lay.end;   // o_cnt: ngood, info
     std::vector<uint8_t> h(end, 0);
     std::memcpy(h.data() + o_pose, pose, sizeof(*pose));
     int32_t* idx = (int32_t*)(h.data() + o_idx);      // feat_off[2], mp_off[2]
@@ -773,19 +546,11 @@ orbx_status orbx_pose_optimization(const orbx_frame_pose* pose, const orbx_keypo
     }
     if (nmp) std::memcpy(h.data() + o_mps, mps, sizeof(orbx_map_point) * (size_t)nmp);
 
-    static std::mutex mu;
-    static DevBuf bufs[ORBX_MAX_DEVICES];          // live for the process, like its stream
-    static hipStream_t streams[ORBX_MAX_DEVICES];
-    std::lock_guard<std::mutex> lk(mu);
-    DevBuf& buf = bufs[device];
-    if (!streams[device] &&
-        !HIPOK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking)))
-        return ORBX_ERR_DEVICE;
-    if (!buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = buf.as<uint8_t>();
-    hipStream_t st = streams[device];
+    ScratchLease lease(device);
+    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    uint8_t* d = lease.s->buf.as<uint8_t>();
+    hipStream_t st = lease.s->st;
     if (!HIPOK(hipMemcpyAsync(d, h.data(), end, hipMemcpyHostToDevice, st))) return ORBX_ERR_DEVICE;
-    const size_t o_cnt = o_res + al(sizeof(orbx_frame_pose));   // ngood, info
     orbx_status s = orbx_pose_optimization_batch_device(
         (const orbx_frame_pose*)(d + o_pose), 1, (const orbx_keypoint*)(d + o_keys),
         u_right ? (const float*)(d + o_ur) : nullptr, (const int32_t*)(d + o_idx), n,

@@ -21,12 +21,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
 #include "orbx_host.h"
+#include "orbx_lm.h"
 #include "orbx_match_kernels.h"
 #include "orbx_math.h"
 
@@ -231,13 +231,6 @@ __device__ __forceinline__ void centroid(const float (*P)[3], float (*Pr)[3], fl
     }
 }
 
-// cv::gemm's small-matrix path for a 3x3 A (row-major) times a 3-vector: float products and sums
-__device__ __forceinline__ float row3(const float* A, int r, const float* b) {
-    float t = A[3 * r] * b[0];
-    t = t + A[3 * r + 1] * b[1];
-    return t + A[3 * r + 2] * b[2];
-}
-
 // ComputeSim3 (:226-337)
 __device__ __forceinline__ void compute_sim3(const float (*P1)[3], const float (*P2)[3],
                                              bool fix_scale, Sim3Hyp& H) {
@@ -379,7 +372,6 @@ struct Sim3Scratch {
     Sim3Prep* prep;
     Sim3Hyp* hyp;
 };
-__host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 __host__ __device__ inline Sim3Scratch scratch_of(void* base, int njobs, int max_n, int max_call) {
     Sim3Scratch s;
     uint8_t* p = (uint8_t*)base;
@@ -619,9 +611,7 @@ int32_t orbx_sim3_ransac_iterations(double prob, int32_t min_inliers, int32_t ma
     if (min_inliers == N) {
         nIterations = 1;
     } else {
-        const double v = ::ceil(::log(1 - prob) / ::log(1 - ::pow((double)epsilon, 3.0)));
-        // cvttsd2si: NaN and everything outside int's range give INT_MIN
-        nIterations = (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
+        nIterations = cvtt(::ceil(::log(1 - prob) / ::log(1 - ::pow((double)epsilon, 3.0))));
     }
     const int lo = nIterations < max_its ? nIterations : max_its;
     return lo > 1 ? lo : 1;
@@ -680,13 +670,14 @@ orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pos
     const int N = job->N, mN1 = job->mN1, max_its = job->max_its;
     const int max_call = job->n_iterations < max_its ? job->n_iterations : max_its;
     // one staging block: the inputs, the in / out state, then the outputs and the scratch
-    const size_t o_pose = 0, o_job = al256(2 * sizeof(orbx_frame_pose)),
-                 o_corr = o_job + al256(sizeof(orbx_sim3_job)),
-                 o_tri = o_corr + al256(sizeof(orbx_sim3_corr) * (size_t)N),
-                 o_state = o_tri + al256(12 * (size_t)max_its), in_end = o_state + 256,
-                 o_res = in_end, o_inl = o_res + al256(sizeof(orbx_sim3_result)),
-                 out_end = o_inl + al256((size_t)mN1), o_scratch = out_end,
-                 end = o_scratch + sim3_scratch_bytes(1, N, max_call);
+    Layout lay;
+    const size_t o_pose = lay.add(2 * sizeof(orbx_frame_pose)),
+                 o_job = lay.add(sizeof(orbx_sim3_job)),
+                 o_corr = lay.add(sizeof(orbx_sim3_corr) * (size_t)N),
+                 o_tri = lay.add(12 * (size_t)max_its), o_state = lay.add(256),
+                 o_res = lay.add(sizeof(orbx_sim3_result)), o_inl = lay.add((size_t)mN1),
+                 out_end = lay.end, o_scratch = lay.add(sim3_scratch_bytes(1, N, max_call)),
+                 end = lay.end;
     std::vector<uint8_t> h(out_end, 0);
     std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
     std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
@@ -700,17 +691,10 @@ orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pos
     std::memcpy(h.data() + o_res, res, sizeof(*res));
     if (mN1) std::memcpy(h.data() + o_inl, inliers, (size_t)mN1);
 
-    static std::mutex mu;
-    static DevBuf bufs[ORBX_MAX_DEVICES];          // live for the process, like its stream
-    static hipStream_t streams[ORBX_MAX_DEVICES];
-    std::lock_guard<std::mutex> lk(mu);
-    DevBuf& buf = bufs[device];
-    if (!streams[device] &&
-        !HIPOK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking)))
-        return ORBX_ERR_DEVICE;
-    if (!buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = buf.as<uint8_t>();
-    hipStream_t st = streams[device];
+    ScratchLease lease(device);
+    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    uint8_t* d = lease.s->buf.as<uint8_t>();
+    hipStream_t st = lease.s->st;
     if (!HIPOK(hipMemcpyAsync(d, h.data(), out_end, hipMemcpyHostToDevice, st)))
         return ORBX_ERR_DEVICE;
     Sim3Launch L{};

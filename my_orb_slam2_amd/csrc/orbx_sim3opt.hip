@@ -18,11 +18,11 @@
 // stored: it is a function of the estimate it was last evaluated at, and that estimate is kept
 // instead (g2o does not recompute errors after a rejected trial).
 //
-// Forms evaluated inside Eigen (quaternion from a matrix, rotation of a vector, quaternion and
-// small matrix products, LDLT) are restated from the published algorithms [unverified-Eigen]
-// (DESIGN.md §2).  sin / cos / exp are orbx_math.h's.  Built with -ffp-contract=off like the rest
-// of the library.  The few helpers shared with orbx_poseopt.hip are duplicated here, so that
-// k_pose_opt's generated code stays as it is.
+// The forms evaluated inside Eigen, the robust kernel and the LDLT are orbx_lm.h's, shared with
+// k_pose_opt; the edge model (s3_*, the perturbed estimates, the numeric Jacobian) is here.  The
+// Levenberg loop (optimize) is written out: over orbx_lm.h's lm_optimize<7> the kernel measured
+// 4 % slower (profiles/lm_share_ab.txt).  sin / cos / exp are orbx_math.h's.  Built with
+// -ffp-contract=off like the rest of the library.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -30,12 +30,12 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
 #include "orbx_host.h"
+#include "orbx_lm.h"
 #include "orbx_match_kernels.h"
 #include "orbx_math.h"
 
@@ -56,62 +56,6 @@ static_assert(SIM3OPT_MAX_N <= 64 * 64, "one dropped bit per chunk in a 64-bit w
 
 struct S3 { double qx, qy, qz, qw, tx, ty, tz, s; };
 struct Cam2 { double fx, fy, cx, cy; };
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ bool uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-// IEEE division and square root whatever the compiler's defaults
-__device__ __forceinline__ double dv(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ double sq(double a) { return __dsqrt_rn(a); }
-
-// Eigen's Quaternion(Matrix3) for one position of the largest diagonal entry
-template <int I>
-__device__ __forceinline__ void quat_branch(const double (&R)[3][3], double (&c)[3], double& w) {
-    constexpr int J = (I + 1) % 3, K = (J + 1) % 3;
-    double t = sq(((R[I][I] - R[J][J]) - R[K][K]) + 1.0);
-    c[I] = 0.5 * t;
-    t = dv(0.5, t);
-    w = (R[K][J] - R[J][K]) * t;
-    c[J] = (R[J][I] + R[I][J]) * t;
-    c[K] = (R[K][I] + R[I][K]) * t;
-}
-
-// Quaterniond(Matrix3d) as g2o::Sim3 keeps it: not normalised afterwards (sim3.h:64-66, :136)
-__device__ __forceinline__ void quat_from_matrix_raw(const double (&R)[3][3], double& x, double& y,
-                                                     double& z, double& w) {
-    double t = (R[0][0] + R[1][1]) + R[2][2];
-    if (t > 0.0) {
-        t = sq(t + 1.0);
-        w = 0.5 * t;
-        t = dv(0.5, t);
-        x = (R[2][1] - R[1][2]) * t;
-        y = (R[0][2] - R[2][0]) * t;
-        z = (R[1][0] - R[0][1]) * t;
-    } else {
-        double c[3];
-        const bool one = R[1][1] > R[0][0];
-        const bool two = R[2][2] > (one ? R[1][1] : R[0][0]);
-        if (two) quat_branch<2>(R, c, w);
-        else if (one) quat_branch<1>(R, c, w);
-        else quat_branch<0>(R, c, w);
-        x = c[0], y = c[1], z = c[2];
-    }
-}
-
-// Eigen's Quaternion * Vector3: v + w*(2 q x v) + q x (2 q x v)
-__device__ __forceinline__ void quat_rotate(double qx, double qy, double qz, double qw, double px,
-                                            double py, double pz, double& ox, double& oy,
-                                            double& oz) {
-    double ux = qy * pz - qz * py, uy = qz * px - qx * pz, uz = qx * py - qy * px;
-    ux = ux + ux, uy = uy + uy, uz = uz + uz;
-    const double cx = qy * uz - qz * uy, cy = qz * ux - qx * uz, cz = qx * uy - qy * ux;
-    ox = (px + qw * ux) + cx;
-    oy = (py + qw * uy) + cy;
-    oz = (pz + qw * uz) + cz;
-}
 
 // Sim3::map (sim3.h:144-146)
 __device__ __forceinline__ void s3_map(const S3& S, double px, double py, double pz, double& x,
@@ -134,10 +78,7 @@ __device__ __forceinline__ S3 s3_inverse(const S3& S) {
 // Sim3::operator* (sim3.h:266-272): the quaternion product is not normalised
 __device__ __forceinline__ S3 s3_mul(const S3& A, const S3& B) {
     S3 N;
-    N.qw = ((A.qw * B.qw - A.qx * B.qx) - A.qy * B.qy) - A.qz * B.qz;
-    N.qx = ((A.qw * B.qx + A.qx * B.qw) + A.qy * B.qz) - A.qz * B.qy;
-    N.qy = ((A.qw * B.qy + A.qy * B.qw) + A.qz * B.qx) - A.qx * B.qz;
-    N.qz = ((A.qw * B.qz + A.qz * B.qw) + A.qx * B.qy) - A.qy * B.qx;
+    quat_mul(A.qx, A.qy, A.qz, A.qw, B.qx, B.qy, B.qz, B.qw, N.qx, N.qy, N.qz, N.qw);
     double rx, ry, rz;
     quat_rotate(A.qx, A.qy, A.qz, A.qw, B.tx, B.ty, B.tz, rx, ry, rz);
     N.tx = A.s * rx + A.tx, N.ty = A.s * ry + A.ty, N.tz = A.s * rz + A.tz;
@@ -197,7 +138,7 @@ __device__ __forceinline__ uint32_t s3_exp(const double (&u)[7], S3& E) {
             R[i][j] = tsmall ? (e + O[i][j]) + o2 : (e + ra * O[i][j]) + rb * o2;
             W[i][j] = (A * O[i][j] + B * o2) + C * e;
         }
-    quat_from_matrix_raw(R, E.qx, E.qy, E.qz, E.qw);
+    quat_from_matrix(R, E.qx, E.qy, E.qz, E.qw);
     E.tx = (W[0][0] * u[3] + W[0][1] * u[4]) + W[0][2] * u[5];
     E.ty = (W[1][0] * u[3] + W[1][1] * u[4]) + W[1][2] * u[5];
     E.tz = (W[2][0] * u[3] + W[2][1] * u[4]) + W[2][2] * u[5];
@@ -217,118 +158,6 @@ __device__ __forceinline__ void edge_error(const S3& S, const double (&X)[3], co
 // chi2 (base_edge.h:60) with information = info * I
 __device__ __forceinline__ double edge_chi2(const double (&err)[2], double info) {
     return err[0] * (info * err[0]) + err[1] * (info * err[1]);
-}
-
-// RobustKernelHuber::robustify: rho and rho'
-__device__ __forceinline__ void huber(double e2, double delta, double& rho0, double& rho1) {
-    const double dsqr = delta * delta;
-    if (e2 <= dsqr) {
-        rho0 = e2;
-        rho1 = 1.0;
-    } else {
-        const double se = sq(e2);
-        rho0 = (2.0 * se) * delta - dsqr;
-        rho1 = dv(delta, se);
-    }
-}
-
-// Eigen::LDLT<MatrixXd>::compute + solve on the lower triangle of the 7x7 at A (row-major, LDS),
-// b -> x [unverified-Eigen]; false: not positive (x is left as it is).  Runs on one lane.
-__device__ __forceinline__ bool ldlt7_solve_lds(double* A, const double* b, double* x) {
-    constexpr int N = 7;
-    int* trl = (int*)(x + N);             // N ints behind x: the transpositions, indexed freely
-    int sign = 0;                         // 0 zero, 1 positive, -1 negative, 2 indefinite
-    for (int k = 0; k < N; ++k) {
-        int idx = k;
-        double best = fabs(A[(N + 1) * k]);
-        for (int i = k + 1; i < N; ++i) {
-            const double v = fabs(A[(N + 1) * i]);
-            if (v > best) best = v, idx = i;
-        }
-        trl[k] = idx;
-        if (idx != k) {
-            for (int j = 0; j < k; ++j) {
-                const double t = A[N * k + j];
-                A[N * k + j] = A[N * idx + j];
-                A[N * idx + j] = t;
-            }
-            for (int i = idx + 1; i < N; ++i) {
-                const double t = A[N * i + k];
-                A[N * i + k] = A[N * i + idx];
-                A[N * i + idx] = t;
-            }
-            {
-                const double t = A[(N + 1) * k];
-                A[(N + 1) * k] = A[(N + 1) * idx];
-                A[(N + 1) * idx] = t;
-            }
-            for (int i = k + 1; i < idx; ++i) {
-                const double t = A[N * i + k];
-                A[N * i + k] = A[N * idx + i];
-                A[N * idx + i] = t;
-            }
-        }
-        if (k > 0) {
-            double* temp = A + N * N;   // D * A10^T
-            for (int j = 0; j < k; ++j) temp[j] = A[(N + 1) * j] * A[N * k + j];
-            double s = A[N * k] * temp[0];
-            for (int j = 1; j < k; ++j) s = s + A[N * k + j] * temp[j];
-            A[(N + 1) * k] = A[(N + 1) * k] - s;
-            for (int i = k + 1; i < N; ++i) {
-                double si = A[N * i] * temp[0];
-                for (int j = 1; j < k; ++j) si = si + A[N * i + j] * temp[j];
-                A[N * i + k] = A[N * i + k] - si;
-            }
-        }
-        const double akk = A[(N + 1) * k];
-        const bool valid = fabs(akk) > 0.0;
-        if (k == 0 && !valid) {
-            for (int j = 0; j < N; ++j) trl[j] = j;
-            break;
-        }
-        if (valid)
-            for (int i = k + 1; i < N; ++i) A[N * i + k] = dv(A[N * i + k], akk);
-        if (sign == 1) {
-            if (akk < 0.0) sign = 2;
-        } else if (sign == -1) {
-            if (akk > 0.0) sign = 2;
-        } else if (sign == 0) {
-            if (akk > 0.0) sign = 1;
-            else if (akk < 0.0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double* y = A + N * N + N;
-    for (int i = 0; i < N; ++i) y[i] = b[i];
-    for (int k = 0; k < N; ++k) {
-        const int o = trl[k];
-        const double t = y[k];
-        y[k] = y[o];
-        y[o] = t;
-    }
-    for (int j = 0; j < N; ++j)
-        for (int i = j + 1; i < N; ++i) y[i] = y[i] - A[N * i + j] * y[j];
-    for (int i = 0; i < N; ++i) y[i] = fabs(A[(N + 1) * i]) > DBL_MIN ? dv(y[i], A[(N + 1) * i]) : 0.0;
-    for (int i = N - 2; i >= 0; --i) {
-        double s = A[N * (i + 1) + i] * y[i + 1];
-        for (int j = i + 2; j < N; ++j) s = s + A[N * j + i] * y[j];
-        y[i] = y[i] - s;
-    }
-    for (int k = N - 1; k >= 0; --k) {
-        const int o = trl[k];
-        const double t = y[k];
-        y[k] = y[o];
-        y[o] = t;
-    }
-    for (int i = 0; i < N; ++i) x[i] = y[i];
-    return true;
-}
-
-// cv::gemm's small-matrix path for a 3x3 A (row-major) times a 3-vector: float products and sums
-__device__ __forceinline__ float row3(const float* A, int r, const float* b) {
-    float t = A[3 * r] * b[0];
-    t = t + A[3 * r + 1] * b[1];
-    return t + A[3 * r + 2] * b[2];
 }
 
 // One correspondence's two edges as the lane holds them
@@ -486,7 +315,8 @@ __device__ __forceinline__ void evaluate(const JobCtx& c, const S3& E, unsigned 
 struct LmCount { uint32_t iters, trials, flags; };
 
 // SparseOptimizer::optimize(max_iter) with OptimizationAlgorithmLevenberg::solve from est, every
-// call with a fresh Levenberg state; err_est: the estimate the edges' errors belong to afterwards
+// call with a fresh Levenberg state (orbx_lm.h's lm_optimize at N = 7, with s3_exp's refusals and
+// fix_scale in the step); err_est: the estimate the edges' errors belong to afterwards
 __device__ __forceinline__ void optimize(const JobCtx& c, int max_iter, unsigned long long dropped,
                                          S3& est, S3& err_est, LmCount& n) {
     double* sums = c.S;                    // [36]
@@ -529,7 +359,7 @@ __device__ __forceinline__ void optimize(const JobCtx& c, int max_iter, unsigned
                 for (int r = 0; r < 7; ++r)
                     for (int q = 0; q < 7; ++q)
                         Am[7 * r + q] = q < r ? sums[o++] : q == r ? sums[o++] + lambda : 0.0;
-                const bool ok = ldlt7_solve_lds(Am, sums + 28, xs);
+                const bool ok = ldlt_solve_lds<7>(Am, sums + 28, xs);
                 ((int*)(xs + 7))[7] = ok ? 1 : 0;
             }
             wave_sync();
@@ -627,7 +457,7 @@ __global__ __launch_bounds__(64 * SO_WAVES) void k_sim3_opt(const Sim3OptLaunch 
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int q = 0; q < 3; ++q) R[r][q] = (double)in.R12[3 * r + q];
-        quat_from_matrix_raw(R, start.qx, start.qy, start.qz, start.qw);
+        quat_from_matrix(R, start.qx, start.qy, start.qz, start.qw);
         start.tx = (double)in.t12[0], start.ty = (double)in.t12[1], start.tz = (double)in.t12[2];
         start.s = (double)in.s12;
     }
@@ -763,13 +593,13 @@ orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_po
     if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
         return ORBX_ERR_DEVICE;
     const int N = job->N, mN1 = job->mN1;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     // one staging block: the inputs, then the outputs
-    const size_t o_pose = 0, o_job = al(2 * sizeof(orbx_frame_pose)),
-                 o_in = o_job + al(sizeof(orbx_sim3opt_job)),
-                 o_corr = o_in + al(sizeof(orbx_sim3opt_in)),
-                 o_res = o_corr + al(sizeof(orbx_sim3opt_corr) * (size_t)N),
-                 o_keep = o_res + al(sizeof(orbx_sim3opt_result)), end = o_keep + al((size_t)mN1);
+    Layout lay;
+    const size_t o_pose = lay.add(2 * sizeof(orbx_frame_pose)),
+                 o_job = lay.add(sizeof(orbx_sim3opt_job)), o_in = lay.add(sizeof(orbx_sim3opt_in)),
+                 o_corr = lay.add(sizeof(orbx_sim3opt_corr) * (size_t)N),
+                 o_res = lay.add(sizeof(orbx_sim3opt_result)), o_keep = lay.add((size_t)mN1),
+                 end = lay.end;
     std::vector<uint8_t> h(end, 0);
     std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
     std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
@@ -780,17 +610,10 @@ orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_po
     if (N) std::memcpy(h.data() + o_corr, corr, sizeof(orbx_sim3opt_corr) * (size_t)N);
     if (mN1) std::memcpy(h.data() + o_keep, keep, (size_t)mN1);
 
-    static std::mutex mu;
-    static DevBuf bufs[ORBX_MAX_DEVICES];          // live for the process, like its stream
-    static hipStream_t streams[ORBX_MAX_DEVICES];
-    std::lock_guard<std::mutex> lk(mu);
-    DevBuf& buf = bufs[device];
-    if (!streams[device] &&
-        !HIPOK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking)))
-        return ORBX_ERR_DEVICE;
-    if (!buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = buf.as<uint8_t>();
-    hipStream_t st = streams[device];
+    ScratchLease lease(device);
+    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    uint8_t* d = lease.s->buf.as<uint8_t>();
+    hipStream_t st = lease.s->st;
     if (!HIPOK(hipMemcpyAsync(d, h.data(), end, hipMemcpyHostToDevice, st))) return ORBX_ERR_DEVICE;
     Sim3OptLaunch L{};
     L.jobs = (const orbx_sim3opt_job*)(d + o_job);

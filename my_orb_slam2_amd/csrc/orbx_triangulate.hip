@@ -17,7 +17,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
 #include "../../include/orbx_frame.h"
@@ -421,14 +420,14 @@ orbx_status orbx_triangulate_matches(
     // one staging block: every input, then the outputs
     const size_t n = (size_t)n1 + (size_t)n2;
     const bool raw = keys_raw1 || keys_raw2, stereo = u_right1 || u_right2;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_pose = 0, o_idx = al(2 * sizeof(orbx_frame_pose)), o_keys = o_idx + 256,
-                 o_raw = o_keys + al(sizeof(orbx_keypoint) * n),
-                 o_ur = o_raw + (raw ? al(sizeof(orbx_keypoint) * n) : 0),
-                 o_depth = o_ur + (stereo ? al(4 * n) : 0), o_cos = o_depth + al(4 * n),
-                 o_match = o_cos + al(4 * n), in_end = o_match + al(4 * (size_t)n1),
-                 o_cnt = in_end, o_status = o_cnt + 256, o_x3d = o_status + al(4 * (size_t)n1),
-                 end = o_x3d + al(12 * (size_t)n1);
+    Layout lay;
+    const size_t o_pose = lay.add(2 * sizeof(orbx_frame_pose)), o_idx = lay.add(256),
+                 o_keys = lay.add(sizeof(orbx_keypoint) * n),
+                 o_raw = lay.add(raw ? sizeof(orbx_keypoint) * n : 0),
+                 o_ur = lay.add(stereo ? 4 * n : 0), o_depth = lay.add(4 * n),
+                 o_cos = lay.add(4 * n), o_match = lay.add(4 * (size_t)n1), in_end = lay.end,
+                 o_cnt = lay.add(256), o_status = lay.add(4 * (size_t)n1),
+                 o_x3d = lay.add(12 * (size_t)n1), end = lay.end;
     std::vector<uint8_t> h(end, 0);
     std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
     std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
@@ -453,17 +452,10 @@ orbx_status orbx_triangulate_matches(
     else if (depth2) orbx_parallax_stereo_cos(mb, depth2, n2, cs + n1);
     if (n1) std::memcpy(h.data() + o_match, match12.data(), 4 * (size_t)n1);
 
-    static std::mutex mu;
-    static DevBuf bufs[ORBX_MAX_DEVICES];          // live for the process, like its stream
-    static hipStream_t streams[ORBX_MAX_DEVICES];
-    std::lock_guard<std::mutex> lk(mu);
-    DevBuf& buf = bufs[device];
-    if (!streams[device] &&
-        !HIPOK(hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking)))
-        return ORBX_ERR_DEVICE;
-    if (!buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = buf.as<uint8_t>();
-    hipStream_t st = streams[device];
+    ScratchLease lease(device);
+    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
+    uint8_t* d = lease.s->buf.as<uint8_t>();
+    hipStream_t st = lease.s->st;
     if (!HIPOK(hipMemcpyAsync(d, h.data(), in_end + 256, hipMemcpyHostToDevice, st)))
         return ORBX_ERR_DEVICE;
     TriPointsLaunch L{};

@@ -296,3 +296,126 @@ def test_capture_beside_cross_stream_wait(orbx_lib, gpu):
         assert_bytes_equal(out["l"][1], ref[nxt][0][1], f"left desc it {it}")
         assert_kps_equal(out["r"][0], ref[it % 4][1][0], f"right it {it}")
         assert_bytes_equal(out["r"][1], ref[it % 4][1][1], f"right desc it {it}")
+
+
+def _host_array_calls():
+    """The five host-array solver entry points, each on its smallest committed directed case that
+    runs at least one full iteration: name -> a function that makes the case's call(s) from fresh
+    inputs and returns every array and record that comes back, as bytes, ahead of a count of the
+    iterations the call ran."""
+    import pnp_cases
+    import poseopt_cases
+    import sim3_cases
+    import sim3opt_cases
+    import triangulate_cases
+    from my_orb_slam2_amd import triangulate_matches
+    from my_orb_slam2_amd.features import pose_optimization
+    from my_orb_slam2_amd.pnp import (PNP_RESULT_DTYPE, PNP_STATE_DTYPE, pnp_iterate,
+                                      pnp_ransac_parameters, pnp_sample_quads)
+    from my_orb_slam2_amd.sim3 import (SIM3_RESULT_DTYPE, SIM3_STATE_DTYPE, sim3_iterate,
+                                       sim3_optimize, sim3_ransac_iterations, sim3_sample_triples)
+
+    def poseopt():      # three edges: the fewest PoseOptimization takes
+        c = poseopt_cases.case_named("count_3_mono")
+        pose, flag, ngood, info = pose_optimization(c["pose"], c["keys"], c["mp_of_feat"], c["mps"],
+                                                    c["ur"], c["outlier_in"])
+        return (poseopt_cases.info_fields(info)["iters"], pose.tobytes(), flag.tobytes(), ngood,
+                info)
+
+    def sim3opt():      # one correspondence: two edges
+        c = sim3opt_cases.case_named("count_1_free")
+        res, keep = sim3_optimize(c["pose1"], c["pose2"], sim3opt_cases.job_record(c), c["corr"],
+                                  c["sim3_in"], c["keep_in"])
+        return (sim3opt_cases.info_fields(res["info"])["iters"], res.tobytes(), keep.tobytes())
+
+    def sim3():         # three correspondences: the one triple
+        c = sim3_cases.case_named("random_3")
+        N = len(c["corr"])
+        max_its = sim3_ransac_iterations(c["prob"], c["min_inliers"], c["max_iterations"], N)
+        tri = sim3_sample_triples(N, c["rand"][:3 * max_its])
+        state = np.zeros(1, SIM3_STATE_DTYPE)
+        state["iterations"], state["best_inliers"] = c["state0"]
+        out = []
+        for n_it in c["calls"]:
+            res = np.zeros(1, SIM3_RESULT_DTYPE)
+            inl = np.zeros(c["mN1"], np.uint8)
+            sim3_iterate(c["pose1"], c["pose2"], sim3_cases.job_of(c, max_its, n_it), c["corr"],
+                         tri, state, res, inl)
+            out += [res.tobytes(), inl.tobytes(), state.tobytes()]
+        return (int(state["iterations"][0]), *out)
+
+    def pnp():          # four correspondences: the one minimal set
+        c = pnp_cases.case_named("n_is_4")
+        N = len(c["corr"])
+        mi, mx = pnp_ransac_parameters(c["prob"], c["min_inliers"], c["max_iterations"], 4,
+                                       c["epsilon"], N)
+        q = pnp_sample_quads(N, c["rand"])
+        for k, v in c["quad_edits"].items():
+            q[k] = v
+        state = np.zeros(1, PNP_STATE_DTYPE)
+        state["iterations"], state["best_inliers"] = c["state0"]
+        state["best_Tcw"] = c["best_Tcw0"]
+        best = c["best0"].copy()
+        out = []
+        for n_it in c["calls"]:
+            res = np.zeros(1, PNP_RESULT_DTYPE)
+            inl = np.zeros(c["n_matches"], np.uint8)
+            pnp_iterate(pnp_cases.job_of(c, mi, mx, n_it), c["corr"], q, state, best, res, inl)
+            out += [res.tobytes(), inl.tobytes(), state.tobytes(), best.tobytes()]
+        return (int(state["iterations"][0]), *out)
+
+    def triangulate():  # two pairs, both triangulated
+        c = triangulate_cases.case_named("far_st01")
+        st, x, nnew = triangulate_matches(
+            c["pose1"], c["pose2"], c["keys1"], c["keys2"], c["pairs"], c["ratio_factor"],
+            mb=c["mb"], u_right1=c["ur1"], u_right2=c["ur2"], depth1=c["depth1"],
+            depth2=c["depth2"], keys_raw1=c["raw1"], keys_raw2=c["raw2"], cos_stereo1=c["cos1"],
+            cos_stereo2=c["cos2"])
+        return (nnew, st.tobytes(), x.tobytes())
+
+    return dict(poseopt=poseopt, sim3opt=sim3opt, sim3=sim3, pnp=pnp, triangulate=triangulate)
+
+
+HOST_ARRAY_ENTRY_POINTS = ("poseopt", "sim3opt", "sim3", "pnp", "triangulate")
+
+
+@pytest.fixture(scope="module")
+def host_array_serial(orbx_lib, gpu):
+    """Every entry point's call made alone, first: what the threads' results must equal."""
+    calls = _host_array_calls()
+    serial = {name: calls[name]() for name in HOST_ARRAY_ENTRY_POINTS}
+    for name, r in serial.items():
+        assert r[0] >= 1, (name, "the case runs no iteration")
+    return calls, serial
+
+
+@pytest.mark.parametrize("name", HOST_ARRAY_ENTRY_POINTS)
+def test_host_array_solver_threads_equal_serial(host_array_serial, name):
+    """orbx_pose_optimization, orbx_sim3_optimize, orbx_sim3_iterate, orbx_pnp_iterate and
+    orbx_triangulate_matches stage through a leased (stream, buffer) slot each (orbx_host.h,
+    ScratchLease), so calls of one entry point from several threads run beside each other: four
+    threads leave a barrier together and call it three times each on the same case while a fifth
+    calls another entry point.  Every array and record equals the serial call's, byte for byte."""
+    calls, serial = host_array_serial
+    other = HOST_ARRAY_ENTRY_POINTS[(HOST_ARRAY_ENTRY_POINTS.index(name) + 1) % 5]
+    barrier = threading.Barrier(5)
+    got, errors = [], []
+
+    def worker(which):
+        try:
+            barrier.wait()
+            for _ in range(3):
+                got.append((which, calls[which]()))
+        except Exception as e:   # pragma: no cover - reported below
+            errors.append((which, repr(e)))
+            barrier.abort()
+
+    ths = [threading.Thread(target=worker, args=(n,)) for n in (name,) * 4 + (other,)]
+    for t in ths:
+        t.start()
+    for t in ths:
+        t.join()
+    assert not errors, errors
+    assert sorted(w for w, _ in got) == sorted([name] * 12 + [other] * 3)
+    for which, r in got:
+        assert r == serial[which], which
