@@ -24,9 +24,10 @@ LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
            "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
-           "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip", "orbx_pnp.hip"]
+           "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip", "orbx_pnp.hip",
+           "orbx_host.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
-           "orbx_host.h", "orbx_lm.h", "orbx_match_kernels.h", "orbx_pattern.inc",
+           "orbx_host.h", "orbx_stage.h", "orbx_lm.h", "orbx_match_kernels.h", "orbx_pattern.inc",
            "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
            "../../include/orbx_frame.h", "../../include/orbx_kfdb.h"]
 HASH_TAG = b"orbx-src:"
@@ -301,3 +302,15 @@ def build_pnp_ref(force: bool = False, verbose: bool = False, sanitize: bool = F
     return _build_native(PNP_REF_SRC, _sanitized(sanitize, out, PNP_REF_BIN), _headers(INCLUDE),
                          [INCLUDE], extra=SANITIZE if sanitize else (), force=force,
                          verbose=verbose)
+
+
+# the staging plan of the host-array entry points, on its own
+STAGING_SRC = NATIVE / "staging_test.cpp"
+STAGING_BIN = NATIVE / "staging_test"
+
+
+def build_staging_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on csrc/orbx_stage.h only, with -fsanitize=address,undefined: no HIP, no liborbx and no
+    GPU."""
+    return _build_native(STAGING_SRC, STAGING_BIN, [CSRC / "orbx_stage.h"], [CSRC], extra=SANITIZE,
+                         force=force, verbose=verbose)

@@ -41,15 +41,6 @@ using namespace orbx;
 
 #include "orbx_host.h"
 
-namespace orbx {
-thread_local char g_err[256] = "";
-bool hip_ok(hipError_t e, const char* what) {
-    if (e == hipSuccess) return true;
-    snprintf(g_err, sizeof(g_err), "%s: %s (%d)", what, hipGetErrorString(e), (int)e);
-    return false;
-}
-}  // namespace orbx
-
 // A helper thread that stages the right image of a stereo frame while the calling thread
 // stages the left one (orbx_stereo_frame_view): the copy of a cold 0.47 MB image into pinned
 // memory is tens of microseconds on one core.

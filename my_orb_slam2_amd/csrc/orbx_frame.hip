@@ -23,7 +23,6 @@
 #include <cstdint>
 #include <cstring>
 #include <mutex>
-#include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "orbx_device.h"
@@ -660,37 +659,7 @@ int depth_scales(int type, float factor) {
     return type != ORBX_DEPTH_F32 || std::fabs(factor - 1.0f) > 1e-5;
 }
 
-// The pool behind ScratchLease (orbx_host.h): the slots no call holds at the moment.
-std::mutex g_scratch_mu;
-std::vector<Scratch*> g_scratch_free;
-
 }  // namespace
-
-orbx::ScratchLease::ScratchLease(int device) {
-    {
-        std::lock_guard<std::mutex> lk(g_scratch_mu);
-        for (size_t i = 0; i < g_scratch_free.size(); ++i)
-            if (g_scratch_free[i]->device == device) {
-                s = g_scratch_free[i];
-                g_scratch_free.erase(g_scratch_free.begin() + i);
-                break;
-            }
-    }
-    if (!s) {
-        Scratch* n = new Scratch();
-        n->device = device;
-        if (!HIPOK(hipStreamCreateWithFlags(&n->st, hipStreamNonBlocking))) {
-            delete n;
-            return;
-        }
-        s = n;
-    }
-}
-orbx::ScratchLease::~ScratchLease() {
-    if (!s) return;
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    g_scratch_free.push_back(s);   // slots live for the process (no teardown-order hazards)
-}
 
 extern "C" {
 
@@ -714,24 +683,19 @@ orbx_status orbx_cvt_color(const uint8_t* src, int32_t width, int32_t height, si
     if (width == 0 || height == 0) return ORBX_OK;
     if (!src || !dst || src_stride < (size_t)width * channels || dst_stride < (size_t)width)
         return ORBX_ERR_INVALID;
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    const size_t sb = (size_t)width * channels * height, db = (size_t)width * height;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(sb + db)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    uint8_t* ds = L.s->buf.as<uint8_t>();
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipMemcpy2DAsync(ds, (size_t)width * channels, src, src_stride,
-                                (size_t)width * channels, height, hipMemcpyHostToDevice, st)))
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    const size_t row = (size_t)width * channels;
+    const size_t p_src = c.plan().scratch(row * height), p_dst = c.plan().scratch((size_t)width * height);
+    if (!c.upload() || !HIPOK(hipMemcpy2DAsync(c.dev<uint8_t>(p_src), row, src, src_stride, row,
+                                               height, hipMemcpyHostToDevice, c.st())))
+        return c.finish(ORBX_ERR_DEVICE);
+    orbx_status s = orbx_cvt_color_device(c.dev<uint8_t>(p_src), width, height, row, channels, rgb,
+                                          c.dev<uint8_t>(p_dst), width, c.st());
+    if (s == ORBX_OK && !HIPOK(hipMemcpy2DAsync(dst, dst_stride, c.dev<uint8_t>(p_dst), width,
+                                                width, height, hipMemcpyDeviceToHost, c.st())))
         s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_cvt_color_device(ds, width, height, (size_t)width * channels, channels, rgb,
-                                  ds + sb, width, st);
-    if (s == ORBX_OK && !HIPOK(hipMemcpy2DAsync(dst, dst_stride, ds + sb, width, width, height,
-                                                hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    return s;
+    return c.finish(s);
 }
 
 orbx_status orbx_undistort_keypoints_device(const float* K4, const float* dist, int32_t ndist,
@@ -754,19 +718,13 @@ orbx_status orbx_undistort_keypoints(const float* K4, const float* dist, int32_t
     if (!make_params(K4, dist, ndist, P) || n < 0 || (n > 0 && (!kps || !kps_un)))
         return ORBX_ERR_INVALID;
     if (n == 0) return ORBX_OK;
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
     const size_t bytes = sizeof(orbx_keypoint) * (size_t)n;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(bytes)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    orbx_keypoint* d = L.s->buf.as<orbx_keypoint>();
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipMemcpyAsync(d, kps, bytes, hipMemcpyHostToDevice, st))) s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK) s = orbx_undistort_keypoints_device(K4, dist, ndist, d, n, d, st);
-    if (s == ORBX_OK && !HIPOK(hipMemcpyAsync(kps_un, d, bytes, hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    return s;
+    const size_t p_k = c.plan().in(kps, bytes), p_un = c.plan().out(kps_un, bytes);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_undistort_keypoints_device(K4, dist, ndist, c.dev<orbx_keypoint>(p_k), n,
+                                                    c.dev<orbx_keypoint>(p_un), c.st()));
 }
 
 orbx_status orbx_image_bounds(const float* K4, const float* dist, int32_t ndist, int32_t width,
@@ -865,38 +823,19 @@ orbx_status orbx_is_in_frustum(const orbx_frame_pose* frame, const orbx_map_poin
         if (nvisible) *nvisible = 0;
         return ORBX_OK;
     }
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_f = 0, o_off = al(sizeof(orbx_frame_pose)), o_cnt = o_off + 256,
-                 o_mp = o_cnt + 256, o_sk = o_mp + al(sizeof(orbx_map_point) * (size_t)n),
-                 o_q = o_sk + al((size_t)n), end = o_q + sizeof(orbx_proj_query) * (size_t)n;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    uint8_t* d = L.s->buf.as<uint8_t>();
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const int32_t off[2] = {0, n};
-    int32_t cnt = 0;
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipMemcpyAsync(d + o_f, frame, sizeof(*frame), hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_off, off, sizeof(off), hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_mp, mps, sizeof(orbx_map_point) * (size_t)n,
-                              hipMemcpyHostToDevice, st)) ||
-        (skip && !HIPOK(hipMemcpyAsync(d + o_sk, skip, (size_t)n, hipMemcpyHostToDevice, st))))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_is_in_frustum_batch_device((const orbx_frame_pose*)(d + o_f), 1,
-                                            (const orbx_map_point*)(d + o_mp),
-                                            (const int32_t*)(d + o_off), n,
-                                            skip ? d + o_sk : nullptr, viewing_cos_limit, th,
-                                            (orbx_proj_query*)(d + o_q), (int32_t*)(d + o_cnt), st);
-    if (s == ORBX_OK &&
-        (!HIPOK(hipMemcpyAsync(q, d + o_q, sizeof(orbx_proj_query) * (size_t)n,
-                               hipMemcpyDeviceToHost, st)) ||
-         !HIPOK(hipMemcpyAsync(&cnt, d + o_cnt, 4, hipMemcpyDeviceToHost, st))))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK && nvisible) *nvisible = cnt;
-    return s;
+    const size_t p_f = p.in(frame, sizeof(*frame)), p_off = p.in(off, sizeof(off)),
+                 p_mp = p.in(mps, sizeof(orbx_map_point) * (size_t)n),
+                 p_sk = p.in_opt(skip, (size_t)n),
+                 p_q = p.out(q, sizeof(orbx_proj_query) * (size_t)n), p_cnt = p.out(nvisible, 4);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_is_in_frustum_batch_device(
+        c.dev<orbx_frame_pose>(p_f), 1, c.dev<orbx_map_point>(p_mp), c.dev<int32_t>(p_off), n,
+        c.dev<uint8_t>(p_sk), viewing_cos_limit, th, c.dev<orbx_proj_query>(p_q),
+        c.dev<int32_t>(p_cnt), c.st()));
 }
 
 orbx_status orbx_project_map_points_batch_device(
@@ -947,41 +886,20 @@ orbx_status orbx_project_map_points(int32_t mode, const orbx_proj_job* job,
         if (nactive) *nactive = 0;
         return ORBX_OK;
     }
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_j = 0, o_off = al(sizeof(orbx_proj_job)), o_cnt = o_off + 256,
-                 o_mp = o_cnt + 256, o_sk = o_mp + al(sizeof(orbx_map_point) * (size_t)n),
-                 o_k = o_sk + al((size_t)n),
-                 o_q = o_k + (keyed ? al(sizeof(orbx_keypoint) * (size_t)n) : 0),
-                 end = o_q + sizeof(orbx_proj_query) * (size_t)n;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    uint8_t* d = L.s->buf.as<uint8_t>();
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const int32_t off[2] = {0, n};
-    int32_t cnt = 0;
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipMemcpyAsync(d + o_j, job, sizeof(*job), hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_off, off, sizeof(off), hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_mp, mps, sizeof(orbx_map_point) * (size_t)n,
-                              hipMemcpyHostToDevice, st)) ||
-        (skip && !HIPOK(hipMemcpyAsync(d + o_sk, skip, (size_t)n, hipMemcpyHostToDevice, st))) ||
-        (keyed && !HIPOK(hipMemcpyAsync(d + o_k, src_keys, sizeof(orbx_keypoint) * (size_t)n,
-                                        hipMemcpyHostToDevice, st))))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_project_map_points_batch_device(
-            mode, (const orbx_proj_job*)(d + o_j), 1, (const orbx_map_point*)(d + o_mp),
-            (const int32_t*)(d + o_off), n, keyed ? (const orbx_keypoint*)(d + o_k) : nullptr,
-            skip ? d + o_sk : nullptr, (orbx_proj_query*)(d + o_q), (int32_t*)(d + o_cnt), st);
-    if (s == ORBX_OK &&
-        (!HIPOK(hipMemcpyAsync(q, d + o_q, sizeof(orbx_proj_query) * (size_t)n,
-                               hipMemcpyDeviceToHost, st)) ||
-         !HIPOK(hipMemcpyAsync(&cnt, d + o_cnt, 4, hipMemcpyDeviceToHost, st))))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK && nactive) *nactive = cnt;
-    return s;
+    const size_t p_j = p.in(job, sizeof(*job)), p_off = p.in(off, sizeof(off)),
+                 p_mp = p.in(mps, sizeof(orbx_map_point) * (size_t)n),
+                 p_sk = p.in_opt(skip, (size_t)n),
+                 p_k = p.in_opt(keyed ? src_keys : nullptr, sizeof(orbx_keypoint) * (size_t)n),
+                 p_q = p.out(q, sizeof(orbx_proj_query) * (size_t)n), p_cnt = p.out(nactive, 4);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_project_map_points_batch_device(
+        mode, c.dev<orbx_proj_job>(p_j), 1, c.dev<orbx_map_point>(p_mp), c.dev<int32_t>(p_off), n,
+        c.dev<orbx_keypoint>(p_k), c.dev<uint8_t>(p_sk), c.dev<orbx_proj_query>(p_q),
+        c.dev<int32_t>(p_cnt), c.st()));
 }
 
 // ---- RGB-D ---------------------------------------------------------------------------------
@@ -1049,33 +967,20 @@ orbx_status orbx_compute_stereo_from_rgbd(const void* depth, int32_t depth_type,
     if (a != ORBX_OK) return a;
     if (n == 0) return ORBX_OK;
     if (!depth || !kps || !kps_un || !u_right || !depth_out) return ORBX_ERR_INVALID;
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const size_t tight = (size_t)width * depth_elem(depth_type), kb = sizeof(orbx_keypoint) * (size_t)n;
-    const size_t o_img = 0, o_k = al(tight * height), o_ku = o_k + al(kb), o_n = o_ku + al(kb),
-                 o_ur = o_n + 256, o_d = o_ur + al(4 * (size_t)n), end = o_d + 4 * (size_t)n;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    uint8_t* d = L.s->buf.as<uint8_t>();
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipMemcpy2DAsync(d + o_img, tight, depth, row_stride, tight, height,
-                                hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_k, kps, kb, hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_ku, kps_un, kb, hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_n, &n, 4, hipMemcpyHostToDevice, st)))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_compute_stereo_from_rgbd_batch_device(
-            d + o_img, depth_type, tight, 0, width, height, factor, mbf,
-            (const orbx_keypoint*)(d + o_k), (const orbx_keypoint*)(d + o_ku), n,
-            (const int32_t*)(d + o_n), 1, (float*)(d + o_ur), (float*)(d + o_d), st);
-    if (s == ORBX_OK &&
-        (!HIPOK(hipMemcpyAsync(u_right, d + o_ur, 4 * (size_t)n, hipMemcpyDeviceToHost, st)) ||
-         !HIPOK(hipMemcpyAsync(depth_out, d + o_d, 4 * (size_t)n, hipMemcpyDeviceToHost, st))))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    return s;
+    const size_t p_k = p.in(kps, kb), p_ku = p.in(kps_un, kb), p_n = p.in(&n, 4),
+                 p_ur = p.out(u_right, 4 * (size_t)n), p_d = p.out(depth_out, 4 * (size_t)n),
+                 p_img = p.scratch(tight * height);
+    if (!c.upload() || !HIPOK(hipMemcpy2DAsync(c.dev<uint8_t>(p_img), tight, depth, row_stride,
+                                               tight, height, hipMemcpyHostToDevice, c.st())))
+        return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_compute_stereo_from_rgbd_batch_device(
+        c.dev<uint8_t>(p_img), depth_type, tight, 0, width, height, factor, mbf,
+        c.dev<orbx_keypoint>(p_k), c.dev<orbx_keypoint>(p_ku), n, c.dev<int32_t>(p_n), 1,
+        c.dev<float>(p_ur), c.dev<float>(p_d), c.st()));
 }
 
 orbx_status orbx_unproject_stereo_batch_device(const orbx_frame_pose* d_poses,
@@ -1097,34 +1002,18 @@ orbx_status orbx_unproject_stereo(const orbx_frame_pose* pose, const orbx_keypoi
                                   int device) {
     if (!pose || n < 0 || (n > 0 && (!keys || !depth || !x3d))) return ORBX_ERR_INVALID;
     if (n == 0) return ORBX_OK;
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t kb = sizeof(orbx_keypoint) * (size_t)n;
-    const size_t o_f = 0, o_n = al(sizeof(orbx_frame_pose)), o_k = o_n + 256, o_d = o_k + al(kb),
-                 o_x = o_d + al(4 * (size_t)n), o_v = o_x + al(12 * (size_t)n),
-                 end = o_v + (size_t)n;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    uint8_t* d = L.s->buf.as<uint8_t>();
-    orbx_status s = ORBX_OK;
-    // x3d goes up first: slots without depth come back as the caller left them
-    if (!HIPOK(hipMemcpyAsync(d + o_f, pose, sizeof(*pose), hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_n, &n, 4, hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_k, keys, kb, hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_d, depth, 4 * (size_t)n, hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_x, x3d, 12 * (size_t)n, hipMemcpyHostToDevice, st)))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_unproject_stereo_batch_device(
-            (const orbx_frame_pose*)(d + o_f), (const orbx_keypoint*)(d + o_k), n,
-            (const float*)(d + o_d), (const int32_t*)(d + o_n), 1, (float*)(d + o_x), d + o_v, st);
-    if (s == ORBX_OK &&
-        (!HIPOK(hipMemcpyAsync(x3d, d + o_x, 12 * (size_t)n, hipMemcpyDeviceToHost, st)) ||
-         (valid && !HIPOK(hipMemcpyAsync(valid, d + o_v, (size_t)n, hipMemcpyDeviceToHost, st)))))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    return s;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
+    // x3d goes up too: slots without depth come back as the caller left them
+    const size_t p_f = p.in(pose, sizeof(*pose)), p_n = p.in(&n, 4),
+                 p_k = p.in(keys, sizeof(orbx_keypoint) * (size_t)n),
+                 p_d = p.in(depth, 4 * (size_t)n), p_x = p.inout(x3d, 12 * (size_t)n),
+                 p_v = p.out(valid, (size_t)n);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_unproject_stereo_batch_device(
+        c.dev<orbx_frame_pose>(p_f), c.dev<orbx_keypoint>(p_k), n, c.dev<float>(p_d),
+        c.dev<int32_t>(p_n), 1, c.dev<float>(p_x), c.dev<uint8_t>(p_v), c.st()));
 }
 
 orbx_status orbx_close_points_batch_device(const orbx_frame_pose* d_poses,
@@ -1156,48 +1045,27 @@ orbx_status orbx_close_points(const orbx_frame_pose* pose, const orbx_keypoint* 
     if (!pose || !counts || n < 0 || (n > 0 && (!keys || !depth || !order || !create || !x3d)))
         return ORBX_ERR_INVALID;
     if (n > CLOSE_MAX_FEATURES) return ORBX_ERR_UNSUPPORTED;
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t kb = sizeof(orbx_keypoint) * (size_t)n, nb = al((size_t)n);
-    const size_t o_f = 0, o_n = al(sizeof(orbx_frame_pose)), o_c = o_n + 256, o_k = o_c + 256,
-                 o_d = o_k + al(kb), o_h = o_d + al(4 * (size_t)n), o_t = o_h + nb,
-                 o_o = o_t + nb, o_cr = o_o + al(4 * (size_t)n), o_x = o_cr + nb,
-                 end = o_x + 12 * (size_t)n;
-    ScratchLease L(device);
-    if (!L.s || !L.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    hipStream_t st = L.s->st;
-    uint8_t* d = L.s->buf.as<uint8_t>();
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipMemcpyAsync(d + o_f, pose, sizeof(*pose), hipMemcpyHostToDevice, st)) ||
-        !HIPOK(hipMemcpyAsync(d + o_n, &n, 4, hipMemcpyHostToDevice, st)) ||
-        (n > 0 &&
-         (!HIPOK(hipMemcpyAsync(d + o_k, keys, kb, hipMemcpyHostToDevice, st)) ||
-          !HIPOK(hipMemcpyAsync(d + o_d, depth, 4 * (size_t)n, hipMemcpyHostToDevice, st)) ||
-          (has_point &&
-           !HIPOK(hipMemcpyAsync(d + o_h, has_point, (size_t)n, hipMemcpyHostToDevice, st))) ||
-          (tracked &&
-           !HIPOK(hipMemcpyAsync(d + o_t, tracked, (size_t)n, hipMemcpyHostToDevice, st))))))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_close_points_batch_device(
-            (const orbx_frame_pose*)(d + o_f), (const orbx_keypoint*)(d + o_k), n,
-            (const float*)(d + o_d), has_point ? d + o_h : nullptr, tracked ? d + o_t : nullptr,
-            (const int32_t*)(d + o_n), 1, th_depth, min_points, (int32_t*)(d + o_o),
-            (int32_t*)(d + o_c), d + o_cr, (float*)(d + o_x), st);
-    int32_t c[4] = {0, 0, 0, 0};
-    if (s == ORBX_OK && (!HIPOK(hipMemcpyAsync(c, d + o_c, 16, hipMemcpyDeviceToHost, st)) ||
-                         !HIPOK(hipStreamSynchronize(st))))
-        s = ORBX_ERR_DEVICE;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
+    const size_t p_f = p.in(pose, sizeof(*pose)), p_n = p.in(&n, 4),
+                 p_k = p.in(keys, sizeof(orbx_keypoint) * (size_t)n),
+                 p_d = p.in(depth, 4 * (size_t)n), p_h = p.in_opt(has_point, (size_t)n),
+                 p_t = p.in_opt(tracked, (size_t)n), p_c = p.out(counts, 16),
+                 p_o = p.out(nullptr, 4 * (size_t)n), p_cr = p.out(nullptr, (size_t)n),
+                 p_x = p.out(nullptr, 12 * (size_t)n);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    const orbx_status s = c.finish(orbx_close_points_batch_device(
+        c.dev<orbx_frame_pose>(p_f), c.dev<orbx_keypoint>(p_k), n, c.dev<float>(p_d),
+        c.dev<uint8_t>(p_h), c.dev<uint8_t>(p_t), c.dev<int32_t>(p_n), 1, th_depth, min_points,
+        c.dev<int32_t>(p_o), c.dev<int32_t>(p_c), c.dev<uint8_t>(p_cr), c.dev<float>(p_x), c.st()));
+    if (s != ORBX_OK) return s;
     // only what the pass wrote comes back: order[0, M), create / x3d [0, V)
-    if (s == ORBX_OK && c[0] > 0 &&
-        !HIPOK(hipMemcpyAsync(order, d + o_o, 4 * (size_t)c[0], hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK && c[1] > 0 &&
-        (!HIPOK(hipMemcpyAsync(create, d + o_cr, (size_t)c[1], hipMemcpyDeviceToHost, st)) ||
-         !HIPOK(hipMemcpyAsync(x3d, d + o_x, 12 * (size_t)c[1], hipMemcpyDeviceToHost, st))))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK) std::memcpy(counts, c, sizeof(c));
+    if (counts[0] > 0) std::memcpy(order, p.host<int32_t>(p_o), 4 * (size_t)counts[0]);
+    if (counts[1] > 0) {
+        std::memcpy(create, p.host<uint8_t>(p_cr), (size_t)counts[1]);
+        std::memcpy(x3d, p.host<float>(p_x), 12 * (size_t)counts[1]);
+    }
     return s;
 }
 

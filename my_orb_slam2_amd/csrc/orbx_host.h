@@ -5,6 +5,9 @@
 #include <climits>
 #include <cstddef>
 
+#include "../../include/orbx.h"
+#include "orbx_stage.h"
+
 #define ORBX_MAX_DEVICES 64  // per-device kernel attribute caches (prepare_kernels, kfdb)
 
 namespace orbx {
@@ -44,37 +47,55 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
-// Offsets inside one staging block: every part starts on a 256-byte boundary.
+// Sizes inside a device block, rounded as StagePlan rounds its parts (also used on the device).
 __host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
-struct Layout {
-    size_t end = 0;
-    size_t add(size_t bytes) {   // the offset of a part of `bytes` bytes, put behind the last one
-        const size_t o = end;
-        end += al256(bytes);
-        return o;
-    }
-};
 
 // (int) of a double as x86-64 converts it (cvttsd2si; cvttss2si for a widened float): NaN and
 // everything outside int's range give INT_MIN
 inline int cvtt(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
 
 // Device staging of the host-array entry points: a pool of (device, non-blocking stream,
-// growable buffer) slots taken for the length of one call.  After warm-up a call allocates
-// nothing, and it waits only for its own stream, never for the device (the reference calls
-// these from the Tracking thread while LocalMapping / LoopClosing run matchers).  The pool is
-// defined in orbx_frame.hip; slots live for the process (no teardown-order hazards).
+// growable device buffer, staging plan) slots taken for the length of one call.  After warm-up a
+// call allocates nothing, and it waits only for its own stream, never for the device (the
+// reference calls these from the Tracking thread while LocalMapping / LoopClosing run matchers).
+// The pool is defined in orbx_host.hip; slots live for the process (no teardown-order hazards).
 struct Scratch {
     int device = -1;
     hipStream_t st = nullptr;
     DevBuf buf;
+    StagePlan plan;
 };
 struct ScratchLease {
-    Scratch* s = nullptr;                  // nullptr: no stream could be created
-    explicit ScratchLease(int device);     // the calling thread's current device is `device`
+    Scratch* s = nullptr;     // nullptr: `device` is out of range or no stream could be created
+    // makes `device` the calling thread's current device first
+    explicit ScratchLease(int device);
     ~ScratchLease();
     ScratchLease(const ScratchLease&) = delete;
     ScratchLease& operator=(const ScratchLease&) = delete;
+};
+
+// One host-array call: makes `device` current, leases a slot, and moves the plan's two spans
+// with one copy each.  An entry point checks its arguments, declares its parts on plan(), calls
+// upload(), hands dev<T>() pointers and st() to the device form and returns finish(status).
+// Large strided images bypass the host block: a scratch part and a hipMemcpy2DAsync on st().
+class HostCall {
+  public:
+    explicit HostCall(int device) : lease_(device) {
+        if (lease_.s) lease_.s->plan.reset();
+    }
+    bool ok() const { return lease_.s; }   // else the entry point returns ORBX_ERR_DEVICE
+    StagePlan& plan() { return lease_.s->plan; }
+    hipStream_t st() const { return lease_.s->st; }
+    // sizes the device block and sends the upload span; false (recorded) on failure
+    bool upload();
+    template <class T> T* dev(size_t part) { return StagePlan::dev<T>(part, base_); }
+    // status still ORBX_OK: fetches the download span.  Always drains the stream, so a slot never
+    // returns to the pool with work in flight; then the copy-outs, on success only.
+    orbx_status finish(orbx_status status);
+
+  private:
+    ScratchLease lease_;
+    void* base_ = nullptr;
 };
 
 }  // namespace orbx

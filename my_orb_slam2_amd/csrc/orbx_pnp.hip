@@ -28,8 +28,6 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
@@ -1072,62 +1070,34 @@ orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
     if (job->N > PNP_MAX_N || job->max_its > PNP_MAX_ITS || window > PNP_MAX_ITS ||
         nq > INT_MAX / 4)
         return ORBX_ERR_UNSUPPORTED;
-    if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
-        return ORBX_ERR_DEVICE;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const int N = job->N, nm = job->n_matches, max_call = (int)window;
-    // one staging block: the inputs, the in / out state and best bytes, then the outputs and the
-    // scratch
-    Layout lay;
-    const size_t o_job = lay.add(sizeof(orbx_pnp_job)),
-                 o_corr = lay.add(sizeof(orbx_pnp_corr) * (size_t)N),
-                 o_quad = lay.add(16 * (size_t)nq), o_state = lay.add(256),
-                 o_best = lay.add((size_t)N), o_res = lay.add(sizeof(orbx_pnp_result)),
-                 o_inl = lay.add((size_t)nm), out_end = lay.end,
-                 o_scratch = lay.add(pnp_scratch_bytes(1, N, max_call)), end = lay.end;
-    std::vector<uint8_t> h(out_end, 0);
     orbx_pnp_job hj = *job;
     hj.corr_off = 0, hj.inlier_off = 0, hj.quad_off = 0, hj.best_off = 0;
-    std::memcpy(h.data() + o_job, &hj, sizeof(hj));
-    if (N) std::memcpy(h.data() + o_corr, corr, sizeof(orbx_pnp_corr) * (size_t)N);
-    if (nq) std::memcpy(h.data() + o_quad, quads, 16 * (size_t)nq);
-    std::memcpy(h.data() + o_state, state, sizeof(*state));
-    if (N) std::memcpy(h.data() + o_best, best, (size_t)N);
-    // what the kernels leave untouched comes back as the caller passed it
-    std::memcpy(h.data() + o_res, res, sizeof(*res));
-    if (nm) std::memcpy(h.data() + o_inl, inliers, (size_t)nm);
-
-    ScratchLease lease(device);
-    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = lease.s->buf.as<uint8_t>();
-    hipStream_t st = lease.s->st;
-    if (!HIPOK(hipMemcpyAsync(d, h.data(), out_end, hipMemcpyHostToDevice, st)))
-        return ORBX_ERR_DEVICE;
+    // res / inliers go up too: what the kernels leave untouched comes back as the caller passed it
+    const size_t p_job = p.in(&hj, sizeof(hj)), p_corr = p.in(corr, sizeof(orbx_pnp_corr) * (size_t)N),
+                 p_quad = p.in(quads, 16 * (size_t)nq), p_state = p.inout(state, sizeof(*state)),
+                 p_best = p.inout(best, (size_t)N), p_res = p.inout(res, sizeof(*res)),
+                 p_inl = p.inout(inliers, (size_t)nm),
+                 p_scratch = p.scratch(pnp_scratch_bytes(1, N, max_call));
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
     PnpLaunch L{};
-    L.jobs = (const orbx_pnp_job*)(d + o_job);
+    L.jobs = c.dev<orbx_pnp_job>(p_job);
     L.njobs = 1, L.max_n = N, L.max_call = max_call;
-    L.corr = (const orbx_pnp_corr*)(d + o_corr);
+    L.corr = c.dev<orbx_pnp_corr>(p_corr);
     L.ncorr = N;
-    L.quads = (const int32_t*)(d + o_quad);
+    L.quads = c.dev<int32_t>(p_quad);
     L.nquads = nq;
-    L.state = (orbx_pnp_state*)(d + o_state);
-    L.best = d + o_best;
+    L.state = c.dev<orbx_pnp_state>(p_state);
+    L.best = c.dev<uint8_t>(p_best);
     L.nbest = N;
-    L.res = (orbx_pnp_result*)(d + o_res);
-    L.inliers = d + o_inl;
+    L.res = c.dev<orbx_pnp_result>(p_res);
+    L.inliers = c.dev<uint8_t>(p_inl);
     L.ninliers = nm;
-    L.scratch = d + o_scratch;
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(launch_pnp(L, st)) ||
-        !HIPOK(hipMemcpyAsync(h.data() + o_state, d + o_state, out_end - o_state,
-                              hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s != ORBX_OK) return s;
-    std::memcpy(state, h.data() + o_state, sizeof(*state));
-    if (N) std::memcpy(best, h.data() + o_best, (size_t)N);
-    std::memcpy(res, h.data() + o_res, sizeof(*res));
-    if (nm) std::memcpy(inliers, h.data() + o_inl, (size_t)nm);
-    return ORBX_OK;
+    L.scratch = c.dev<uint8_t>(p_scratch);
+    return c.finish(HIPOK(launch_pnp(L, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
 }
 
 orbx_status orbx_pnp_correspondences_batch_device(

@@ -23,7 +23,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "orbx_host.h"
@@ -524,49 +523,24 @@ orbx_status orbx_pose_optimization(const orbx_frame_pose* pose, const orbx_keypo
     if (!pose || !pose_out || !ngood || n < 0 || n > (int32_t)PO_MAX_FEAT || nmp < 0 ||
         (n > 0 && (!keys_un || !mp_of_feat || !outlier)) || (nmp > 0 && !mps))
         return ORBX_ERR_INVALID;
-    if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
-        return ORBX_ERR_DEVICE;
-    // one staging block: the inputs, the in / out outlier bytes, then the outputs
-    Layout lay;
-    const size_t o_pose = lay.add(sizeof(orbx_frame_pose)), o_idx = lay.add(256),
-                 o_keys = lay.add(sizeof(orbx_keypoint) * (size_t)n),
-                 o_ur = lay.add(u_right ? 4 * (size_t)n : 0), o_mpf = lay.add(4 * (size_t)n),
-                 o_mps = lay.add(sizeof(orbx_map_point) * (size_t)nmp + 256),
-                 o_out = lay.add((size_t)n), o_res = lay.add(sizeof(orbx_frame_pose)),
-                 o_cnt = lay.add(256), end = lay.end;   // o_cnt: ngood, info
-    std::vector<uint8_t> h(end, 0);
-    std::memcpy(h.data() + o_pose, pose, sizeof(*pose));
-    int32_t* idx = (int32_t*)(h.data() + o_idx);      // feat_off[2], mp_off[2]
-    idx[0] = 0, idx[1] = n, idx[2] = 0, idx[3] = nmp;
-    if (n) {
-        std::memcpy(h.data() + o_keys, keys_un, sizeof(orbx_keypoint) * (size_t)n);
-        if (u_right) std::memcpy(h.data() + o_ur, u_right, 4 * (size_t)n);
-        std::memcpy(h.data() + o_mpf, mp_of_feat, 4 * (size_t)n);
-        std::memcpy(h.data() + o_out, outlier, (size_t)n);
-    }
-    if (nmp) std::memcpy(h.data() + o_mps, mps, sizeof(orbx_map_point) * (size_t)nmp);
-
-    ScratchLease lease(device);
-    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = lease.s->buf.as<uint8_t>();
-    hipStream_t st = lease.s->st;
-    if (!HIPOK(hipMemcpyAsync(d, h.data(), end, hipMemcpyHostToDevice, st))) return ORBX_ERR_DEVICE;
-    orbx_status s = orbx_pose_optimization_batch_device(
-        (const orbx_frame_pose*)(d + o_pose), 1, (const orbx_keypoint*)(d + o_keys),
-        u_right ? (const float*)(d + o_ur) : nullptr, (const int32_t*)(d + o_idx), n,
-        (const int32_t*)(d + o_mpf), (const orbx_map_point*)(d + o_mps),
-        (const int32_t*)(d + o_idx) + 2, (orbx_frame_pose*)(d + o_res), d + o_out,
-        (int32_t*)(d + o_cnt), (uint32_t*)(d + o_cnt) + 1, st);
-    if (s == ORBX_OK &&
-        !HIPOK(hipMemcpyAsync(h.data() + o_out, d + o_out, end - o_out, hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s != ORBX_OK) return s;
-    std::memcpy(pose_out, h.data() + o_res, sizeof(*pose_out));
-    if (n) std::memcpy(outlier, h.data() + o_out, (size_t)n);
-    *ngood = *(const int32_t*)(h.data() + o_cnt);
-    if (info) *info = *((const uint32_t*)(h.data() + o_cnt) + 1);
-    return ORBX_OK;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
+    const int32_t idx[4] = {0, n, 0, nmp};   // feat_off[2], mp_off[2]
+    const size_t mpb = sizeof(orbx_map_point) * (size_t)nmp;
+    const size_t p_pose = p.in(pose, sizeof(*pose)), p_idx = p.in(idx, sizeof(idx)),
+                 p_keys = p.in(keys_un, sizeof(orbx_keypoint) * (size_t)n),
+                 p_ur = p.in_opt(u_right, 4 * (size_t)n), p_mpf = p.in(mp_of_feat, 4 * (size_t)n),
+                 p_mps = p.in(nullptr, mpb + 256), p_out = p.inout(outlier, (size_t)n),
+                 p_res = p.out(pose_out, sizeof(*pose_out), true), p_ngood = p.out(ngood, 4, true),
+                 p_info = p.out(info, 4, true);   // the outputs start at zero on the device, as ever
+    if (nmp) std::memcpy(p.host<uint8_t>(p_mps), mps, mpb);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_pose_optimization_batch_device(
+        c.dev<orbx_frame_pose>(p_pose), 1, c.dev<orbx_keypoint>(p_keys), c.dev<float>(p_ur),
+        c.dev<int32_t>(p_idx), n, c.dev<int32_t>(p_mpf), c.dev<orbx_map_point>(p_mps),
+        c.dev<int32_t>(p_idx) + 2, c.dev<orbx_frame_pose>(p_res), c.dev<uint8_t>(p_out),
+        c.dev<int32_t>(p_ngood), c.dev<uint32_t>(p_info), c.st()));
 }
 
 orbx_status orbx_matches_to_features_batch_device(const int32_t* d_match, const int32_t* d_q_off,

@@ -388,28 +388,20 @@ orbx_status orbx_remap(const orbx_rectifier* r, const uint8_t* src, size_t src_s
                        uint8_t* dst, size_t dst_stride) {
     if (!r || !src || !dst || src_stride < (size_t)r->src_w || dst_stride < (size_t)r->dst_w)
         return ORBX_ERR_INVALID;
-    if (!HIPOK(hipSetDevice(r->device))) return ORBX_ERR_DEVICE;
+    HostCall c(r->device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
     const size_t sb = (size_t)r->src_w * r->src_h, db = (size_t)r->dst_w * r->dst_h;
-    uint8_t* d = nullptr;
-    hipStream_t st = nullptr;
-    if (!HIPOK(hipMalloc((void**)&d, sb + db))) return ORBX_ERR_DEVICE;
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking))) s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK && !HIPOK(hipMemcpy2DAsync(d, r->src_w, src, src_stride, r->src_w, r->src_h,
-                                                hipMemcpyHostToDevice, st)))
-        s = ORBX_ERR_DEVICE;
-    if (s == ORBX_OK)
-        s = orbx_remap_batch_device(r, d, r->src_w, sb, d + sb, r->dst_w, db, 1, st);
+    const size_t p_src = c.plan().scratch(sb), p_dst = c.plan().scratch(db);
+    if (!c.upload() || !HIPOK(hipMemcpy2DAsync(c.dev<uint8_t>(p_src), r->src_w, src, src_stride,
+                                               r->src_w, r->src_h, hipMemcpyHostToDevice, c.st())))
+        return c.finish(ORBX_ERR_DEVICE);
+    orbx_status s = orbx_remap_batch_device(r, c.dev<uint8_t>(p_src), r->src_w, sb,
+                                            c.dev<uint8_t>(p_dst), r->dst_w, db, 1, c.st());
     // only the dst_w bytes of each row come back: the rest of the caller's rows is untouched
-    if (s == ORBX_OK && !HIPOK(hipMemcpy2DAsync(dst, dst_stride, d + sb, r->dst_w, r->dst_w,
-                                                r->dst_h, hipMemcpyDeviceToHost, st)))
+    if (s == ORBX_OK && !HIPOK(hipMemcpy2DAsync(dst, dst_stride, c.dev<uint8_t>(p_dst), r->dst_w,
+                                                r->dst_w, r->dst_h, hipMemcpyDeviceToHost, c.st())))
         s = ORBX_ERR_DEVICE;
-    if (st) {
-        if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-        (void)hipStreamDestroy(st);
-    }
-    (void)hipFree(d);
-    return s;
+    return c.finish(s);
 }
 
 }  // extern "C"

@@ -20,8 +20,6 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
@@ -665,63 +663,37 @@ orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pos
         (job->N > 0 && !corr) || (job->mN1 > 0 && !inliers))
         return ORBX_ERR_INVALID;
     if (job->N > SIM3_MAX_N || job->max_its > SIM3_MAX_ITS) return ORBX_ERR_UNSUPPORTED;
-    if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
-        return ORBX_ERR_DEVICE;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const int N = job->N, mN1 = job->mN1, max_its = job->max_its;
     const int max_call = job->n_iterations < max_its ? job->n_iterations : max_its;
-    // one staging block: the inputs, the in / out state, then the outputs and the scratch
-    Layout lay;
-    const size_t o_pose = lay.add(2 * sizeof(orbx_frame_pose)),
-                 o_job = lay.add(sizeof(orbx_sim3_job)),
-                 o_corr = lay.add(sizeof(orbx_sim3_corr) * (size_t)N),
-                 o_tri = lay.add(12 * (size_t)max_its), o_state = lay.add(256),
-                 o_res = lay.add(sizeof(orbx_sim3_result)), o_inl = lay.add((size_t)mN1),
-                 out_end = lay.end, o_scratch = lay.add(sim3_scratch_bytes(1, N, max_call)),
-                 end = lay.end;
-    std::vector<uint8_t> h(out_end, 0);
-    std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
-    std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
+    const orbx_frame_pose poses[2] = {*pose1, *pose2};
     orbx_sim3_job hj = *job;
     hj.kf1 = 0, hj.kf2 = 1, hj.corr_off = 0, hj.inlier_off = 0, hj.triple_off = 0;
-    std::memcpy(h.data() + o_job, &hj, sizeof(hj));
-    if (N) std::memcpy(h.data() + o_corr, corr, sizeof(orbx_sim3_corr) * (size_t)N);
-    std::memcpy(h.data() + o_tri, triples, 12 * (size_t)max_its);
-    std::memcpy(h.data() + o_state, state, sizeof(*state));
-    // what the kernels leave untouched comes back as the caller passed it
-    std::memcpy(h.data() + o_res, res, sizeof(*res));
-    if (mN1) std::memcpy(h.data() + o_inl, inliers, (size_t)mN1);
-
-    ScratchLease lease(device);
-    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = lease.s->buf.as<uint8_t>();
-    hipStream_t st = lease.s->st;
-    if (!HIPOK(hipMemcpyAsync(d, h.data(), out_end, hipMemcpyHostToDevice, st)))
-        return ORBX_ERR_DEVICE;
+    // res / inliers go up too: what the kernels leave untouched comes back as the caller passed it
+    const size_t p_pose = p.in(poses, sizeof(poses)), p_job = p.in(&hj, sizeof(hj)),
+                 p_corr = p.in(corr, sizeof(orbx_sim3_corr) * (size_t)N),
+                 p_tri = p.in(triples, 12 * (size_t)max_its),
+                 p_state = p.inout(state, sizeof(*state)), p_res = p.inout(res, sizeof(*res)),
+                 p_inl = p.inout(inliers, (size_t)mN1),
+                 p_scratch = p.scratch(sim3_scratch_bytes(1, N, max_call));
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
     Sim3Launch L{};
-    L.jobs = (const orbx_sim3_job*)(d + o_job);
+    L.jobs = c.dev<orbx_sim3_job>(p_job);
     L.njobs = 1, L.max_n = N, L.max_call = max_call;
-    L.poses = (const orbx_frame_pose*)(d + o_pose);
+    L.poses = c.dev<orbx_frame_pose>(p_pose);
     L.nposes = 2;
-    L.corr = (const orbx_sim3_corr*)(d + o_corr);
+    L.corr = c.dev<orbx_sim3_corr>(p_corr);
     L.ncorr = N;
-    L.triples = (const int32_t*)(d + o_tri);
+    L.triples = c.dev<int32_t>(p_tri);
     L.ntriples = max_its;
-    L.state = (orbx_sim3_state*)(d + o_state);
-    L.res = (orbx_sim3_result*)(d + o_res);
-    L.inliers = d + o_inl;
+    L.state = c.dev<orbx_sim3_state>(p_state);
+    L.res = c.dev<orbx_sim3_result>(p_res);
+    L.inliers = c.dev<uint8_t>(p_inl);
     L.ninliers = mN1;
-    L.scratch = d + o_scratch;
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(launch_sim3(L, st)) ||
-        !HIPOK(hipMemcpyAsync(h.data() + o_state, d + o_state, out_end - o_state,
-                              hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s != ORBX_OK) return s;
-    std::memcpy(state, h.data() + o_state, sizeof(*state));
-    std::memcpy(res, h.data() + o_res, sizeof(*res));
-    if (mN1) std::memcpy(inliers, h.data() + o_inl, (size_t)mN1);
-    return ORBX_OK;
+    L.scratch = c.dev<uint8_t>(p_scratch);
+    return c.finish(HIPOK(launch_sim3(L, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
 }
 
 }  // extern "C"

@@ -29,8 +29,6 @@
 #include <cstddef>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <vector>
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
@@ -590,52 +588,31 @@ orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_po
     if (job->N < 0 || job->mN1 < 0 || (job->N > 0 && !corr) || (job->mN1 > 0 && !keep))
         return ORBX_ERR_INVALID;
     if (job->N > SIM3OPT_MAX_N) return ORBX_ERR_UNSUPPORTED;
-    if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
-        return ORBX_ERR_DEVICE;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const int N = job->N, mN1 = job->mN1;
-    // one staging block: the inputs, then the outputs
-    Layout lay;
-    const size_t o_pose = lay.add(2 * sizeof(orbx_frame_pose)),
-                 o_job = lay.add(sizeof(orbx_sim3opt_job)), o_in = lay.add(sizeof(orbx_sim3opt_in)),
-                 o_corr = lay.add(sizeof(orbx_sim3opt_corr) * (size_t)N),
-                 o_res = lay.add(sizeof(orbx_sim3opt_result)), o_keep = lay.add((size_t)mN1),
-                 end = lay.end;
-    std::vector<uint8_t> h(end, 0);
-    std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
-    std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
+    const orbx_frame_pose poses[2] = {*pose1, *pose2};
     orbx_sim3opt_job hj = *job;
     hj.kf1 = 0, hj.kf2 = 1, hj.corr_off = 0, hj.flag_off = 0;
-    std::memcpy(h.data() + o_job, &hj, sizeof(hj));
-    std::memcpy(h.data() + o_in, sim3_in, sizeof(*sim3_in));
-    if (N) std::memcpy(h.data() + o_corr, corr, sizeof(orbx_sim3opt_corr) * (size_t)N);
-    if (mN1) std::memcpy(h.data() + o_keep, keep, (size_t)mN1);
-
-    ScratchLease lease(device);
-    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = lease.s->buf.as<uint8_t>();
-    hipStream_t st = lease.s->st;
-    if (!HIPOK(hipMemcpyAsync(d, h.data(), end, hipMemcpyHostToDevice, st))) return ORBX_ERR_DEVICE;
+    const size_t p_pose = p.in(poses, sizeof(poses)), p_job = p.in(&hj, sizeof(hj)),
+                 p_in = p.in(sim3_in, sizeof(*sim3_in)),
+                 p_corr = p.in(corr, sizeof(orbx_sim3opt_corr) * (size_t)N),
+                 p_keep = p.inout(keep, (size_t)mN1), p_res = p.out(res, sizeof(*res), true);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
     Sim3OptLaunch L{};
-    L.jobs = (const orbx_sim3opt_job*)(d + o_job);
+    L.jobs = c.dev<orbx_sim3opt_job>(p_job);
     L.njobs = 1, L.max_n = N;
-    L.poses = (const orbx_frame_pose*)(d + o_pose);
+    L.poses = c.dev<orbx_frame_pose>(p_pose);
     L.nposes = 2;
-    L.corr = (const orbx_sim3opt_corr*)(d + o_corr);
+    L.corr = c.dev<orbx_sim3opt_corr>(p_corr);
     L.ncorr = N;
-    L.sim3_in = d + o_in;
+    L.sim3_in = c.dev<uint8_t>(p_in);
     L.in_stride = sizeof(orbx_sim3opt_in);
-    L.res = (orbx_sim3opt_result*)(d + o_res);
-    L.keep = d + o_keep;
+    L.res = c.dev<orbx_sim3opt_result>(p_res);
+    L.keep = c.dev<uint8_t>(p_keep);
     L.nkeep = mN1;
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(launch_sim3_opt(L, st)) ||
-        !HIPOK(hipMemcpyAsync(h.data() + o_res, d + o_res, end - o_res, hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
-    if (s != ORBX_OK) return s;
-    std::memcpy(res, h.data() + o_res, sizeof(*res));
-    if (mN1) std::memcpy(keep, h.data() + o_keep, (size_t)mN1);
-    return ORBX_OK;
+    return c.finish(HIPOK(launch_sim3_opt(L, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
 }
 
 }  // extern "C"

@@ -414,83 +414,71 @@ orbx_status orbx_triangulate_matches(
     }
     if (nnew) *nnew = 0;
     if (npairs == 0) return ORBX_OK;
-    if (device < 0 || device >= ORBX_MAX_DEVICES || !HIPOK(hipSetDevice(device)))
-        return ORBX_ERR_DEVICE;
-
-    // one staging block: every input, then the outputs
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
     const size_t n = (size_t)n1 + (size_t)n2;
     const bool raw = keys_raw1 || keys_raw2, stereo = u_right1 || u_right2;
-    Layout lay;
-    const size_t o_pose = lay.add(2 * sizeof(orbx_frame_pose)), o_idx = lay.add(256),
-                 o_keys = lay.add(sizeof(orbx_keypoint) * n),
-                 o_raw = lay.add(raw ? sizeof(orbx_keypoint) * n : 0),
-                 o_ur = lay.add(stereo ? 4 * n : 0), o_depth = lay.add(4 * n),
-                 o_cos = lay.add(4 * n), o_match = lay.add(4 * (size_t)n1), in_end = lay.end,
-                 o_cnt = lay.add(256), o_status = lay.add(4 * (size_t)n1),
-                 o_x3d = lay.add(12 * (size_t)n1), end = lay.end;
-    std::vector<uint8_t> h(end, 0);
-    std::memcpy(h.data() + o_pose, pose1, sizeof(*pose1));
-    std::memcpy(h.data() + o_pose + sizeof(*pose1), pose2, sizeof(*pose2));
-    int32_t* idx = (int32_t*)(h.data() + o_idx);   // feat_off[3], kf1, kf2, job_off[2]
-    idx[0] = 0, idx[1] = n1, idx[2] = n1 + n2, idx[3] = 0, idx[4] = 1, idx[5] = 0, idx[6] = n1;
-    auto put = [&](size_t off, const void* a, const void* b, size_t elem) {
-        if (a && n1) std::memcpy(h.data() + off, a, elem * (size_t)n1);
-        if (b && n2) std::memcpy(h.data() + off + elem * (size_t)n1, b, elem * (size_t)n2);
+    const orbx_frame_pose poses[2] = {*pose1, *pose2};
+    const int32_t idx[7] = {0, n1, n1 + n2, 0, 1, 0, n1};   // feat_off[3], kf1, kf2, job_off[2]
+    // a part over both frames' features: a's n1 elements, then b's n2 (zeros where null)
+    auto both = [&](bool present, const void* a, const void* b, size_t elem) {
+        if (!present) return StagePlan::NONE;
+        const size_t o = p.in(nullptr, elem * n);
+        if (a && n1) std::memcpy(p.host<uint8_t>(o), a, elem * (size_t)n1);
+        if (b && n2) std::memcpy(p.host<uint8_t>(o) + elem * (size_t)n1, b, elem * (size_t)n2);
+        return o;
     };
-    put(o_keys, keys1, keys2, sizeof(orbx_keypoint));
-    if (raw) put(o_raw, keys_raw1 ? keys_raw1 : keys1, keys_raw2 ? keys_raw2 : keys2, sizeof(orbx_keypoint));
+    const size_t p_pose = p.in(poses, sizeof(poses)), p_idx = p.in(idx, sizeof(idx)),
+                 p_keys = both(true, keys1, keys2, sizeof(orbx_keypoint));
+    const size_t p_raw = both(raw, keys_raw1 ? keys_raw1 : keys1, keys_raw2 ? keys_raw2 : keys2,
+                              sizeof(orbx_keypoint));
+    const size_t p_ur = stereo ? p.in(nullptr, 4 * n) : StagePlan::NONE;
     if (stereo) {
-        float* ur = (float*)(h.data() + o_ur);
+        float* ur = p.host<float>(p_ur);
         for (size_t k = 0; k < n; ++k) ur[k] = -1.0f;
-        put(o_ur, u_right1, u_right2, 4);
+        if (u_right1 && n1) std::memcpy(ur, u_right1, 4 * (size_t)n1);
+        if (u_right2 && n2) std::memcpy(ur + n1, u_right2, 4 * (size_t)n2);
     }
-    put(o_depth, depth1, depth2, 4);
-    float* cs = (float*)(h.data() + o_cos);
-    if (cos_stereo1) put(o_cos, cos_stereo1, nullptr, 4);
-    else if (depth1) orbx_parallax_stereo_cos(mb, depth1, n1, cs);
-    if (cos_stereo2) put(o_cos, nullptr, cos_stereo2, 4);
-    else if (depth2) orbx_parallax_stereo_cos(mb, depth2, n2, cs + n1);
-    if (n1) std::memcpy(h.data() + o_match, match12.data(), 4 * (size_t)n1);
-
-    ScratchLease lease(device);
-    if (!lease.s || !lease.s->buf.ensure(end)) return ORBX_ERR_DEVICE;
-    uint8_t* d = lease.s->buf.as<uint8_t>();
-    hipStream_t st = lease.s->st;
-    if (!HIPOK(hipMemcpyAsync(d, h.data(), in_end + 256, hipMemcpyHostToDevice, st)))
-        return ORBX_ERR_DEVICE;
+    const size_t p_depth = both(true, depth1, depth2, 4);
+    const size_t p_cos = both(true, cos_stereo1, cos_stereo2, 4);
+    float* cs = p.host<float>(p_cos);
+    if (!cos_stereo1 && depth1) orbx_parallax_stereo_cos(mb, depth1, n1, cs);
+    if (!cos_stereo2 && depth2) orbx_parallax_stereo_cos(mb, depth2, n2, cs + n1);
+    // cnt: nnew, err (zeroed with the block; the host checks came first)
+    const size_t p_match = p.in(match12.data(), 4 * (size_t)n1), p_cnt = p.out(nullptr, 8, true),
+                 p_status = p.out(nullptr, 4 * (size_t)n1), p_x3d = p.out(nullptr, 12 * (size_t)n1);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
     TriPointsLaunch L{};
     L.nkf = 2;
-    L.feat_off = (const int32_t*)(d + o_idx);
-    L.keys = (const orbx_keypoint*)(d + o_keys);
-    L.keys_raw = raw ? (const orbx_keypoint*)(d + o_raw) : nullptr;
-    L.u_right = stereo ? (const float*)(d + o_ur) : nullptr;
-    L.depth = (const float*)(d + o_depth);
-    L.cos_stereo = (const float*)(d + o_cos);
-    L.poses = (const orbx_frame_pose*)(d + o_pose);
+    L.feat_off = c.dev<int32_t>(p_idx);
+    L.keys = c.dev<orbx_keypoint>(p_keys);
+    L.keys_raw = c.dev<orbx_keypoint>(p_raw);
+    L.u_right = c.dev<float>(p_ur);
+    L.depth = c.dev<float>(p_depth);
+    L.cos_stereo = c.dev<float>(p_cos);
+    L.poses = c.dev<orbx_frame_pose>(p_pose);
     L.kf1 = L.feat_off + 3;
     L.kf2 = L.feat_off + 4;
     L.job_off = L.feat_off + 5;
-    L.match12 = (const int32_t*)(d + o_match);
+    L.match12 = c.dev<int32_t>(p_match);
     L.ratio_factor = ratio_factor;
-    L.status = (int32_t*)(d + o_status);
-    L.x3d = (float*)(d + o_x3d);
-    L.nnew = (int32_t*)(d + o_cnt);
-    L.err = (int*)(d + o_cnt) + 1;     // zeroed with the block; the host checks came first
-    orbx_status s = ORBX_OK;
-    if (!HIPOK(launch_triangulate_points(L, n1, 1, st)) ||
-        !HIPOK(hipMemcpyAsync(h.data() + o_cnt, d + o_cnt, end - o_cnt, hipMemcpyDeviceToHost, st)))
-        s = ORBX_ERR_DEVICE;
-    if (!HIPOK(hipStreamSynchronize(st))) s = ORBX_ERR_DEVICE;
+    L.status = c.dev<int32_t>(p_status);
+    L.x3d = c.dev<float>(p_x3d);
+    L.nnew = c.dev<int32_t>(p_cnt);
+    L.err = c.dev<int>(p_cnt) + 1;
+    const orbx_status s =
+        c.finish(HIPOK(launch_triangulate_points(L, n1, 1, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
     if (s != ORBX_OK) return s;
-    const int32_t* hs = (const int32_t*)(h.data() + o_status);
-    const float* hx = (const float*)(h.data() + o_x3d);
-    for (int32_t p = 0; p < npairs; ++p) {
-        const int32_t i1 = pairs[2 * p];
-        status[p] = hs[i1];
+    const int32_t* hs = p.host<int32_t>(p_status);
+    const float* hx = p.host<float>(p_x3d);
+    for (int32_t q = 0; q < npairs; ++q) {
+        const int32_t i1 = pairs[2 * q];
+        status[q] = hs[i1];
         if (hs[i1] <= ORBX_TRI_OK_STEREO2)
-            for (int k = 0; k < 3; ++k) x3d[3 * (size_t)p + k] = hx[3 * (size_t)i1 + k];
+            for (int k = 0; k < 3; ++k) x3d[3 * (size_t)q + k] = hx[3 * (size_t)i1 + k];
     }
-    if (nnew) *nnew = *(const int32_t*)(h.data() + o_cnt);
+    if (nnew) *nnew = *p.host<int32_t>(p_cnt);
     return ORBX_OK;
 }
 

@@ -366,40 +366,20 @@ orbx_status orbx_bow_db_score(const uint32_t* qword, const double* qval, int32_t
     const int nw = kf_off[nkf] - kf_off[0];
     if (nw < 0 || (nw > 0 && (!word || !val)) || (nq > 0 && (!qword || !qval)))
         return ORBX_ERR_INVALID;
-    if (!HIPOK(hipSetDevice(device))) return ORBX_ERR_DEVICE;
-    std::vector<int32_t> rel(nkf + 1);
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
+    const size_t p_qv = p.in(qval, 8 * (size_t)nq), p_qw = p.in(qword, 4 * (size_t)nq),
+                 p_v = p.in(nw ? val + kf_off[0] : nullptr, 8 * (size_t)nw),
+                 p_w = p.in(nw ? word + kf_off[0] : nullptr, 4 * (size_t)nw),
+                 p_off = p.in(nullptr, 4 * ((size_t)nkf + 1)),
+                 p_sc = p.out(score, 4 * (size_t)nkf), p_cm = p.out(common, 4 * (size_t)nkf);
+    int32_t* rel = p.host<int32_t>(p_off);
     for (int i = 0; i <= nkf; ++i) rel[i] = kf_off[i] - kf_off[0];
-    const size_t bytes = 4 * (size_t)nq + 8 * (size_t)nq + 4 * rel.size() + 4 * (size_t)nw +
-                         8 * (size_t)nw + 8 * (size_t)nkf + 64 * 6;
-    DevBuf buf;
-    if (!buf.ensure(bytes)) return ORBX_ERR_DEVICE;
-    uint8_t* b = buf.as<uint8_t>();
-    size_t o = 0;
-    auto put = [&](const void* src, size_t n) {
-        uint8_t* d = b + o;
-        o = (o + n + 63) & ~(size_t)63;
-        if (n && src && !HIPOK(hipMemcpy(d, src, n, hipMemcpyHostToDevice))) return (uint8_t*)nullptr;
-        return d;
-    };
-    uint8_t* dqv = put(qval, 8 * (size_t)nq);
-    uint8_t* dqw = put(qword, 4 * (size_t)nq);
-    uint8_t* dv = put(nw ? val + kf_off[0] : nullptr, 8 * (size_t)nw);
-    uint8_t* dw = put(nw ? word + kf_off[0] : nullptr, 4 * (size_t)nw);
-    uint8_t* doff = put(rel.data(), 4 * rel.size());
-    uint8_t* dsc = put(nullptr, 4 * (size_t)nkf);
-    uint8_t* dcm = put(nullptr, 4 * (size_t)nkf);
-    orbx_status s = ORBX_ERR_DEVICE;
-    if (dqv && dqw && dv && dw && doff) {
-        s = orbx_bow_db_score_device((uint32_t*)dqw, (double*)dqv, nq, nkf, (int32_t*)doff,
-                                     (uint32_t*)dw, (double*)dv, (int32_t*)dcm, (float*)dsc,
-                                     nullptr);
-        if (s == ORBX_OK &&
-            (!HIPOK(hipMemcpy(common, dcm, 4 * (size_t)nkf, hipMemcpyDeviceToHost)) ||
-             !HIPOK(hipMemcpy(score, dsc, 4 * (size_t)nkf, hipMemcpyDeviceToHost))))
-            s = ORBX_ERR_DEVICE;
-    }
-    buf.release();
-    return s;
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(orbx_bow_db_score_device(
+        c.dev<uint32_t>(p_qw), c.dev<double>(p_qv), nq, nkf, c.dev<int32_t>(p_off),
+        c.dev<uint32_t>(p_w), c.dev<double>(p_v), c.dev<int32_t>(p_cm), c.dev<float>(p_sc), c.st()));
 }
 
 int32_t orbx_bow_db_score_max_query(void) {

@@ -163,3 +163,34 @@ def test_cvt_gray_gpu(orbx_lib, gpu, rgb, c):
     from my_orb_slam2_amd.features import cvt_color_gray
     img = np.random.default_rng(7).integers(0, 256, (376, 1241, c), dtype=np.uint8)
     np.testing.assert_array_equal(cvt_color_gray(img, bool(rgb)), om.cvt_gray(img, rgb))
+
+
+@pytest.mark.gpu
+def test_undistort_host_form_sentinels(orbx_lib, gpu):
+    """orbx_undistort_keypoints on three keypoints, the output inside a sentinel-filled allocation:
+    x / y are the restatement's, the other fields the input's, nothing else is written."""
+    import host_array_cases as hc
+    c = hc.case("undistort")
+    un = c.call()["keys_un"]
+    assert un.guards_intact()
+    want = undistort_np(np.stack([c.keys["x"], c.keys["y"]], 1), c.K4, c.dist)
+    assert (want != np.stack([c.keys["x"], c.keys["y"]], 1)).all()       # k1 != 0: they moved
+    np.testing.assert_array_equal(un.a["x"].view(np.int32), want[:, 0].view(np.int32))
+    np.testing.assert_array_equal(un.a["y"].view(np.int32), want[:, 1].view(np.int32))
+    for f in ("size", "angle", "response", "octave", "class_id"):
+        assert un.a[f].tobytes() == c.keys[f].tobytes(), f
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("channels", [3, 4])
+def test_cvt_color_host_form_sentinels(orbx_lib, gpu, channels):
+    """orbx_cvt_color on 5 x 3 pixels with both strides padded: the `width` bytes of each
+    destination row are the restatement's, the row padding and the guards keep the sentinel."""
+    import host_array_cases as hc
+    c = hc.case(f"cvt_color{channels}")
+    dst = c.call()["dst"]
+    assert dst.guards_intact()
+    px = c.src[:, :hc.CVT_W * channels].reshape(hc.CVT_H, hc.CVT_W, channels).astype(np.int64)
+    want = ((px[..., 0] * 4899 + px[..., 1] * 9617 + px[..., 2] * 1868 + 8192) >> 14).astype(np.uint8)
+    np.testing.assert_array_equal(dst.a[:, :hc.CVT_W], want)               # rgb order
+    assert (dst.a[:, hc.CVT_W:] == hc.SENT).all()

@@ -158,3 +158,18 @@ def test_gpu_frustum_one_frame(oracle_mod, orbx_lib, gpu, seed):
     assert q3.tobytes() == qo3.tobytes()
     qe, ne = is_in_frustum(F, mps[:0])
     assert ne == 0 and len(qe) == 0
+
+
+@pytest.mark.gpu
+def test_gpu_frustum_host_form_sentinels(orbx_lib, gpu):
+    """orbx_is_in_frustum on three MapPoints, one skipped, the outputs inside sentinel-filled
+    allocations: the three queries and the count are the restatement's (the skipped point's query
+    is the not-in-view record), nothing else is written."""
+    import host_array_cases as hc
+    c = hc.case("frustum")
+    r = c.call()
+    assert r["q"].guards_intact() and r["nvisible"].guards_intact()
+    want, n = numpy_is_in_frustum(c.F, c.mps, c.skip)
+    assert n >= 1 and want["radius"][1] == -1.0
+    assert r["q"].a.tobytes() == want.tobytes()
+    assert int(r["nvisible"].a[0]) == n

@@ -299,10 +299,13 @@ def test_capture_beside_cross_stream_wait(orbx_lib, gpu):
 
 
 def _host_array_calls():
-    """The five host-array solver entry points, each on its smallest committed directed case that
-    runs at least one full iteration: name -> a function that makes the case's call(s) from fresh
-    inputs and returns every array and record that comes back, as bytes, ahead of a count of the
-    iterations the call ran."""
+    """The fourteen host-array entry points.  The five solvers, each on its smallest committed
+    directed case that runs at least one full iteration: name -> a function that makes the case's
+    call(s) from fresh inputs and returns every array and record that comes back, as bytes, ahead of
+    a count of the iterations the call ran.  The nine per-frame ones on the tiny cases of
+    tests/host_array_cases.py (the count is 1): the returned bytes are the callers' whole output
+    allocations, sentinel guards and row padding included."""
+    import host_array_cases
     import pnp_cases
     import poseopt_cases
     import sim3_cases
@@ -373,10 +376,15 @@ def _host_array_calls():
             cos_stereo2=c["cos2"])
         return (nnew, st.tobytes(), x.tobytes())
 
-    return dict(poseopt=poseopt, sim3opt=sim3opt, sim3=sim3, pnp=pnp, triangulate=triangulate)
+    calls = dict(poseopt=poseopt, sim3opt=sim3opt, sim3=sim3, pnp=pnp, triangulate=triangulate)
+    for name in host_array_cases.NAMES:
+        calls[name] = host_array_cases.case(name).call_bytes
+    return calls
 
 
-HOST_ARRAY_ENTRY_POINTS = ("poseopt", "sim3opt", "sim3", "pnp", "triangulate")
+HOST_ARRAY_ENTRY_POINTS = ("poseopt", "sim3opt", "sim3", "pnp", "triangulate", "undistort",
+                           "frustum", "project", "unproject", "close", "rgbd_u16", "rgbd_f32",
+                           "cvt_color3", "cvt_color4", "remap", "bow_db_score")
 
 
 @pytest.fixture(scope="module")
@@ -391,13 +399,14 @@ def host_array_serial(orbx_lib, gpu):
 
 @pytest.mark.parametrize("name", HOST_ARRAY_ENTRY_POINTS)
 def test_host_array_solver_threads_equal_serial(host_array_serial, name):
-    """orbx_pose_optimization, orbx_sim3_optimize, orbx_sim3_iterate, orbx_pnp_iterate and
-    orbx_triangulate_matches stage through a leased (stream, buffer) slot each (orbx_host.h,
-    ScratchLease), so calls of one entry point from several threads run beside each other: four
-    threads leave a barrier together and call it three times each on the same case while a fifth
-    calls another entry point.  Every array and record equals the serial call's, byte for byte."""
+    """Every host-array entry point stages through a leased (stream, buffer, plan) slot
+    (orbx_host.h, HostCall), so calls of one entry point from several threads run beside each
+    other: four threads leave a barrier together and call it three times each on the same case
+    while a fifth calls another entry point.  Every array and record equals the serial call's,
+    byte for byte."""
     calls, serial = host_array_serial
-    other = HOST_ARRAY_ENTRY_POINTS[(HOST_ARRAY_ENTRY_POINTS.index(name) + 1) % 5]
+    names = HOST_ARRAY_ENTRY_POINTS
+    other = names[(names.index(name) + 1) % len(names)]
     barrier = threading.Barrier(5)
     got, errors = [], []
 

@@ -344,3 +344,17 @@ def test_rgbd_track_with_motion_model(oracle_mod, orbx_lib, gpu):
     # stereo: the forward and the backward window and the default one all occur
     assert {w for p in per for w in p["window"]} == {"", "default", "forward", "backward"}
     _track_check(mt, per, ku, desc, ur, gpu)
+
+
+def test_host_form_sentinels(orbx_lib, gpu):
+    """orbx_project_map_points (LAST_FRAME, so that src_keys is staged) on three MapPoints, one
+    skipped, the outputs inside sentinel-filled allocations: the three queries and the count are
+    the restatement's, nothing else is written."""
+    import host_array_cases as hc
+    c = hc.case("project")
+    r = c.call()
+    assert r["q"].guards_intact() and r["nactive"].guards_intact()
+    want, n, _ = pc.project_np(PROJ_LAST_FRAME, c.job, c.mps, c.src_keys, c.skip)
+    assert n >= 1 and want["radius"][1] == -1.0
+    _assert_queries(r["q"].a, want, "host form")
+    assert int(r["nactive"].a[0]) == n

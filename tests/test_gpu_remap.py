@@ -176,3 +176,17 @@ def test_statuses(orbx_lib, gpu):
     assert L.orbx_remap_stereo_batch_device(r._h, r._h, a, a, 8, 32, b, _vp(buf, 3072), 8, 32, 1,
                                             None) == 0
     torch.cuda.synchronize()
+
+
+def test_host_form_guards(gpu):
+    """orbx_remap through the smallest rectifier with dst_stride > dst_w, the destination inside a
+    sentinel-filled allocation: the dst_w bytes of each row are the restatement's, the row padding
+    and the guards keep the sentinel."""
+    import host_array_cases as hc
+    c = hc.case("remap")
+    dst = c.call()["dst"]
+    assert dst.guards_intact()
+    dw = c.c0["map1"].shape[1]
+    want = rc.remap_closed(c.c0["src"][:1], c.c0["map1"], c.c0["map2"])[0]
+    assert np.array_equal(dst.a[:, :dw], want)
+    assert (dst.a[:, dw:] == hc.SENT).all() and dst.a.shape[1] > dw

@@ -395,3 +395,51 @@ def test_rgbd_track_batch(oracle_mod, orbx_lib, gpu):
         np.testing.assert_array_equal(out[q_off[j]:q_off[j + 1]], m_o)
     assert cnt[0] > 100 and cnt[1] == 0
     assert not np.array_equal(blind[0][1], refs[0][1])       # u_right changed the outcome
+
+
+@pytest.mark.parametrize("name", ["rgbd_u16", "rgbd_f32"])
+def test_depth_host_form_sentinels(orbx_lib, gpu, name):
+    """orbx_compute_stereo_from_rgbd on three keypoints of the padded image, the outputs inside
+    sentinel-filled allocations: three values each, the restatement's; nothing else is written."""
+    import host_array_cases as hc
+    c = hc.case(name)
+    r = c.call()
+    assert r["u_right"].guards_intact() and r["depth"].guards_intact()
+    d = c.d
+    ur, de = rc.compute_stereo_from_rgbd(d["img"], d["depth_type"], d["factor"], d["mbf"], d["kps"],
+                                         d["kps_un"])
+    assert np.array_equal(_bits(r["u_right"].a), _bits(ur))
+    assert np.array_equal(_bits(r["depth"].a), _bits(de))
+
+
+def test_unprojection_host_form_sentinels(orbx_lib, gpu):
+    """orbx_unproject_stereo on three keypoints, the middle one without depth: its x3d row keeps the
+    sentinel bytes it held, the other rows and `valid` are the restatement's, the guards intact."""
+    import host_array_cases as hc
+    c = hc.case("unproject")
+    r = c.call()
+    assert r["x3d"].guards_intact() and r["valid"].guards_intact()
+    want, valid = rc.unproject_all(c.F, c.keys, c.depth, hc.sentinel(f32, 9).reshape(3, 3).copy())
+    assert valid.tolist() == [1, 0, 1] and r["valid"].a.tolist() == [1, 0, 1]
+    assert r["x3d"].a.tobytes() == want.tobytes()
+    assert r["x3d"].a[1].tobytes() == bytes([hc.SENT]) * 12
+
+
+def test_close_points_host_form_guards(orbx_lib, gpu):
+    """orbx_close_points with has_point given and tracked null on five keypoints: order[:M],
+    create[:V], x3d[:V] and the counts are the restatement's; the slots past the counts and the
+    guards keep the sentinel."""
+    import host_array_cases as hc
+    c = hc.case("close")
+    r = c.call()
+    assert all(g.guards_intact() for g in r.values())
+    order_o, counts_o, create_o, x3d_o = rc.close_points_ref(c.F, c.keys, c.depth, c.th,
+                                                             c.has_point, None)
+    M, V = int(counts_o[0]), int(counts_o[1])
+    assert 0 < V <= M < 5
+    assert np.array_equal(r["counts"].a, counts_o)
+    assert np.array_equal(r["order"].a[:M], order_o) and np.array_equal(r["create"].a[:V], create_o)
+    assert np.array_equal(_bits(r["x3d"].a[:V]), _bits(x3d_o))
+    assert r["order"].a[M:].tobytes() == bytes([hc.SENT]) * (4 * (5 - M))
+    assert (r["create"].a[V:] == hc.SENT).all()
+    assert r["x3d"].a[V:].tobytes() == bytes([hc.SENT]) * (12 * (5 - V))

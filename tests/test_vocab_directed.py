@@ -218,3 +218,17 @@ def test_gpu_bow_db_score_query_limit(oracle_mod, orbx_lib, gpu):
     with pytest.raises(OrbxError) as e:
         bow_db_score(q, kfs)
     assert e.value.code == ERR_UNSUPPORTED
+
+
+@pytest.mark.gpu
+def test_gpu_bow_db_score_sentinels(oracle_mod, orbx_lib, gpu):
+    """orbx_bow_db_score with two keyframes, three query words and kf_off[0] = 5, the outputs
+    inside sentinel-filled allocations: nkf values each, the restatement's; nothing else written."""
+    import host_array_cases as hc
+    c = hc.case("bow_db_score")
+    r = c.call()
+    assert r["common"].guards_intact() and r["score"].guards_intact()
+    want_c, want_s = _expected_scores(c.q, c.kfs)
+    assert want_c.tolist() == [2, 1]
+    np.testing.assert_array_equal(r["common"].a, want_c)
+    np.testing.assert_array_equal(r["score"].a.view(np.uint32), want_s.view(np.uint32))
