@@ -15,11 +15,13 @@
  *
  * Outputs are feature indices (-1 = no match); the facade turns them back into MapPoint*.
  * Every function returns the reference method's return value in *nmatches.  All host-pointer
- * entry points copy their inputs to the device, run on the matcher's stream and wait.
+ * entry points copy their inputs to the device, run on a stream of their own and wait.
  * Functions named *_device take device pointers and run on the caller's stream.
  *
  * A matcher handle is not re-entrant (its device workspace is reused); use one per thread,
  * as the reference's Tracking / LocalMapping / LoopClosing threads each own their ORBmatcher.
+ * A host-pointer call reports ORBX_ERR_CAPACITY from a word of its own: it neither clears nor
+ * reads the flag that *_device calls on the same handle leave for orbx_matcher_sync.
  */
 #ifndef ORBX_MATCH_H
 #define ORBX_MATCH_H

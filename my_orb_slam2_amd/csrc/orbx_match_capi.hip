@@ -1,10 +1,10 @@
 // orbx_match_capi.hip — the extern "C" matcher boundary (include/orbx_match.h).
 //
-// Host side: argument validation, packing of the caller's arrays into one staging block
-// (one H2D copy per call), the launch sequence on the matcher's stream, and the host-only
-// tails of the reference methods (SearchBySim3's agreement check :1363-1379,
-// SearchForInitialization's vbPrevMatched update :555-558, the (idx1, idx2) pair list of
-// SearchForTriangulation :861-869).
+// Host side: argument validation, one function per launch struct that both the host-array form
+// and the *_batch_device form run with the handle's mutex held, the host forms' staging through
+// HostCall (orbx_host.h), and the host-only tails of the reference methods (SearchBySim3's
+// agreement check :1363-1379, SearchForInitialization's vbPrevMatched update :555-558, the
+// (idx1, idx2) pair list of SearchForTriangulation :861-869).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,11 +24,10 @@ static_assert((int)ORBX_MK_COUNT <= (int)orbx::K_COUNT, "the matcher timer share
 
 struct orbx_matcher {
     orbx_matcher_params prm;
-    hipStream_t stream = nullptr;
     int ncu = 256;                     // compute units of the device (BF chunk sizing)
-    DevBuf d_in, d_out, d_aux, d_proj, d_bf, d_sim3, d_pnp;
-    int* d_err = nullptr;
-    std::vector<uint8_t> staging;
+    // d_bf_db: the database of orbx_hamming_bf_top2 (it may be gigabytes: not in a pooled slot)
+    DevBuf d_aux, d_proj, d_bf, d_bf_db, d_sim3, d_pnp;
+    int* d_err = nullptr;              // the capacity word of the *_device forms (orbx_matcher_sync)
     KernelTimer timer;
     std::mutex mu;
     // recorded after the last brute-force launch (its partial-result scratch d_bf is shared by
@@ -44,25 +43,6 @@ namespace {
 
 constexpr int MAX_FEAT = 32768;        // per featureset (on-chip claim / state arrays)
 constexpr int MAX_POS = 1 << 23;       // grid CSR positions in the 32-bit search keys
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Accumulates the caller's arrays into one host block copied to the device at once.
-struct Packer {
-    std::vector<uint8_t>& h;
-    explicit Packer(std::vector<uint8_t>& buf) : h(buf) { h.clear(); }
-    size_t reserve(size_t bytes) {
-        const size_t off = align256(h.size());
-        h.resize(off + std::max<size_t>(bytes, 4), 0);
-        return off;
-    }
-    size_t add(const void* p, size_t bytes) {
-        const size_t off = reserve(bytes);
-        if (bytes && p) std::memcpy(h.data() + off, p, bytes);
-        return off;
-    }
-    template <class T> T* at(size_t off) { return (T*)(h.data() + off); }
-};
 
 bool valid_nodes(const orbx_featureset* f) {
     if (f->n_nodes < 0) return false;
@@ -99,15 +79,33 @@ bool valid_feat(const orbx_featureset* f, bool nodes, bool grid) {
     return true;
 }
 
-// A keyframe database built from host featuresets (device offsets inside the staging block).
-struct DbOffsets {
+// The members of a device orbx_kf_db that a call reads: the feature arrays and the node CSR
+// always, node_id (DB_NODE_ID) for the matchers that pair nodes by id, and (DB_NODE_ORDERED) the
+// optional node-ordered copies, all there or none.  desc and node_desc are read as 16-byte words.
+enum { DB_NODE_ID = 1, DB_NODE_ORDERED = 2 };
+bool valid_kf_db(const orbx_kf_db* db, int need) {
+    if (!db->feat_off || !db->keys || !db->desc || !db->flag || !db->node_off ||
+        !db->node_feat_off || !db->node_feat || ((need & DB_NODE_ID) && !db->node_id) ||
+        ((uintptr_t)db->desc & 15))
+        return false;
+    if ((need & DB_NODE_ORDERED) &&
+        (db->node_keys || db->node_desc || db->node_flag || db->node_u_right) &&
+        (!db->node_keys || !db->node_desc || !db->node_flag ||
+         (db->u_right != nullptr) != (db->node_u_right != nullptr) ||
+         ((uintptr_t)db->node_desc & 15)))
+        return false;
+    return true;
+}
+
+// A keyframe database built from host featuresets: its parts in the call's plan.
+struct DbParts {
     size_t feat_off, keys, desc, u_right, flag, node_off, node_id, node_feat_off, node_feat;
     int nkf, max_feat;
 };
 
-DbOffsets pack_db(Packer& P, const orbx_featureset* const* fs, const uint8_t* const* flags,
-                  int nkf) {
-    DbOffsets o{};
+DbParts pack_db(StagePlan& P, const orbx_featureset* const* fs, const uint8_t* const* flags,
+                int nkf) {
+    DbParts o{};
     o.nkf = nkf;
     int nf = 0, nn = 0, nnf = 0;
     for (int k = 0; k < nkf; ++k) {
@@ -116,47 +114,51 @@ DbOffsets pack_db(Packer& P, const orbx_featureset* const* fs, const uint8_t* co
         if (fs[k]->n_nodes > 0) nnf += fs[k]->node_off[fs[k]->n_nodes] - fs[k]->node_off[0];
         o.max_feat = std::max(o.max_feat, fs[k]->n);
     }
-    o.feat_off = P.reserve(4 * (nkf + 1));
-    o.keys = P.reserve(sizeof(orbx_keypoint) * (size_t)nf);
-    o.desc = P.reserve(32 * (size_t)nf);
-    o.u_right = P.reserve(4 * (size_t)nf);
-    o.flag = P.reserve((size_t)nf);
-    o.node_off = P.reserve(4 * (nkf + 1));
-    o.node_id = P.reserve(4 * (size_t)nn);
-    o.node_feat_off = P.reserve(4 * ((size_t)nn + 1));
-    o.node_feat = P.reserve(4 * (size_t)nnf);
+    o.feat_off = P.in(nullptr, 4 * (nkf + 1));
+    o.keys = P.in(nullptr, sizeof(orbx_keypoint) * (size_t)nf);
+    o.desc = P.in(nullptr, 32 * (size_t)nf);
+    o.u_right = P.in(nullptr, 4 * (size_t)nf);
+    o.flag = P.in(nullptr, (size_t)nf);
+    o.node_off = P.in(nullptr, 4 * (nkf + 1));
+    o.node_id = P.in(nullptr, 4 * (size_t)nn);
+    o.node_feat_off = P.in(nullptr, 4 * ((size_t)nn + 1));
+    o.node_feat = P.in(nullptr, 4 * (size_t)nnf);
+    // every part is declared: the block stays where it is while they are filled
+    int32_t* feat_off = P.host<int32_t>(o.feat_off);
+    int32_t* node_off = P.host<int32_t>(o.node_off);
+    int32_t* node_feat_off = P.host<int32_t>(o.node_feat_off);
     int f0 = 0, n0 = 0, e0 = 0;
     for (int k = 0; k < nkf; ++k) {
         const orbx_featureset* f = fs[k];
-        P.at<int32_t>(o.feat_off)[k] = f0;
-        P.at<int32_t>(o.node_off)[k] = n0;
+        feat_off[k] = f0;
+        node_off[k] = n0;
         if (f->n > 0) {
-            std::memcpy(P.at<orbx_keypoint>(o.keys) + f0, f->keys, sizeof(orbx_keypoint) * f->n);
-            std::memcpy(P.at<uint8_t>(o.desc) + 32 * (size_t)f0, f->desc, 32 * (size_t)f->n);
-            float* ur = P.at<float>(o.u_right) + f0;
+            std::memcpy(P.host<orbx_keypoint>(o.keys) + f0, f->keys, sizeof(orbx_keypoint) * f->n);
+            std::memcpy(P.host<uint8_t>(o.desc) + 32 * (size_t)f0, f->desc, 32 * (size_t)f->n);
+            float* ur = P.host<float>(o.u_right) + f0;
             for (int i = 0; i < f->n; ++i) ur[i] = f->u_right ? f->u_right[i] : -1.0f;
-            uint8_t* fl = P.at<uint8_t>(o.flag) + f0;
+            uint8_t* fl = P.host<uint8_t>(o.flag) + f0;
             for (int i = 0; i < f->n; ++i) fl[i] = (flags && flags[k]) ? (flags[k][i] != 0) : 0;
         }
         for (int j = 0; j < f->n_nodes; ++j) {
-            P.at<uint32_t>(o.node_id)[n0 + j] = f->node_id[j];
-            P.at<int32_t>(o.node_feat_off)[n0 + j] = e0 + f->node_off[j] - f->node_off[0];
+            P.host<uint32_t>(o.node_id)[n0 + j] = f->node_id[j];
+            node_feat_off[n0 + j] = e0 + f->node_off[j] - f->node_off[0];
         }
         if (f->n_nodes > 0) {
             const int cnt = f->node_off[f->n_nodes] - f->node_off[0];
-            std::memcpy(P.at<int32_t>(o.node_feat) + e0, f->node_feat + f->node_off[0], 4 * (size_t)cnt);
+            std::memcpy(P.host<int32_t>(o.node_feat) + e0, f->node_feat + f->node_off[0], 4 * (size_t)cnt);
             e0 += cnt;
         }
         f0 += f->n;
         n0 += f->n_nodes;
     }
-    P.at<int32_t>(o.feat_off)[nkf] = f0;
-    P.at<int32_t>(o.node_off)[nkf] = n0;
-    P.at<int32_t>(o.node_feat_off)[n0] = e0;
+    feat_off[nkf] = f0;
+    node_off[nkf] = n0;
+    node_feat_off[n0] = e0;
     return o;
 }
 
-orbx_kf_db dev_db(const DbOffsets& o, uint8_t* base) {
+orbx_kf_db dev_db(const DbParts& o, uint8_t* base) {
     orbx_kf_db d{};
     d.nkf = o.nkf;
     d.max_feat = o.max_feat;
@@ -173,24 +175,24 @@ orbx_kf_db dev_db(const DbOffsets& o, uint8_t* base) {
 }
 
 // A single featureset with its grid (projection searches).
-struct FeatOffsets {
+struct FeatParts {
     size_t keys, desc, u_right, grid_off, grid_feat;
 };
 
-FeatOffsets pack_feat(Packer& P, const orbx_featureset* f) {
-    FeatOffsets o{};
-    o.keys = P.add(f->keys, sizeof(orbx_keypoint) * (size_t)f->n);
-    o.desc = P.add(f->desc, 32 * (size_t)f->n);
-    o.u_right = P.reserve(4 * (size_t)f->n);
-    float* ur = P.at<float>(o.u_right);
-    for (int i = 0; i < f->n; ++i) ur[i] = f->u_right ? f->u_right[i] : -1.0f;
+FeatParts pack_feat(StagePlan& P, const orbx_featureset* f) {
+    FeatParts o{};
     const size_t cells = (size_t)f->grid_cols * f->grid_rows;
-    o.grid_off = P.add(f->grid_off, 4 * (cells + 1));
-    o.grid_feat = P.add(f->grid_feat, 4 * (size_t)f->grid_off[cells]);
+    o.keys = P.in(f->keys, sizeof(orbx_keypoint) * (size_t)f->n);
+    o.desc = P.in(f->desc, 32 * (size_t)f->n);
+    o.u_right = P.in(nullptr, 4 * (size_t)f->n);
+    o.grid_off = P.in(f->grid_off, 4 * (cells + 1));
+    o.grid_feat = P.in(f->grid_feat, 4 * (size_t)f->grid_off[cells]);
+    float* ur = P.host<float>(o.u_right);
+    for (int i = 0; i < f->n; ++i) ur[i] = f->u_right ? f->u_right[i] : -1.0f;
     return o;
 }
 
-orbx_featureset dev_feat(const orbx_featureset* f, const FeatOffsets& o, uint8_t* base) {
+orbx_featureset dev_feat(const orbx_featureset* f, const FeatParts& o, uint8_t* base) {
     orbx_featureset d = *f;
     d.keys = (const orbx_keypoint*)(base + o.keys);
     d.desc = base + o.desc;
@@ -204,24 +206,132 @@ orbx_featureset dev_feat(const orbx_featureset* f, const FeatOffsets& o, uint8_t
     return d;
 }
 
-orbx_status upload(orbx_matcher* m) {
-    if (!m->d_in.ensure(m->staging.size())) return ORBX_ERR_DEVICE;
-    if (!HIPOK(hipMemcpyAsync(m->d_in.p, m->staging.data(), m->staging.size(),
-                              hipMemcpyHostToDevice, m->stream)))
-        return ORBX_ERR_DEVICE;
-    if (!HIPOK(hipMemsetAsync(m->d_err, 0, sizeof(int), m->stream))) return ORBX_ERR_DEVICE;
+// The capacity word of one host-array call: a part of its own, zeroed on the device too because
+// k_bow, k_triangulate, k_proj_resolve and k_distinctive only ever OR into it.  The handle's
+// d_err belongs to the *_device forms alone.
+size_t err_part(StagePlan& P) { return P.out(nullptr, sizeof(int), /*zeroed=*/true); }
+
+orbx_status finish(HostCall& c, size_t p_err, orbx_status s) {
+    s = c.finish(s);
+    return (s == ORBX_OK && *c.plan().host<int>(p_err)) ? ORBX_ERR_CAPACITY : s;
+}
+
+// The three launch bodies below run with m->mu held, from the host-array form (device pointers
+// into its HostCall block, `err` its own word) and from the *_batch_device form (the caller's
+// pointers, m->d_err).
+
+orbx_status run_bow(orbx_matcher* m, const orbx_kf_db& A, const orbx_kf_db& B, int a_fixed,
+                    int kf_kf, int njobs, int32_t* out, int out_stride, int32_t* nmatches,
+                    int* err, hipStream_t st) {
+    BowLaunch L{};
+    L.A = A;
+    L.B = B;
+    L.a_fixed = a_fixed;
+    L.b_fixed = 1;
+    L.kf_kf = kf_kf;
+    L.njobs = njobs;
+    L.ratio = m->prm.nnratio;
+    L.check_ori = m->prm.check_orientation;
+    L.out = out;
+    L.out_stride = out_stride;
+    L.nmatches = nmatches;
+    L.err = err;
+    if (bow_lds_bytes(L) > MATCH_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
+    hipEvent_t e = m->timer.start(st);
+    if (!HIPOK(launch_bow(L, st))) return ORBX_ERR_DEVICE;
+    m->timer.stop(ORBX_MK_BOW, e, st);
     return ORBX_OK;
 }
 
-// Copies `bytes` from the device output block to `dst` and waits; checks the error word.
-orbx_status finish(orbx_matcher* m, void* dst, const void* src, size_t bytes) {
-    int err = 0;
-    if (bytes && !HIPOK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, m->stream)))
-        return ORBX_ERR_DEVICE;
-    if (!HIPOK(hipMemcpyAsync(&err, m->d_err, sizeof(int), hipMemcpyDeviceToHost, m->stream)) ||
-        !HIPOK(hipStreamSynchronize(m->stream)))
-        return ORBX_ERR_DEVICE;
-    return err ? ORBX_ERR_CAPACITY : ORBX_OK;
+orbx_status run_tri(orbx_matcher* m, const orbx_kf_db& db, int njobs, const int32_t* kf1,
+                    const int32_t* kf2, const float* F12, const float* epi, const float* sigma2,
+                    const float* scale, int nlevels, int only_stereo, const int32_t* job_off,
+                    int32_t* out, int32_t* nmatches, int* err, hipStream_t st) {
+    TriLaunch L{};
+    L.db = db;
+    L.njobs = njobs;
+    L.kf1 = kf1;
+    L.kf2 = kf2;
+    L.F12 = F12;
+    L.epi = epi;
+    for (int l = 0; l < MATCH_MAX_LEVELS; ++l) {
+        L.sigma2[l] = l < nlevels ? sigma2[l] : 0.f;
+        L.scale[l] = l < nlevels ? scale[l] : 0.f;
+    }
+    L.only_stereo = only_stereo;
+    L.check_ori = m->prm.check_orientation;
+    L.job_off = job_off;
+    L.out = out;
+    L.nmatches = nmatches;
+    L.err = err;
+    if (tri_lds_bytes(db.max_feat) > TRI_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
+    hipEvent_t e = m->timer.start(st);
+    if (!HIPOK(launch_triangulate(L, st))) return ORBX_ERR_DEVICE;
+    m->timer.stop(ORBX_MK_TRIANGULATE, e, st);
+    return ORBX_OK;
+}
+
+// The scratch of one projection search over njobs targets and nq queries in all: offsets from a
+// 256-byte aligned base.  A kernel writes every region before one reads it (k_proj_search top2 /
+// cand / ncand; k_proj_resolve bins and hist, counted from zero in its LDS), so none is zeroed.
+struct ProjScratch {
+    size_t hist, top2, bins, cand, ncand, end;
+};
+ProjScratch proj_scratch(int njobs, size_t nq) {
+    ProjScratch s{};
+    s.top2 = al256(128 * (size_t)njobs);
+    s.bins = s.top2 + al256(16 * nq);
+    s.cand = s.bins + al256(nq);
+    s.ncand = s.cand + al256(8 * PROJ_K * nq);
+    s.end = s.ncand + al256(4 * nq);
+    return s;
+}
+
+// T: the targets' device arrays with T.n = the largest target; t_off / g_off / q_off are null
+// for a single job.  scratch: proj_scratch(njobs, nq).end bytes.
+orbx_status run_proj(orbx_matcher* m, int mode, const orbx_featureset& T, int njobs,
+                     const int32_t* t_off, const int32_t* g_off, const int32_t* q_off,
+                     const uint8_t* claimed, const uint8_t* qdesc, const orbx_proj_query* q,
+                     const uint8_t* qflags, int nq, const float* inv_sigma2, int nlevels,
+                     int orb_dist, int flags, uint8_t* scratch, int32_t* out, int32_t* nmatches,
+                     int* err, hipStream_t st) {
+    const ProjScratch s = proj_scratch(njobs, (size_t)nq);
+    ProjLaunch L{};
+    L.mode = mode;
+    L.T = T;
+    L.T.n_nodes = 0;
+    L.T.node_id = nullptr;
+    L.T.node_off = nullptr;
+    L.T.node_feat = nullptr;
+    L.njobs = njobs;
+    L.t_off = t_off;
+    L.g_off = g_off;
+    L.q_off = q_off;
+    L.max_t = T.n;
+    L.qdesc = qdesc;
+    L.q = q;
+    L.nq = nq;
+    for (int l = 0; l < MATCH_MAX_LEVELS; ++l)
+        L.inv_sigma2[l] = (inv_sigma2 && l < nlevels) ? inv_sigma2[l] : 0.f;
+    L.orb_dist = orb_dist;
+    L.ratio = m->prm.nnratio;
+    L.check_ori = m->prm.check_orientation;
+    L.claimed_in = claimed;
+    L.qflags = qflags;
+    L.prefilter = (flags & ORBX_PROJ_PREFILTER) != 0;
+    L.out = out;
+    L.top2 = (int4*)(scratch + s.top2);
+    L.cand = (int2*)(scratch + s.cand);
+    L.ncand = (int32_t*)(scratch + s.ncand);
+    L.out_bin = (int8_t*)(scratch + s.bins);
+    L.hist = (int32_t*)(scratch + s.hist);
+    L.nmatches = nmatches;
+    L.err = err;
+    if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, L.max_t, nq) > MATCH_MAX_LDS)
+        return ORBX_ERR_UNSUPPORTED;
+    if (nq == 0)   // every job: no queries, no matches
+        return HIPOK(hipMemsetAsync(nmatches, 0, 4 * (size_t)njobs, st)) ? ORBX_OK : ORBX_ERR_DEVICE;
+    return HIPOK(launch_proj(L, st, &m->timer)) ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
 orbx_status bow_common(orbx_matcher* m, const orbx_featureset* a, const uint8_t* va,
@@ -230,44 +340,22 @@ orbx_status bow_common(orbx_matcher* m, const orbx_featureset* a, const uint8_t*
     if (!m || !out || !nmatches || !va || (kf_kf && !vb)) return ORBX_ERR_INVALID;
     if (!valid_feat(a, true, false) || !valid_feat(b, true, false)) return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    Packer P(m->staging);
-    const orbx_featureset* fa[1] = {a};
-    const orbx_featureset* fb[1] = {b};
-    const uint8_t* la[1] = {va};
-    const uint8_t* lb[1] = {vb};
-    const DbOffsets oa = pack_db(P, fa, la, 1), ob = pack_db(P, fb, lb, 1);
-    orbx_status s = upload(m);
-    if (s != ORBX_OK) return s;
+    HostCall c(m->prm.device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& P = c.plan();
+    const DbParts pa = pack_db(P, &a, &va, 1), pb = pack_db(P, &b, &vb, 1);
     const int nout = kf_kf ? a->n : b->n;
-    if (!m->d_out.ensure(4 * ((size_t)nout + 64))) return ORBX_ERR_DEVICE;
-    BowLaunch L{};
-    L.A = dev_db(oa, m->d_in.as<uint8_t>());
-    L.B = dev_db(ob, m->d_in.as<uint8_t>());
-    L.a_fixed = 1;
-    L.b_fixed = 1;
-    L.kf_kf = kf_kf;
-    L.njobs = 1;
-    L.ratio = m->prm.nnratio;
-    L.check_ori = m->prm.check_orientation;
-    L.out = m->d_out.as<int32_t>() + 64;
-    L.out_stride = nout;
-    L.nmatches = m->d_out.as<int32_t>();
-    L.err = m->d_err;
-    if (bow_lds_bytes(L) > MATCH_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
-    hipEvent_t e = m->timer.start(m->stream);
-    if (!HIPOK(launch_bow(L, m->stream))) return ORBX_ERR_DEVICE;
-    m->timer.stop(ORBX_MK_BOW, e, m->stream);
-    std::vector<int32_t> res((size_t)nout + 64);
-    s = finish(m, res.data(), m->d_out.p, 4 * res.size());
-    if (s != ORBX_OK) return s;
-    std::memcpy(out, res.data() + 64, 4 * (size_t)nout);
-    *nmatches = res[0];
-    return ORBX_OK;
+    const size_t p_out = P.out(out, 4 * (size_t)nout), p_n = P.out(nmatches, 4),
+                 p_err = err_part(P);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    uint8_t* base = c.dev<uint8_t>(0);
+    return finish(c, p_err, run_bow(m, dev_db(pa, base), dev_db(pb, base), 1, kf_kf, 1,
+                                    c.dev<int32_t>(p_out), nout, c.dev<int32_t>(p_n),
+                                    c.dev<int>(p_err), c.st()));
 }
 
-// The size limits of one projection search (any mode, PROJ_INIT included): shared by the entry
-// points and orbx_matcher_variant.
+// The size limits of one projection search (any mode, PROJ_INIT included) as the host forms
+// apply them (valid_feat, proj_common, run_proj), for orbx_matcher_variant.
 orbx_status proj_size_status(int mode, int n_target, int nq) {
     if (nq < 0 || nq > (1 << 22) || n_target < 0 || n_target > MAX_FEAT) return ORBX_ERR_INVALID;
     if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, n_target, nq) > MATCH_MAX_LDS)
@@ -284,63 +372,22 @@ orbx_status proj_common(orbx_matcher* m, int mode, const orbx_featureset* T,
     if (!valid_feat(T, false, true)) return ORBX_ERR_INVALID;
     if (mode == ORBX_PROJ_FUSE && (!inv_sigma2 || nlevels <= 0)) return ORBX_ERR_INVALID;
     if (nlevels > MATCH_MAX_LEVELS) return ORBX_ERR_UNSUPPORTED;
-    const orbx_status sz = proj_size_status(mode, T->n, nq);
-    if (sz != ORBX_OK) return sz;
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    Packer P(m->staging);
-    const FeatOffsets ot = pack_feat(P, T);
-    const size_t oq = P.add(q, sizeof(orbx_proj_query) * (size_t)nq);
-    const size_t od = P.add(qdesc, 32 * (size_t)nq);
-    size_t oc = 0, of = 0;
-    if (claimed) oc = P.add(claimed, (size_t)T->n);
-    if (qflags) of = P.add(qflags, (size_t)nq);
-    orbx_status s = upload(m);
-    if (s != ORBX_OK) return s;
-    // outputs: nmatches(64 ints) | out[nq] | hist[32] | top2[nq] | bins[nq] | cand | ncand
-    const size_t o_out = 256, o_hist = align256(o_out + 4 * (size_t)nq),
-                 o_top = align256(o_hist + 128), o_bin = align256(o_top + 16 * (size_t)nq),
-                 o_cand = align256(o_bin + (size_t)nq),
-                 o_nc = align256(o_cand + 8 * PROJ_K * (size_t)nq),
-                 o_end = align256(o_nc + 4 * (size_t)nq);
-    if (!m->d_out.ensure(o_end)) return ORBX_ERR_DEVICE;
-    uint8_t* base = m->d_in.as<uint8_t>();
-    uint8_t* ob = m->d_out.as<uint8_t>();
-    ProjLaunch L{};
-    L.mode = mode;
-    L.T = dev_feat(T, ot, base);
-    L.njobs = 1;
-    L.max_t = T->n;
-    L.qdesc = base + od;
-    L.q = (const orbx_proj_query*)(base + oq);
-    L.nq = nq;
-    for (int l = 0; l < MATCH_MAX_LEVELS; ++l)
-        L.inv_sigma2[l] = (inv_sigma2 && l < nlevels) ? inv_sigma2[l] : 0.f;
-    L.orb_dist = orb_dist;
-    L.ratio = m->prm.nnratio;
-    L.check_ori = m->prm.check_orientation;
-    L.claimed_in = claimed ? base + oc : nullptr;
-    L.qflags = qflags ? base + of : nullptr;
-    L.prefilter = (flags & ORBX_PROJ_PREFILTER) != 0;
-    L.out = (int32_t*)(ob + o_out);
-    L.top2 = (int4*)(ob + o_top);
-    L.cand = (int2*)(ob + o_cand);
-    L.ncand = (int32_t*)(ob + o_nc);
-    L.out_bin = (int8_t*)(ob + o_bin);
-    L.hist = (int32_t*)(ob + o_hist);
-    L.nmatches = (int32_t*)ob;
-    L.err = m->d_err;
-    if (nq == 0) {
-        *nmatches = 0;
-        return ORBX_OK;
-    }
-    if (!HIPOK(launch_proj(L, m->stream, &m->timer))) return ORBX_ERR_DEVICE;
-    std::vector<int32_t> res(64 + (size_t)nq);
-    s = finish(m, res.data(), ob, 4 * res.size());
-    if (s != ORBX_OK) return s;
-    std::memcpy(out, res.data() + 64, 4 * (size_t)nq);
-    *nmatches = res[0];
-    return ORBX_OK;
+    HostCall c(m->prm.device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& P = c.plan();
+    const FeatParts pt = pack_feat(P, T);
+    const size_t p_q = P.in(q, sizeof(orbx_proj_query) * (size_t)nq), p_d = P.in(qdesc, 32 * (size_t)nq),
+                 p_c = P.in_opt(claimed, (size_t)T->n), p_f = P.in_opt(qflags, (size_t)nq),
+                 p_out = P.out(out, 4 * (size_t)nq), p_n = P.out(nmatches, 4),
+                 p_err = err_part(P), p_scr = P.scratch(proj_scratch(1, (size_t)nq).end);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    return finish(c, p_err,
+                  run_proj(m, mode, dev_feat(T, pt, c.dev<uint8_t>(0)), 1, nullptr, nullptr,
+                           nullptr, c.dev<uint8_t>(p_c), c.dev<uint8_t>(p_d),
+                           c.dev<orbx_proj_query>(p_q), c.dev<uint8_t>(p_f), nq, inv_sigma2,
+                           nlevels, orb_dist, flags, c.dev<uint8_t>(p_scr), c.dev<int32_t>(p_out),
+                           c.dev<int32_t>(p_n), c.dev<int>(p_err), c.st()));
 }
 
 }  // namespace
@@ -359,7 +406,6 @@ orbx_status orbx_matcher_create(const orbx_matcher_params* params, orbx_matcher*
     orbx_matcher* m = new orbx_matcher();
     m->prm = p;
     if (!HIPOK(hipSetDevice(p.device)) ||
-        !HIPOK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking)) ||
         !HIPOK(hipMalloc((void**)&m->d_err, 64)) || !HIPOK(hipMemset(m->d_err, 0, 64)) ||
         !HIPOK(hipEventCreateWithFlags(&m->bf_done, hipEventDisableTiming)) ||
         !HIPOK(prepare_match_kernels())) {
@@ -376,19 +422,16 @@ orbx_status orbx_matcher_create(const orbx_matcher_params* params, orbx_matcher*
 orbx_status orbx_matcher_destroy(orbx_matcher* m) {
     if (!m) return ORBX_ERR_INVALID;
     (void)hipSetDevice(m->prm.device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
     if (m->have_bf) (void)hipEventSynchronize(m->bf_done);
     if (m->bf_done) (void)hipEventDestroy(m->bf_done);
-    m->d_in.release();
-    m->d_out.release();
     m->d_aux.release();
     m->d_proj.release();
     m->d_bf.release();
+    m->d_bf_db.release();
     m->d_sim3.release();
     m->d_pnp.release();
     if (m->d_err) (void)hipFree(m->d_err);
     m->timer.destroy();
-    if (m->stream) (void)hipStreamDestroy(m->stream);
     delete m;
     return ORBX_OK;
 }
@@ -443,60 +486,36 @@ orbx_status orbx_search_for_triangulation(orbx_matcher* m, const orbx_featureset
     if (nlevels > MATCH_MAX_LEVELS) return ORBX_ERR_UNSUPPORTED;
     if (!valid_feat(kf1, true, false) || !valid_feat(kf2, true, false)) return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    Packer P(m->staging);
+    HostCall c(m->prm.device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& P = c.plan();
     const orbx_featureset* fs[2] = {kf1, kf2};
     const uint8_t* fl[2] = {has_mp1, has_mp2};
-    const DbOffsets od = pack_db(P, fs, fl, 2);
-    const size_t ojob = P.reserve(4 * 4);
-    int32_t* jb = P.at<int32_t>(ojob);
-    jb[0] = 0;       // kf1
-    jb[1] = 1;       // kf2
-    jb[2] = 0;       // job_off[0]
-    jb[3] = kf1->n;  // job_off[1]
-    const size_t of = P.add(F12, 9 * sizeof(float));
+    const DbParts pd = pack_db(P, fs, fl, 2);
+    const int32_t job[4] = {0, 1, 0, kf1->n};   // kf1, kf2, job_off[0], job_off[1]
     const float epi[2] = {ex, ey};
-    const size_t oe = P.add(epi, sizeof(epi));
-    orbx_status s = upload(m);
-    if (s != ORBX_OK) return s;
-    if (!m->d_out.ensure(4 * ((size_t)kf1->n + 64))) return ORBX_ERR_DEVICE;
-    uint8_t* base = m->d_in.as<uint8_t>();
-    TriLaunch L{};
-    L.db = dev_db(od, base);
-    L.njobs = 1;
-    L.kf1 = (const int32_t*)(base + ojob);
-    L.kf2 = (const int32_t*)(base + ojob) + 1;
-    L.F12 = (const float*)(base + of);
-    L.epi = (const float*)(base + oe);
-    for (int l = 0; l < MATCH_MAX_LEVELS; ++l) {
-        L.sigma2[l] = l < nlevels ? sigma2_2[l] : 0.f;
-        L.scale[l] = l < nlevels ? scale_2[l] : 0.f;
-    }
-    L.only_stereo = only_stereo;
-    L.check_ori = m->prm.check_orientation;
-    L.job_off = (const int32_t*)(base + ojob) + 2;
-    L.out = m->d_out.as<int32_t>() + 64;
-    L.nmatches = m->d_out.as<int32_t>();
-    L.err = m->d_err;
-    if (tri_lds_bytes(L.db.max_feat) > TRI_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
-    hipEvent_t e = m->timer.start(m->stream);
-    if (!HIPOK(launch_triangulate(L, m->stream))) return ORBX_ERR_DEVICE;
-    m->timer.stop(ORBX_MK_TRIANGULATE, e, m->stream);
-    std::vector<int32_t> res((size_t)kf1->n + 64);
-    s = finish(m, res.data(), m->d_out.p, 4 * res.size());
+    const size_t p_job = P.in(job, sizeof(job)), p_F = P.in(F12, 9 * sizeof(float)),
+                 p_epi = P.in(epi, sizeof(epi)), p_m12 = P.out(nullptr, 4 * (size_t)kf1->n),
+                 p_n = P.out(nmatches, 4), p_err = err_part(P);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    const int32_t* d_job = c.dev<int32_t>(p_job);
+    const orbx_status s =
+        finish(c, p_err,
+               run_tri(m, dev_db(pd, c.dev<uint8_t>(0)), 1, d_job, d_job + 1, c.dev<float>(p_F),
+                       c.dev<float>(p_epi), sigma2_2, scale_2, nlevels, only_stereo, d_job + 2,
+                       c.dev<int32_t>(p_m12), c.dev<int32_t>(p_n), c.dev<int>(p_err), c.st()));
     if (s != ORBX_OK) return s;
     // vMatchedPairs in idx1 order (:861-869)
+    const int32_t* m12 = P.host<int32_t>(p_m12);
     int np = 0;
     for (int i = 0; i < kf1->n; ++i) {
-        const int j = res[64 + i];
-        if (j < 0) continue;
+        if (m12[i] < 0) continue;
         if (np < pair_cap) {
             pairs[2 * np] = i;
-            pairs[2 * np + 1] = j;
+            pairs[2 * np + 1] = m12[i];
         }
         ++np;
     }
-    *nmatches = res[0];
     return np > pair_cap ? ORBX_ERR_CAPACITY : ORBX_OK;
 }
 
@@ -596,11 +615,10 @@ orbx_status orbx_search_by_bow_kf_frame_batch_device(orbx_matcher* m, const orbx
     if (db->nkf < 0 || db->max_feat < 0 || db->max_feat > MAX_FEAT || f->n < 0 || f->n > MAX_FEAT)
         return ORBX_ERR_INVALID;
     if (db->nkf == 0) return ORBX_OK;
-    if (!db->feat_off || !db->keys || !db->desc || !db->flag || !db->node_off || !db->node_id ||
-        !db->node_feat_off || !db->node_feat || (f->n > 0 && (!f->keys || !f->desc)) ||
-        (f->n_nodes > 0 && (!f->node_id || !f->node_off || !f->node_feat)))
+    if (!valid_kf_db(db, DB_NODE_ID) || (f->n > 0 && (!f->keys || !f->desc)) ||
+        (f->n_nodes > 0 && (!f->node_id || !f->node_off || !f->node_feat)) ||
+        ((uintptr_t)f->desc & 15))
         return ORBX_ERR_INVALID;
-    if (((uintptr_t)db->desc & 15) || ((uintptr_t)f->desc & 15)) return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
     if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
     hipStream_t st = (hipStream_t)stream;
@@ -609,34 +627,19 @@ orbx_status orbx_search_by_bow_kf_frame_batch_device(orbx_matcher* m, const orbx
     int32_t offs[4] = {0, f->n, 0, f->n_nodes};
     if (!HIPOK(hipMemcpyAsync(m->d_aux.p, offs, sizeof(offs), hipMemcpyHostToDevice, st)))
         return ORBX_ERR_DEVICE;
-    BowLaunch L{};
-    L.A = *db;
-    L.B.nkf = 1;
-    L.B.max_feat = f->n;
-    L.B.feat_off = m->d_aux.as<int32_t>();
-    L.B.keys = f->keys;
-    L.B.desc = f->desc;
-    L.B.u_right = f->u_right;
-    L.B.flag = db->flag;   // not read for SearchByBoW(KeyFrame*, Frame&)
-    L.B.node_off = m->d_aux.as<int32_t>() + 2;
-    L.B.node_id = f->node_id;
-    L.B.node_feat_off = f->node_off;
-    L.B.node_feat = f->node_feat;
-    L.a_fixed = 0;
-    L.b_fixed = 1;
-    L.kf_kf = 0;
-    L.njobs = db->nkf;
-    L.ratio = m->prm.nnratio;
-    L.check_ori = m->prm.check_orientation;
-    L.out = d_match;
-    L.out_stride = f->n;
-    L.nmatches = d_nmatches;
-    L.err = m->d_err;
-    if (bow_lds_bytes(L) > MATCH_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
-    hipEvent_t e = m->timer.start(st);
-    if (!HIPOK(launch_bow(L, st))) return ORBX_ERR_DEVICE;
-    m->timer.stop(ORBX_MK_BOW, e, st);
-    return ORBX_OK;
+    orbx_kf_db B{};
+    B.nkf = 1;
+    B.max_feat = f->n;
+    B.feat_off = m->d_aux.as<int32_t>();
+    B.keys = f->keys;
+    B.desc = f->desc;
+    B.u_right = f->u_right;
+    B.flag = db->flag;   // not read for SearchByBoW(KeyFrame*, Frame&)
+    B.node_off = m->d_aux.as<int32_t>() + 2;
+    B.node_id = f->node_id;
+    B.node_feat_off = f->node_off;
+    B.node_feat = f->node_feat;
+    return run_bow(m, *db, B, 0, 0, db->nkf, d_match, f->n, d_nmatches, m->d_err, st);
 }
 
 orbx_status orbx_search_for_triangulation_batch_device(
@@ -649,41 +652,14 @@ orbx_status orbx_search_for_triangulation_batch_device(
     if (db->max_feat < 0 || db->max_feat > MAX_FEAT) return ORBX_ERR_INVALID;
     if (njobs == 0) return ORBX_OK;
     if (!d_kf1 || !d_kf2 || !d_F12 || !d_epi || !d_job_off || !d_match12 || !d_nmatches ||
-        !db->feat_off || !db->keys || !db->desc || !db->flag || !db->node_off || !db->node_id ||
-        !db->node_feat_off || !db->node_feat)
-        return ORBX_ERR_INVALID;
-    if ((uintptr_t)db->desc & 15) return ORBX_ERR_INVALID;
-    const bool nord = db->node_keys || db->node_desc || db->node_flag || db->node_u_right;
-    if (nord && (!db->node_keys || !db->node_desc || !db->node_flag ||
-                 (db->u_right != nullptr) != (db->node_u_right != nullptr) ||
-                 ((uintptr_t)db->node_desc & 15)))
+        !valid_kf_db(db, DB_NODE_ID | DB_NODE_ORDERED))
         return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
     if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    TriLaunch L{};
-    L.db = *db;
-    L.njobs = njobs;
-    L.kf1 = d_kf1;
-    L.kf2 = d_kf2;
-    L.F12 = d_F12;
-    L.epi = d_epi;
-    for (int l = 0; l < MATCH_MAX_LEVELS; ++l) {
-        L.sigma2[l] = l < nlevels ? sigma2[l] : 0.f;
-        L.scale[l] = l < nlevels ? scale[l] : 0.f;
-    }
-    L.only_stereo = only_stereo;
-    L.check_ori = m->prm.check_orientation;
-    L.job_off = d_job_off;
-    L.out = d_match12;
-    L.nmatches = d_nmatches;
-    L.err = m->d_err;
-    if (tri_lds_bytes(db->max_feat) > TRI_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    hipEvent_t e = m->timer.start(st);
-    if (!HIPOK(launch_triangulate(L, st))) return ORBX_ERR_DEVICE;
-    m->timer.stop(ORBX_MK_TRIANGULATE, e, st);
-    return ORBX_OK;
+    return run_tri(m, *db, njobs, d_kf1, d_kf2, d_F12, d_epi, sigma2, scale, nlevels, only_stereo,
+                   d_job_off, d_match12, d_nmatches, m->d_err, (hipStream_t)stream);
 }
+
 
 orbx_status orbx_triangulate_matches_batch_device(
     orbx_matcher* m, const orbx_kf_db* db, int32_t njobs, const int32_t* d_kf1,
@@ -847,54 +823,14 @@ orbx_status orbx_search_by_projection_batch_device(
         !frames->desc || !frames->grid_off || !frames->grid_feat || (nq > 0 && (!d_qdesc || !d_q)))
         return ORBX_ERR_INVALID;
     if (((uintptr_t)frames->desc & 15) || ((uintptr_t)d_qdesc & 15)) return ORBX_ERR_INVALID;
-    if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, max_feat, 0) > MATCH_MAX_LDS)
-        return ORBX_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lk(m->mu);
     if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    hipStream_t st = (hipStream_t)stream;
-    // scratch: hist[32 * njobs] | top2[nq] | bins[nq] | cand[nq * PROJ_K] | ncand[nq]
-    const size_t o_top = align256(128 * (size_t)njobs), o_bin = align256(o_top + 16 * (size_t)nq),
-                 o_cand = align256(o_bin + (size_t)nq),
-                 o_nc = align256(o_cand + 8 * PROJ_K * (size_t)nq),
-                 o_end = align256(o_nc + 4 * (size_t)nq);
-    if (!m->d_proj.ensure(o_end)) return ORBX_ERR_DEVICE;
-    uint8_t* sb = m->d_proj.as<uint8_t>();
-    ProjLaunch L{};
-    L.mode = mode;
-    L.T = *frames;
-    L.T.n = max_feat;
-    L.T.n_nodes = 0;
-    L.T.node_id = nullptr;
-    L.T.node_off = nullptr;
-    L.T.node_feat = nullptr;
-    L.njobs = njobs;
-    L.t_off = d_feat_off;
-    L.g_off = d_grid_off;
-    L.q_off = d_q_off;
-    L.max_t = max_feat;
-    L.qdesc = d_qdesc;
-    L.q = d_q;
-    L.nq = nq;
-    for (int l = 0; l < MATCH_MAX_LEVELS; ++l)
-        L.inv_sigma2[l] = (inv_sigma2 && l < nlevels) ? inv_sigma2[l] : 0.f;
-    L.orb_dist = orb_dist;
-    L.ratio = m->prm.nnratio;
-    L.check_ori = m->prm.check_orientation;
-    L.claimed_in = d_claimed;
-    L.out = d_match;
-    L.top2 = (int4*)(sb + o_top);
-    L.cand = (int2*)(sb + o_cand);
-    L.ncand = (int32_t*)(sb + o_nc);
-    L.out_bin = (int8_t*)(sb + o_bin);
-    L.hist = (int32_t*)sb;
-    L.nmatches = d_nmatches;
-    L.err = m->d_err;
-    if (nq == 0) {   // every job: no queries, no matches
-        if (!HIPOK(hipMemsetAsync(d_nmatches, 0, 4 * (size_t)njobs, st))) return ORBX_ERR_DEVICE;
-        return ORBX_OK;
-    }
-    if (!HIPOK(launch_proj(L, st, &m->timer))) return ORBX_ERR_DEVICE;
-    return ORBX_OK;
+    if (!m->d_proj.ensure(proj_scratch(njobs, (size_t)nq).end)) return ORBX_ERR_DEVICE;
+    orbx_featureset T = *frames;
+    T.n = max_feat;
+    return run_proj(m, mode, T, njobs, d_feat_off, d_grid_off, d_q_off, d_claimed, d_qdesc, d_q,
+                    nullptr, nq, inv_sigma2, nlevels, orb_dist, 0, m->d_proj.as<uint8_t>(), d_match,
+                    d_nmatches, m->d_err, (hipStream_t)stream);
 }
 
 orbx_status orbx_compute_distinctive_descriptors(orbx_matcher* m, const uint8_t* desc,
@@ -910,23 +846,23 @@ orbx_status orbx_compute_distinctive_descriptors(orbx_matcher* m, const uint8_t*
     const int n = off[npoints] - off[0];
     if (n > 0 && !desc) return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    Packer P(m->staging);
-    const size_t od = P.add(n > 0 ? desc + 32 * (size_t)off[0] : nullptr, 32 * (size_t)n);
-    std::vector<int32_t> rel((size_t)npoints + 1);
+    HostCall c(m->prm.device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& P = c.plan();
+    const size_t p_d = P.in(n > 0 ? desc + 32 * (size_t)off[0] : nullptr, 32 * (size_t)n),
+                 p_off = P.in(nullptr, 4 * ((size_t)npoints + 1)),
+                 p_best = P.out(best, 4 * (size_t)npoints), p_err = err_part(P);
+    int32_t* rel = P.host<int32_t>(p_off);
     for (int p = 0; p <= npoints; ++p) rel[p] = off[p] - off[0];
-    const size_t oo = P.add(rel.data(), 4 * rel.size());
-    orbx_status s = upload(m);
-    if (s != ORBX_OK) return s;
-    if (!m->d_out.ensure(4 * (size_t)npoints)) return ORBX_ERR_DEVICE;
-    uint8_t* base = m->d_in.as<uint8_t>();
-    hipEvent_t e = m->timer.start(m->stream);
-    if (!HIPOK(launch_distinctive(base + od, (const int32_t*)(base + oo),
-                                  npoints, m->d_out.as<int32_t>(), m->d_err, m->stream)))
-        return ORBX_ERR_DEVICE;
-    m->timer.stop(ORBX_MK_DISTINCTIVE, e, m->stream);
-    return finish(m, best, m->d_out.p, 4 * (size_t)npoints);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    hipEvent_t e = m->timer.start(c.st());
+    if (!HIPOK(launch_distinctive(c.dev<uint8_t>(p_d), c.dev<int32_t>(p_off), npoints,
+                                  c.dev<int32_t>(p_best), c.dev<int>(p_err), c.st())))
+        return c.finish(ORBX_ERR_DEVICE);
+    m->timer.stop(ORBX_MK_DISTINCTIVE, e, c.st());
+    return finish(c, p_err, ORBX_OK);
 }
+
 
 orbx_status orbx_compute_distinctive_descriptors_device(orbx_matcher* m, const uint8_t* d_desc,
                                                         const int32_t* d_off, int32_t npoints,
@@ -987,27 +923,22 @@ orbx_status orbx_hamming_bf_top2(orbx_matcher* m, const uint8_t* q, int32_t nq,
     if (nq == 0) return ORBX_OK;
     if (!q || !best_idx || !best_dist || !second_dist || (ndb > 0 && !db)) return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    const size_t qb = 32 * (size_t)nq, dbb = 32 * (size_t)ndb, ob = 4 * (size_t)nq;
-    if (!m->d_in.ensure(align256(qb) + std::max<size_t>(dbb, 32)) || !m->d_out.ensure(3 * align256(ob)))
-        return ORBX_ERR_DEVICE;
-    uint8_t* din = m->d_in.as<uint8_t>();
-    uint8_t* dout = m->d_out.as<uint8_t>();
-    if (!HIPOK(hipMemcpyAsync(din, q, qb, hipMemcpyHostToDevice, m->stream)) ||
-        (dbb && !HIPOK(hipMemcpyAsync(din + align256(qb), db, dbb, hipMemcpyHostToDevice, m->stream))))
-        return ORBX_ERR_DEVICE;
-    int32_t* bi = (int32_t*)dout;
-    int32_t* bd = (int32_t*)(dout + align256(ob));
-    int32_t* sd = (int32_t*)(dout + 2 * align256(ob));
-    orbx_status s = bf_run(m, din, nq, din + align256(qb), ndb, 0, bi, bd, sd, m->stream);
-    if (s != ORBX_OK) return s;
-    if (!HIPOK(hipMemcpyAsync(best_idx, bi, ob, hipMemcpyDeviceToHost, m->stream)) ||
-        !HIPOK(hipMemcpyAsync(best_dist, bd, ob, hipMemcpyDeviceToHost, m->stream)) ||
-        !HIPOK(hipMemcpyAsync(second_dist, sd, ob, hipMemcpyDeviceToHost, m->stream)) ||
-        !HIPOK(hipStreamSynchronize(m->stream)))
-        return ORBX_ERR_DEVICE;
-    return ORBX_OK;
+    HostCall c(m->prm.device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& P = c.plan();
+    const size_t dbb = 32 * (size_t)ndb, ob = 4 * (size_t)nq;
+    const size_t p_q = P.in(q, 32 * (size_t)nq), p_bi = P.out(best_idx, ob),
+                 p_bd = P.out(best_dist, ob), p_sd = P.out(second_dist, ob);
+    // the database goes from the caller's pointer to the handle's own buffer, past the host
+    // block; the call drains c.st() before it returns, so the next one may overwrite or grow it
+    if (!m->d_bf_db.ensure(std::max<size_t>(dbb, 32)) || !c.upload() ||
+        (dbb && !HIPOK(hipMemcpyAsync(m->d_bf_db.p, db, dbb, hipMemcpyHostToDevice, c.st()))))
+        return c.finish(ORBX_ERR_DEVICE);
+    return c.finish(bf_run(m, c.dev<uint8_t>(p_q), nq, m->d_bf_db.as<uint8_t>(), ndb, 0,
+                           c.dev<int32_t>(p_bi), c.dev<int32_t>(p_bd), c.dev<int32_t>(p_sd),
+                           c.st()));
 }
+
 
 const char* orbx_bf_kernel(void) { return orbx::bf_kernel_name(ORBX_BF_MFMA); }
 
@@ -1065,9 +996,8 @@ orbx_status orbx_kf_db_node_order(orbx_matcher* m, const orbx_kf_db* db, int32_t
                                   uint8_t* d_flag, void* stream) {
     if (!m || !db || n < 0 || db->nkf < 0) return ORBX_ERR_INVALID;
     if (db->nkf == 0 || n == 0) return ORBX_OK;
-    if (!db->feat_off || !db->keys || !db->desc || !db->flag || !db->node_off ||
-        !db->node_feat_off || !db->node_feat || !d_keys || !d_desc || !d_flag ||
-        (db->u_right && !d_u_right) || ((uintptr_t)d_desc & 15) || ((uintptr_t)db->desc & 15))
+    if (!valid_kf_db(db, 0) || !d_keys || !d_desc || !d_flag || (db->u_right && !d_u_right) ||
+        ((uintptr_t)d_desc & 15))
         return ORBX_ERR_INVALID;
     std::lock_guard<std::mutex> lk(m->mu);
     if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;

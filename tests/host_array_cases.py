@@ -1,6 +1,8 @@
 """The nine per-frame host-array entry points (orbx_undistort_keypoints, orbx_is_in_frustum,
 orbx_project_map_points, orbx_unproject_stereo, orbx_close_points, orbx_compute_stereo_from_rgbd,
-orbx_cvt_color, orbx_remap, orbx_bow_db_score) on one tiny case each, called straight through the C
+orbx_cvt_color, orbx_remap, orbx_bow_db_score) and the nine of a matcher handle (MATCHER_NAMES: the
+BoW, triangulation, projection, Sim3 and initialization searches, the distinctive descriptors and
+the brute-force top-2) on one tiny case each, called straight through the C
 ABI so that the caller's output arrays can sit inside sentinel-filled allocations: 64 guard bytes
 on both sides, padded rows, slots the call does not document as written.
 
@@ -11,13 +13,14 @@ The sentinel tests next to each entry point's GPU tests check `r` against that e
 restatement; tests/test_gpu_concurrency.py compares `r` across threads."""
 import ctypes
 import functools
+import threading
 
 import numpy as np
 
 from my_orb_slam2_amd import synth
 from my_orb_slam2_amd._lib import KEYPOINT_DTYPE
-from my_orb_slam2_amd.features import (DEPTH_F32, DEPTH_U16, MAP_POINT_DTYPE, PROJ_LAST_FRAME,
-                                       PROJ_QUERY_DTYPE)
+from my_orb_slam2_amd.features import (DEPTH_F32, DEPTH_U16, MAP_POINT_DTYPE, PROJ_FRAME_MAPPOINTS,
+                                       PROJ_FUSE, PROJ_LAST_FRAME, PROJ_QUERY_DTYPE, featureset_c)
 
 f32 = np.float32
 SENT = 0xA5
@@ -219,9 +222,173 @@ def _bow_db_score():
     return Case("bow_db_score", call, q=q, kfs=kfs, off=off, words=words, vals=vals)
 
 
+# ---- the matcher handle's host-array forms -------------------------------------------------------
+# 70 and 130 features, 70 queries: more than a wave, and parts that end inside and past a 256-byte
+# block (70 int32 = 280 bytes, 70 flag bytes, 130 x 32 descriptor bytes)
+N1, N2 = 70, 130
+MATCHER_NAMES = ("bow_kf_frame", "bow_kf_kf", "tri_exact", "tri_short", "proj_greedy", "proj_fuse",
+                 "proj_ex", "proj_nq0", "by_sim3", "init", "distinctive", "bf", "bf_ndb0")
+ERR_CAPACITY = -3
+_tls = threading.local()
+
+
+def _matcher(nnratio, check_ori):
+    """The calling thread's handle for these parameters: a handle is not re-entrant."""
+    from my_orb_slam2_amd import ORBmatcher
+    cache = _tls.__dict__.setdefault("matchers", {})
+    if (nnratio, check_ori) not in cache:
+        cache[nnratio, check_ori] = ORBmatcher(nnratio, check_ori)
+    return cache[nnratio, check_ori]
+
+
+def _fs(fs):
+    return ctypes.byref(featureset_c(fs))
+
+
+def _bow(kf_kf):
+    f1, f2, _ = synth.feature_pair(501, n1=N1, n2=N2, nodes=8)
+    rng = np.random.default_rng(501)
+    v1, v2 = (rng.random(N1) < 0.85).astype(np.uint8), (rng.random(N2) < 0.85).astype(np.uint8)
+
+    def call(L, c):
+        h = _matcher(*c.params)._h
+        out, n = Guarded(np.int32, N1 if kf_kf else N2), Guarded(np.int32, 1)
+        if kf_kf:
+            _ok(c.name, L.orbx_search_by_bow_kf_kf(h, _fs(c.f1), _p(c.v1), _fs(c.f2), _p(c.v2),
+                                                   _p(out.a), _p(n.a)))
+        else:
+            _ok(c.name, L.orbx_search_by_bow_kf_frame(h, _fs(c.f1), _p(c.v1), _fs(c.f2), _p(out.a),
+                                                      _p(n.a)))
+        return dict(match=out, nmatches=n)
+    return Case("bow_kf_kf" if kf_kf else "bow_kf_frame", call, f1=f1, f2=f2, v1=v1, v2=v2,
+                params=(0.75, True))
+
+
+def _tri(short):
+    """pair_cap is the number of pairs (needs the GPU: one call with room for every feature), or
+    with `short` one less; the pair array has room for the number of pairs either way."""
+    k1, k2, F, epi, _ = synth.keyframe_pair(502, n1=N1, n2=N2, nodes=8)
+    rng = np.random.default_rng(502)
+    h1, h2 = (rng.random(N1) < 0.3).astype(np.uint8), (rng.random(N2) < 0.3).astype(np.uint8)
+    scale, sigma2, _ = synth.scale_tables()
+    params = (0.6, False)
+    count, _ = _matcher(*params).SearchForTriangulation(k1, h1, k2, h2, F, epi, sigma2, scale)
+    assert count >= 2
+
+    def call(L, c):
+        pairs, n = Guarded(np.int32, (c.count, 2)), Guarded(np.int32, 1)
+        status = L.orbx_search_for_triangulation(
+            _matcher(*c.params)._h, _fs(c.k1), _p(c.h1), _fs(c.k2), _p(c.h2), _p(c.F),
+            float(c.epi[0]), float(c.epi[1]), _p(c.sigma2), _p(c.scale), len(c.sigma2), 0,
+            _p(pairs.a), c.pair_cap, _p(n.a))
+        return dict(pairs=pairs, nmatches=n, status=status)
+    return Case("tri_short" if short else "tri_exact", call, k1=k1, k2=k2, h1=h1, h2=h2,
+                F=np.ascontiguousarray(F, f32).reshape(9), epi=epi, sigma2=sigma2, scale=scale,
+                params=params, count=count, pair_cap=count - int(short))
+
+
+def _proj(name):
+    """proj_greedy: FRAME_MAPPOINTS with a claimed mask; proj_fuse: FUSE with inv_sigma2; proj_ex:
+    LAST_FRAME through _ex with no-claim queries and the prefilter flag; proj_nq0: no query, a
+    four-slot match array that stays as it is."""
+    mode = {"proj_greedy": PROJ_FRAME_MAPPOINTS, "proj_fuse": PROJ_FUSE, "proj_ex": PROJ_LAST_FRAME,
+            "proj_nq0": PROJ_FRAME_MAPPOINTS}[name]
+    f1, f2, t = synth.feature_pair(503, n1=N1, n2=N2, dup_frac=0.1)
+    q, d = synth.projection_queries(3, f1, f2, t, th=15.0,
+                                    mode_levels="kf" if mode == PROJ_FUSE else "frame")
+    rng = np.random.default_rng(503)
+    claimed = None if mode == PROJ_FUSE else (rng.random(N2) < 0.1).astype(np.uint8)
+    qflags = (rng.random(len(q)) < 0.33).astype(np.uint8) if name == "proj_ex" else None
+    isg = synth.scale_tables()[2] if mode == PROJ_FUSE else None
+    nq = 0 if name == "proj_nq0" else len(q)
+
+    def call(L, c):
+        h = _matcher(*c.params)._h
+        out, n = Guarded(np.int32, c.nq or 4), Guarded(np.int32, 1)
+        nlev = 0 if c.isg is None else len(c.isg)
+        if c.qflags is None:
+            _ok(c.name, L.orbx_search_by_projection(h, c.mode, _fs(c.f2), _p(c.claimed), _p(c.d),
+                                                    _p(c.q), c.nq, _p(c.isg), nlev, 64, _p(out.a),
+                                                    _p(n.a)))
+        else:
+            _ok(c.name, L.orbx_search_by_projection_ex(h, c.mode, _fs(c.f2), _p(c.claimed), _p(c.d),
+                                                       _p(c.q), _p(c.qflags), c.nq, _p(c.isg), nlev,
+                                                       64, 1, _p(out.a), _p(n.a)))
+        return dict(match=out, nmatches=n)
+    return Case(name, call, mode=mode, f2=f2, q=q, d=d, claimed=claimed, qflags=qflags, isg=isg,
+                nq=nq, params=(0.8, True))
+
+
+def _sim3():
+    f1, f2, t = synth.feature_pair(504, n1=N1, n2=N2)
+    q12, d1 = synth.projection_queries(1, f1, f2, t, th=7.5, mode_levels="kf")
+    inv = np.full(N2, -1, np.int64)
+    inv[t[t >= 0]] = np.nonzero(t >= 0)[0]
+    q21, d2 = synth.projection_queries(2, f2, f1, inv, th=7.5, mode_levels="kf")
+
+    def call(L, c):
+        out, n = Guarded(np.int32, N1), Guarded(np.int32, 1)
+        _ok(c.name, L.orbx_search_by_sim3(_matcher(*c.params)._h, _fs(c.f1), _fs(c.f2), _p(c.d1),
+                                          _p(c.q12), N1, _p(c.d2), _p(c.q21), N2, _p(out.a),
+                                          _p(n.a)))
+        return dict(match=out, nmatches=n)
+    return Case("by_sim3", call, f1=f1, f2=f2, q12=q12, d1=d1, q21=q21, d2=d2, params=(0.75, True))
+
+
+def _init():
+    f1, f2, _ = synth.feature_pair(505, n1=N1, n2=N2, dup_frac=0.1)
+    prev = np.ascontiguousarray(np.stack([f1.keys["x"], f1.keys["y"]], 1), f32)
+
+    def call(L, c):
+        prev, out, n = Guarded(f32, (N1, 2)), Guarded(np.int32, N1), Guarded(np.int32, 1)
+        prev.a[:] = c.prev
+        _ok(c.name, L.orbx_search_for_initialization(_matcher(*c.params)._h, _fs(c.f1), _fs(c.f2),
+                                                     _p(prev.a), c.window, _p(out.a), _p(n.a)))
+        return dict(prev_matched=prev, match=out, nmatches=n)
+    return Case("init", call, f1=f1, f2=f2, prev=prev, window=100, params=(0.9, True))
+
+
+def _distinctive():
+    from test_oracle_match import _distinctive_case
+    lead = 3                                                          # off[0] != 0
+    desc, off = _distinctive_case(506, N1, 12)
+    desc = np.concatenate([np.full((lead, 32), 0x5A, np.uint8), desc])
+
+    def call(L, c):
+        best = Guarded(np.int32, N1)
+        _ok(c.name, L.orbx_compute_distinctive_descriptors(_matcher(*c.params)._h, _p(c.desc),
+                                                           _p(c.off), N1, _p(best.a)))
+        return dict(best=best)
+    return Case("distinctive", call, desc=np.ascontiguousarray(desc),
+                off=(off + lead).astype(np.int32), params=(0.6, True))
+
+
+def _bf(ndb):
+    rng = np.random.default_rng(507)
+    q = rng.integers(0, 256, (N1, 32), dtype=np.uint8)
+    db = rng.integers(0, 256, (ndb, 32), dtype=np.uint8)
+    if ndb:
+        db[rng.choice(ndb, 40, replace=False)] = q[:40]               # exact hits and ties
+        db[7] = db[11] = q[50]
+
+    def call(L, c):
+        bi, bd, sd = Guarded(np.int32, N1), Guarded(np.int32, N1), Guarded(np.int32, N1)
+        _ok(c.name, L.orbx_hamming_bf_top2(_matcher(*c.params)._h, _p(c.q), N1,
+                                           _p(c.db) if len(c.db) else None, len(c.db), _p(bi.a),
+                                           _p(bd.a), _p(sd.a)))
+        return dict(best_idx=bi, best_dist=bd, second_dist=sd)
+    return Case("bf" if ndb else "bf_ndb0", call, q=q, db=db, params=(0.6, True))
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
-    """The case of `name` (one of NAMES), built once; "remap" needs the GPU (its rectifier)."""
+    """The case of `name` (one of NAMES or MATCHER_NAMES), built once; "remap" (its rectifier) and
+    the two "tri_*" (the number of pairs) need the GPU."""
+    if name in MATCHER_NAMES:
+        return {"bow_kf_frame": lambda: _bow(0), "bow_kf_kf": lambda: _bow(1),
+                "tri_exact": lambda: _tri(False), "tri_short": lambda: _tri(True),
+                "by_sim3": _sim3, "init": _init, "distinctive": _distinctive,
+                "bf": lambda: _bf(300), "bf_ndb0": lambda: _bf(0)}.get(name, lambda: _proj(name))()
     return {"undistort": _undistort, "frustum": _frustum, "project": _project,
             "unproject": _unproject, "close": _close, "rgbd_u16": lambda: _rgbd(DEPTH_U16),
             "rgbd_f32": lambda: _rgbd(DEPTH_F32), "cvt_color3": lambda: _cvt_color(3),

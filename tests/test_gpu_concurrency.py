@@ -299,12 +299,15 @@ def test_capture_beside_cross_stream_wait(orbx_lib, gpu):
 
 
 def _host_array_calls():
-    """The fourteen host-array entry points.  The five solvers, each on its smallest committed
+    """The fourteen handle-free host-array entry points and the nine of a matcher handle.  The five
+    solvers, each on its smallest committed
     directed case that runs at least one full iteration: name -> a function that makes the case's
     call(s) from fresh inputs and returns every array and record that comes back, as bytes, ahead of
     a count of the iterations the call ran.  The nine per-frame ones on the tiny cases of
     tests/host_array_cases.py (the count is 1): the returned bytes are the callers' whole output
-    allocations, sentinel guards and row padding included."""
+    allocations, sentinel guards and row padding included.  The matcher forms on the cases of
+    host_array_cases.MATCHER_NAMES in the same way, every calling thread with matcher handles of
+    its own (a handle is not re-entrant)."""
     import host_array_cases
     import pnp_cases
     import poseopt_cases
@@ -377,14 +380,18 @@ def _host_array_calls():
         return (nnew, st.tobytes(), x.tobytes())
 
     calls = dict(poseopt=poseopt, sim3opt=sim3opt, sim3=sim3, pnp=pnp, triangulate=triangulate)
-    for name in host_array_cases.NAMES:
+    for name in host_array_cases.NAMES + host_array_cases.MATCHER_NAMES:
+        assert name not in calls, name          # a solver and a case of one name would share an id
         calls[name] = host_array_cases.case(name).call_bytes
     return calls
 
 
 HOST_ARRAY_ENTRY_POINTS = ("poseopt", "sim3opt", "sim3", "pnp", "triangulate", "undistort",
                            "frustum", "project", "unproject", "close", "rgbd_u16", "rgbd_f32",
-                           "cvt_color3", "cvt_color4", "remap", "bow_db_score")
+                           "cvt_color3", "cvt_color4", "remap", "bow_db_score",
+                           "bow_kf_frame", "bow_kf_kf", "tri_exact", "tri_short", "proj_greedy",
+                           "proj_fuse", "proj_ex", "proj_nq0", "by_sim3", "init", "distinctive", "bf",
+                           "bf_ndb0")
 
 
 @pytest.fixture(scope="module")

@@ -335,12 +335,10 @@ def test_batch_projection(oracle_mod, orbx_lib, gpu, mode):
     assert cnt.sum() > 0
 
 
-def test_batch_projection_capacity(oracle_mod, orbx_lib, gpu):
-    """A frame above the declared max_feat is flagged (ORBX_ERR_CAPACITY at sync) and gets no
-    matches; the others are unaffected."""
+def _overflowing_batch_projection(gpu):
+    """Three frames through orbx_search_by_projection_batch_device with max_feat declared as the
+    second one's size, so the third overflows; not yet synchronised."""
     import torch
-    from oracle import matcher as om
-    from my_orb_slam2_amd._lib import OrbxError
     from my_orb_slam2_amd.matcher import DeviceFrameBatch
     frames, qs, ds = [], [], []
     for j in range(3):
@@ -359,6 +357,15 @@ def test_batch_projection_capacity(oracle_mod, orbx_lib, gpu):
     m.search_by_projection_batch_device(PROJ_FRAME_MAPPOINTS, fb, T(np.concatenate(ds)),
                                         T(np.concatenate(qs)), torch.from_numpy(q_off).to(gpu),
                                         out, cnt, orb_dist=64)
+    return m, fb, frames, qs, ds, q_off, out, cnt
+
+
+def test_batch_projection_capacity(oracle_mod, orbx_lib, gpu):
+    """A frame above the declared max_feat is flagged (ORBX_ERR_CAPACITY at sync) and gets no
+    matches; the others are unaffected."""
+    from oracle import matcher as om
+    from my_orb_slam2_amd._lib import OrbxError
+    m, _fb, frames, qs, ds, q_off, out, cnt = _overflowing_batch_projection(gpu)
     with pytest.raises(OrbxError):
         m.sync()
     out, cnt = out.cpu().numpy(), cnt.cpu().numpy()
@@ -378,3 +385,123 @@ def test_distinctive_descriptors(oracle_mod, orbx_lib, gpu):
         m = _matcher(0.6, True)
         np.testing.assert_array_equal(m.compute_distinctive_descriptors(desc, off),
                                       om.distinctive_descriptors(desc, off))
+
+
+# ---- the host-array forms through the C ABI, outputs inside sentinel-filled allocations ---------
+
+def _sentinel_call(name):
+    """tests/host_array_cases.py's case `name`, one call of it, the guards of every output."""
+    import host_array_cases as hc
+    c = hc.case(name)
+    r = c.call()
+    for k, v in r.items():
+        assert not isinstance(v, hc.Guarded) or v.guards_intact(), (name, k)
+    return c, r
+
+
+def _untouched(a):
+    import host_array_cases as hc
+    return bool((a.view(np.uint8) == hc.SENT).all())
+
+
+@pytest.mark.parametrize("kf_kf", [False, True])
+def test_host_form_sentinels_bow(oracle_mod, orbx_lib, gpu, kf_kf):
+    from oracle import matcher as om
+    c, r = _sentinel_call("bow_kf_kf" if kf_kf else "bow_kf_frame")
+    if kf_kf:
+        n_o, m_o = om.search_by_bow_kf_kf(c.f1, c.v1, c.f2, c.v2, *c.params)
+    else:
+        n_o, m_o = om.search_by_bow_kf_frame(c.f1, c.v1, c.f2, *c.params)
+    assert int(r["nmatches"].a[0]) == n_o and n_o > 0
+    np.testing.assert_array_equal(r["match"].a, m_o)
+
+
+@pytest.mark.parametrize("short", [False, True])
+def test_host_form_sentinels_triangulation(oracle_mod, orbx_lib, gpu, short):
+    """pair_cap exactly the number of pairs: ORBX_OK and every pair.  One short:
+    ORBX_ERR_CAPACITY, the first pair_cap pairs, *nmatches the true count, and the slot past
+    pair_cap as it was."""
+    import host_array_cases as hc
+    from oracle import matcher as om
+    c, r = _sentinel_call("tri_short" if short else "tri_exact")
+    n_o, p_o = om.search_for_triangulation(c.k1, c.h1, c.k2, c.h2, c.F, c.epi, c.sigma2, c.scale,
+                                           False, c.params[1])
+    assert c.count == n_o == len(p_o) and c.pair_cap == n_o - int(short)
+    assert r["status"] == (hc.ERR_CAPACITY if short else 0)
+    assert int(r["nmatches"].a[0]) == n_o
+    np.testing.assert_array_equal(r["pairs"].a[:c.pair_cap], p_o[:c.pair_cap])
+    assert _untouched(r["pairs"].a[c.pair_cap:])
+
+
+@pytest.mark.parametrize("name", ["proj_greedy", "proj_fuse", "proj_ex", "proj_nq0"])
+def test_host_form_sentinels_projection(oracle_mod, orbx_lib, gpu, name):
+    """A greedy mode with a claimed mask, FUSE with inv_sigma2, _ex with no-claim queries and
+    ORBX_PROJ_PREFILTER, and a call without queries: *nmatches = 0, match_q as it was."""
+    from oracle import matcher as om
+    c, r = _sentinel_call(name)
+    n_o, m_o = om.search_by_projection_ex(c.mode, c.f2, c.q[:c.nq], c.d[:c.nq], c.qflags, c.claimed,
+                                          c.isg, orb_dist=64, nnratio=c.params[0],
+                                          prefilter=c.qflags is not None)
+    assert int(r["nmatches"].a[0]) == n_o and (n_o > 0) == (c.nq > 0)
+    if c.nq:
+        np.testing.assert_array_equal(r["match"].a, m_o)
+    else:
+        assert _untouched(r["match"].a)
+
+
+def test_host_form_sentinels_sim3(oracle_mod, orbx_lib, gpu):
+    from oracle import matcher as om
+    c, r = _sentinel_call("by_sim3")
+    n_o, m_o = om.search_by_sim3(c.f1, c.f2, c.d1, c.q12, c.d2, c.q21)
+    assert int(r["nmatches"].a[0]) == n_o and n_o > 0
+    np.testing.assert_array_equal(r["match"].a, m_o)
+
+
+def test_host_form_sentinels_initialization(oracle_mod, orbx_lib, gpu):
+    """prev_matched changes at the matched rows only."""
+    from oracle import matcher as om
+    c, r = _sentinel_call("init")
+    p_o = c.prev.copy()
+    n_o, m_o = om.search_for_initialization(c.f1, c.f2, p_o, c.window, *c.params)
+    assert int(r["nmatches"].a[0]) == n_o and 0 < n_o < c.f1.n
+    np.testing.assert_array_equal(r["match"].a, m_o)
+    got = r["prev_matched"].a
+    np.testing.assert_array_equal(got.view(np.int32), p_o.view(np.int32))
+    np.testing.assert_array_equal(got[m_o < 0].view(np.int32), c.prev[m_o < 0].view(np.int32))
+    assert (got[m_o >= 0] != c.prev[m_o >= 0]).any()
+
+
+def test_host_form_sentinels_distinctive(oracle_mod, orbx_lib, gpu):
+    from oracle import matcher as om
+    c, r = _sentinel_call("distinctive")
+    want = om.distinctive_descriptors(c.desc, c.off)
+    assert (want >= 0).sum() > 10 and (want < 0).any()
+    np.testing.assert_array_equal(r["best"].a, want)
+
+
+@pytest.mark.parametrize("name", ["bf", "bf_ndb0"])
+def test_host_form_sentinels_bf(oracle_mod, orbx_lib, gpu, name):
+    """70 queries against 300 rows, and against none: no row is below distance 256."""
+    from oracle import matcher as om
+    c, r = _sentinel_call(name)
+    bi, bd, sd = om.bf_top2(c.q, c.db)
+    assert ((bi >= 0).all() and (bd == 0).sum() >= 40) if len(c.db) else (bi == -1).all()
+    np.testing.assert_array_equal(r["best_idx"].a, bi)
+    np.testing.assert_array_equal(r["best_dist"].a, bd)
+    np.testing.assert_array_equal(r["second_dist"].a, sd)
+
+
+def test_host_form_keeps_pending_capacity(oracle_mod, orbx_lib, gpu):
+    """The capacity word of a host-array call is its own: between an overflowing device-form call
+    and its sync, a host-array search on the same handle succeeds, equals the oracle, and leaves
+    the pending ORBX_ERR_CAPACITY for the sync."""
+    from oracle import matcher as om
+    from my_orb_slam2_amd._lib import OrbxError
+    m, _fb, frames, qs, ds, _, _, _ = _overflowing_batch_projection(gpu)
+    n_g, m_g = m.search_by_projection(PROJ_FRAME_MAPPOINTS, frames[0], qs[0], ds[0], orb_dist=64)
+    n_o, m_o = om.search_by_projection(PROJ_FRAME_MAPPOINTS, frames[0], qs[0], ds[0], None, None,
+                                       orb_dist=64, nnratio=0.8)
+    assert n_g == n_o and n_o > 0
+    np.testing.assert_array_equal(m_g, m_o)
+    with pytest.raises(OrbxError):
+        m.sync()
