@@ -84,11 +84,18 @@ __global__ __launch_bounds__(256) void k_undistort(UndistParams P, const orbx_ke
     out[i] = kp;
 }
 
-// PosInGrid (Frame.cc:407-417): round((x - mnMinX) * inv) in float, half away from zero.
+// (int) of a float as x86 cvttss2si: INT_MIN when out of range or NaN
+__device__ __forceinline__ int x86_trunc(float f) {
+    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
+}
+
+// PosInGrid (Frame.cc:407-417): round((x - mnMinX) * inv) in float, half away from zero, then
+// the reference's (int): a NaN or out-of-range coordinate becomes INT_MIN and is outside the grid
+// (a bare device conversion turns NaN into 0, which is column / row 0).
 __device__ inline int grid_cell(const orbx_keypoint& kp, int cols, int rows, float min_x,
                                 float min_y, float inv_w, float inv_h) {
-    const int px = (int)roundf((kp.x - min_x) * inv_w);
-    const int py = (int)roundf((kp.y - min_y) * inv_h);
+    const int px = x86_trunc(roundf((kp.x - min_x) * inv_w));
+    const int py = x86_trunc(roundf((kp.y - min_y) * inv_h));
     if (px < 0 || px >= cols || py < 0 || py >= rows) return -1;
     return px * rows + py;
 }
@@ -233,8 +240,7 @@ __device__ __forceinline__ bool frustum_query(const orbx_frame_pose& F, const or
     // PredictScale: ceil(log(ratio) / mfLogScaleFactor) on floats (std::log / std::ceil)
     const float ratio = __fdiv_rn(M.max_dist, dist);
     const float qf = ceilf(__fdiv_rn(glibc_logf(ratio), F.log_scale_factor));
-    // (int) of a float as x86 cvttss2si: INT_MIN when out of range or NaN
-    int lvl = (qf >= -2147483648.0f && qf < 2147483648.0f) ? (int)qf : INT_MIN;
+    int lvl = x86_trunc(qf);
     if (lvl < 0) lvl = 0;
     else if (lvl >= F.nlevels) lvl = F.nlevels - 1;
     // SearchByProjection: r = RadiusByViewingCos (viewCos > 0.998 in double), * th if th != 1
@@ -279,11 +285,6 @@ __global__ __launch_bounds__(256) void k_frustum(const orbx_frame_pose* __restri
 }
 
 // ---- RGB-D: depth at the keypoints, unprojection, the close-point pass -------------------------
-
-// (int) of a float as x86 cvttss2si: INT_MIN when out of range or NaN
-__device__ __forceinline__ int x86_trunc(float f) {
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
-}
 
 // Frame::ComputeStereoFromRGBD (src/Frame.cc:689-710) for keypoint slot i of frame f, on the raw
 // depth image: imDepth.at<float>(v, u) truncates the raw keypoint to a pixel; the sample is

@@ -1,39 +1,16 @@
 """Frame geometry around the matchers: undistortion (cvUndistortPoints, OpenCV 3.2 restated),
 image bounds and the feature grid.  CPU: the restatement against a numpy float64 reading and
-the host bounds; GPU: device undistortion and grid against the restatement."""
+the host bounds; GPU: device undistortion and grid against the restatement on uniformly random
+input.  The regimes of the kernels (cell boundaries, non-finite coordinates, counts and grid
+shapes, the copy path, in-place runs, widths and strides, ...) are in
+tests/test_gpu_frame_directed.py, on the cases of tests/frame_cases.py."""
 import numpy as np
 import pytest
 
+from frame_cases import CAMS, undistort_np
 from my_orb_slam2_amd import synth
 from my_orb_slam2_amd._lib import KEYPOINT_DTYPE
 from my_orb_slam2_amd.features import assign_features_to_grid, image_bounds
-
-CAMS = {"euroc": synth.EUROC_CAM, "tum1": synth.TUM1_CAM,
-        "rational": ((500.0, 501.0, 320.5, 240.25), (0.1, -0.05, 0.001, -0.002, 0.01, 0.02, -0.01, 0.005))}
-
-
-def undistort_np(xy, K4, dist):
-    """cvUndistortPoints (OpenCV 3.2) in numpy float64, same operation order."""
-    k = np.zeros(8)
-    d = np.asarray(dist, np.float32).astype(np.float64)
-    k[:len(d)] = d
-    fx, fy, cx, cy = (float(np.float32(v)) for v in K4)
-    ifx, ify = 1.0 / fx, 1.0 / fy
-    x = (xy[:, 0].astype(np.float64) - cx) * ifx
-    y = (xy[:, 1].astype(np.float64) - cy) * ify
-    x0, y0 = x.copy(), y.copy()
-    for _ in range(5):
-        r2 = x * x + y * y
-        icdist = (1 + ((k[7] * r2 + k[6]) * r2 + k[5]) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2)
-        dx = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x)
-        dy = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y
-        x = (x0 - dx) * icdist
-        y = (y0 - dy) * icdist
-    xx = fx * x + 0.0 * y + cx
-    yy = 0.0 * x + fy * y + cy
-    ww = 1.0 / (0.0 * x + 0.0 * y + 1.0)
-    return np.stack([(xx * ww).astype(np.float32), (yy * ww).astype(np.float32)], 1)
-
 
 def _keys(n, w=752, h=480, seed=0):
     rng = np.random.default_rng(seed)

@@ -12,6 +12,7 @@ import math
 import numpy as np
 import pytest
 
+from frame_cases import numpy_is_in_frustum
 from my_orb_slam2_amd import synth
 from my_orb_slam2_amd._lib import KEYPOINT_DTYPE
 from my_orb_slam2_amd.features import MAP_POINT_DTYPE, PROJ_QUERY_DTYPE, frame_pose
@@ -38,56 +39,6 @@ def _scene(seed, n=2000):
     bounds = (0.0, 752.0, 0.0, 480.0)
     keys, desc = _keys(seed)
     return synth.local_map_points(seed, keys, desc, n, K4, bounds, mbf=40.0)
-
-
-def numpy_is_in_frustum(F, mps, skip, cos_lim=0.5, th=1.0):
-    """Second restatement, statement by statement in numpy float32 / Python double."""
-    q = np.zeros(len(mps), PROJ_QUERY_DTYPE)
-    q["radius"] = -1.0
-    q["min_level"] = q["max_level"] = q["pred_level"] = -1
-    R, t, Ow = F["Rcw"].reshape(3, 3), F["tcw"], F["Ow"]
-    n_vis = 0
-    for i, m in enumerate(mps):
-        if skip is not None and skip[i]:
-            continue
-        P = m["pos"]
-        Pc = []
-        for r in range(3):
-            s = f32(f32(R[r, 0] * P[0]) + f32(R[r, 1] * P[1]))
-            s = f32(s + f32(R[r, 2] * P[2]))
-            Pc.append(f32(float(s) + float(t[r])))
-        if Pc[2] < f32(0):
-            continue
-        with np.errstate(divide="ignore", invalid="ignore"):
-            invz = f32(f32(1.0) / Pc[2])
-            u = f32(f32(f32(F["fx"] * Pc[0]) * invz) + F["cx"])
-            v = f32(f32(f32(F["fy"] * Pc[1]) * invz) + F["cy"])
-        if u < F["min_x"] or u > F["max_x"] or v < F["min_y"] or v > F["max_y"]:
-            continue
-        maxd, mind = f32(f32(1.2) * m["max_dist"]), f32(f32(0.8) * m["min_dist"])
-        PO = [f32(P[k] - Ow[k]) for k in range(3)]
-        ss = 0.0
-        for k in range(3):
-            ss += float(PO[k]) * float(PO[k])
-        dist = f32(math.sqrt(ss))
-        if dist < mind or dist > maxd:
-            continue
-        dot = 0.0
-        for k in range(3):
-            dot += float(PO[k]) * float(m["normal"][k])
-        vc = f32(dot / float(dist))
-        if vc < f32(cos_lim):
-            continue
-        ratio = f32(m["max_dist"] / dist)
-        qf = _libm.ceilf(f32(f32(_libm.logf(ratio)) / F["log_scale_factor"]))
-        lvl = int(qf) if -2.0 ** 31 <= qf < 2.0 ** 31 else -2 ** 31
-        lvl = 0 if lvl < 0 else min(lvl, int(F["nlevels"]) - 1)
-        r = f32(2.5) if float(vc) > 0.998 else f32(4.0)
-        if th != 1.0:
-            r = f32(r * f32(th))
-        q[i] = (u, v, f32(u - f32(F["mbf"] * invz)), f32(r * F["scale"][lvl]), lvl - 1, lvl, lvl, 0)
-        n_vis += 1
-    return q, n_vis
 
 
 def test_log_scale_factor_is_glibc_logf():
