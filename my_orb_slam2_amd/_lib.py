@@ -71,6 +71,16 @@ class BfLaunchInfo(ctypes.Structure):
                 ("merge_slice", ctypes.c_int32), ("partial_bytes", ctypes.c_int64)]
 
 
+class MapViewC(ctypes.Structure):
+    """orbx_map_view (include/orbx_localmap.h)."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ("n_kf", "n_mp", "n_cov", "n_child", "n_kfmp",
+                                                "n_obs")] +
+                [(n, ctypes.c_void_p) for n in ("kf_order", "kf_bad", "kf_parent", "kf_cov_off",
+                                                "kf_cov", "kf_child_off", "kf_child", "kf_mp_off",
+                                                "kf_mp", "mp_bad", "mp_obs_off", "mp_obs",
+                                                "mp_rec")])
+
+
 # name -> (restype, argtypes); the exported C ABI (include/orbx.h)
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -238,6 +248,15 @@ SIGNATURES = {
                                                  _vp, _vp, _vp, _vp]),
     "orbx_pose_optimization": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i]),
     "orbx_matches_to_features_batch_device": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    # include/orbx_localmap.h
+    "orbx_update_local_map_batch_device": (_i, [ctypes.POINTER(MapViewC), _i, _vp, _i, _vp, _vp, _i,
+                                                _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _sz, _vp]),
+    "orbx_local_map_search_inputs_batch_device": (_i, [ctypes.POINTER(MapViewC), _vp, _i, _vp, _vp,
+                                                       _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "orbx_update_local_map_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "orbx_update_local_map": (_i, [ctypes.POINTER(MapViewC), _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

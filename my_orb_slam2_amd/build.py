@@ -25,11 +25,12 @@ SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_matc
            "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
            "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
            "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip", "orbx_pnp.hip",
-           "orbx_host.hip"]
+           "orbx_localmap.hip", "orbx_host.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
            "orbx_host.h", "orbx_stage.h", "orbx_lm.h", "orbx_match_kernels.h", "orbx_pattern.inc",
            "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
-           "../../include/orbx_frame.h", "../../include/orbx_kfdb.h"]
+           "../../include/orbx_frame.h", "../../include/orbx_kfdb.h",
+           "../../include/orbx_localmap.h"]
 HASH_TAG = b"orbx-src:"
 
 # -ffp-contract=off: every float a*b+c in the path is two roundings, as in the x86 reference
@@ -302,6 +303,18 @@ def build_pnp_ref(force: bool = False, verbose: bool = False, sanitize: bool = F
     return _build_native(PNP_REF_SRC, _sanitized(sanitize, out, PNP_REF_BIN), _headers(INCLUDE),
                          [INCLUDE], extra=SANITIZE if sanitize else (), force=force,
                          verbose=verbose)
+
+
+# Tracking::UpdateLocalMap restated over stand-in KeyFrame / MapPoint objects
+LOCALMAP_REF_SRC = NATIVE / "localmap_ref.cpp"
+LOCALMAP_REF_BIN = NATIVE / "localmap_ref"
+
+
+def build_localmap_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on the standard library only: no liborbx and no GPU (the CPU reference of
+    orbx_update_local_map*)."""
+    return _build_native(LOCALMAP_REF_SRC, LOCALMAP_REF_BIN, [], [], flags=("-Wextra",),
+                         force=force, verbose=verbose)
 
 
 # the staging plan of the host-array entry points, on its own

@@ -30,6 +30,7 @@ from .features import (CLOSE_MAX_FEATURES, FRAME_GRID_COLS, FRAME_GRID_ROWS, PRO
                        is_in_frustum_batch_device, matches_to_features_batch_device,
                        pose_optimization_batch_device, project_map_points_batch_device,
                        rgbd_frame_geometry_batch_device, undistort_keypoints_batch_device)
+from .localmap import local_map_search_inputs, update_local_map
 from .matcher import ORBmatcher
 
 
@@ -179,6 +180,58 @@ class MonoTrackBatch:
                                  stream=stream)
         self.pose_optimization(d_poses, d_mp_of_feat, d_mps, d_mp_off, d_poses_out, d_outlier,
                                d_ngood, d_info, stream)
+
+    def local_map_offsets(self, cap_mp: int):
+        """d_mp_off of the blocks ``update_local_map`` writes: frame j's at j * cap_mp (a device
+        tensor, made once per cap_mp: ask for it ahead of a graph capture)."""
+        import torch
+        if self._lm_off is None or self._lm_off[0] != cap_mp:
+            off = torch.arange(self.batch + 1, dtype=torch.int32, device=self.dev) * cap_mp
+            self._lm_off = (cap_mp, off)
+        return self._lm_off[1]
+
+    _lm_off = None
+
+    def update_local_map(self, view, d_feat_mp, d_outlier, cap_kf: int, cap_mp: int, d_local_kf,
+                         d_n_local_kf, d_ref_kf, d_local_mp, d_n_local_mp, d_mps, d_skip,
+                         d_mp_of_feat, d_info, stream: int = 0):
+        """Tracking::UpdateLocalMap for every frame of the last ``frames`` call
+        (Tracking.cc:1288-1442) over the map snapshot `view` (LocalMapView): d_feat_mp
+        [B, kp_cap] the MapPoint id of each feature or -1 (mvpMapPoints after
+        TrackWithMotionModel), d_outlier [B, kp_cap] (or None) what ``pose_optimization`` flagged;
+        d_local_kf [B, cap_kf], d_n_local_kf [B], d_ref_kf [B] in/out.  Writes d_local_mp
+        [B, cap_mp], d_n_local_mp [B, 2], the block d_mps / d_skip [B, cap_mp] that
+        ``project_local_map`` reads at ``local_map_offsets(cap_mp)``, d_mp_of_feat [B, kp_cap]
+        (block indices) and the LOCALMAP_* words d_info [B]."""
+        v = self.ext.batch_view()
+        update_local_map(view, self.batch, d_feat_mp, self.kp_cap, v.nkp, d_outlier, cap_kf,
+                         cap_mp, d_local_kf, d_n_local_kf, d_ref_kf, d_local_mp, d_n_local_mp,
+                         d_mps, d_skip, d_mp_of_feat, d_info, stream)
+
+    def track_local_map(self, view, d_mp_desc, d_feat_mp, d_outlier_in, cap_kf: int, cap_mp: int,
+                        d_local_kf, d_n_local_kf, d_ref_kf, d_local_mp, d_n_local_mp, d_mps,
+                        d_skip, d_mp_prior, d_lm_info, d_poses, d_q, d_qdesc, d_claimed, d_match,
+                        d_nmatches, d_mp_of_feat, d_flagged, d_poses_out, d_outlier, d_ngood,
+                        d_info, d_nvisible=None, th: float = 1.0, stream: int = 0):
+        """TrackLocalMap up to and including its PoseOptimization (Tracking.cc:991-1001) on one
+        stream with no host step: ``update_local_map`` (block indices into d_mp_prior), the
+        block's descriptors (d_mp_desc [n_mp, 32] -> d_qdesc [B, cap_mp, 32]) and the claimed
+        features (d_claimed [B, kp_cap]), ``project_local_map`` from d_poses, ``search_local_points``,
+        ``matches_to_features`` with d_mp_prior as the earlier search's MapPoints (-> d_mp_of_feat),
+        then ``pose_optimization`` (d_poses_out, d_outlier, d_ngood, d_info).  A frame whose
+        d_lm_info has a LOCALMAP_REFUSED_ANY bit kept its old block: its results mean nothing."""
+        off = self.local_map_offsets(cap_mp)
+        self.update_local_map(view, d_feat_mp, d_outlier_in, cap_kf, cap_mp, d_local_kf,
+                              d_n_local_kf, d_ref_kf, d_local_mp, d_n_local_mp, d_mps, d_skip,
+                              d_mp_prior, d_lm_info, stream)
+        local_map_search_inputs(view, d_mp_desc, self.batch, d_local_mp, d_n_local_mp, cap_mp,
+                                d_mp_prior, self.kp_cap, self.ext.batch_view().nkp, d_qdesc,
+                                d_claimed, stream)
+        self.project_local_map(d_poses, d_mps, off, cap_mp, d_skip, d_q, d_nvisible, th, stream)
+        self.search_local_points(d_qdesc, d_q, off, d_match, d_nmatches, d_claimed, stream)
+        self.matches_to_features(d_match, off, cap_mp, d_mp_of_feat, d_flagged, d_mp_prior, stream)
+        self.pose_optimization(d_poses, d_mp_of_feat, d_mps, off, d_poses_out, d_outlier, d_ngood,
+                               d_info, stream)
 
     def __call__(self, images, d_qdesc, d_q, d_q_off, d_match, d_nmatches, d_claimed=None,
                  stream: int = 0, local_map=None):
