@@ -22,12 +22,13 @@ PKG = pathlib.Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "liborbx.so"
 SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_match.hip",
-           "orbx_capi.hip", "orbx_match_capi.hip", "orbx_vocab.hip", "orbx_frame.hip",
-           "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
+           "orbx_plan.hip", "orbx_capi.hip", "orbx_stereo_frame.hip", "orbx_match_capi.hip",
+           "orbx_vocab.hip", "orbx_frame.hip", "orbx_kfdb.hip", "orbx_bf.hip", "orbx_rectify.hip", "orbx_triangulate.hip",
            "orbx_poseopt.hip", "orbx_sim3.hip", "orbx_sim3opt.hip", "orbx_pnp.hip",
            "orbx_localmap.hip", "orbx_host.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
-           "orbx_host.h", "orbx_stage.h", "orbx_lm.h", "orbx_match_kernels.h", "orbx_pattern.inc",
+           "orbx_host.h", "orbx_stage.h", "orbx_layout.h", "orbx_extractor.h", "orbx_lm.h",
+           "orbx_match_kernels.h", "orbx_pattern.inc",
            "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
            "../../include/orbx_frame.h", "../../include/orbx_kfdb.h",
            "../../include/orbx_localmap.h"]
@@ -327,3 +328,15 @@ def build_staging_test(force: bool = False, verbose: bool = False) -> pathlib.Pa
     GPU."""
     return _build_native(STAGING_SRC, STAGING_BIN, [CSRC / "orbx_stage.h"], [CSRC], extra=SANITIZE,
                          force=force, verbose=verbose)
+
+
+# the extractor's output-block layouts, on their own
+LAYOUT_SRC = NATIVE / "layout_test.cpp"
+LAYOUT_BIN = NATIVE / "layout_test"
+
+
+def build_layout_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on csrc/orbx_layout.h (and the record layouts of include/orbx.h) only, with
+    -fsanitize=address,undefined: no HIP, no liborbx and no GPU."""
+    return _build_native(LAYOUT_SRC, LAYOUT_BIN, [CSRC / "orbx_layout.h", INCLUDE / "orbx.h"],
+                         [CSRC], extra=SANITIZE, force=force, verbose=verbose)

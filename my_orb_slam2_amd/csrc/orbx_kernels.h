@@ -119,10 +119,8 @@ struct ExtractLaunch {
     uint16_t* operm;   // [B][out_words] k_orient_desc's processing order (list indices)
     uint8_t* kscratch;
     long long kscratch_per_image;
-    int ncap, kcap;          // level 0 (the largest node list)
+    int ncap, kcap;          // the node and candidate arrays of the largest list
     size_t octree_lds;
-    int ncap1, kcap1;        // levels 1.. (a second launch with a smaller LDS footprint)
-    size_t octree_lds1;
     // small batches (a few octree workgroups on the chip): the large LDS budget
     int oct_small = 0, kcap_small = 0;
     size_t octree_lds_small = 0;
@@ -176,6 +174,9 @@ struct StereoLaunch {
     int16_t* sidx;
 };
 
+// raises the kernels' dynamic-LDS limits on the current device to at least these sizes
+hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t level_lds,
+                           size_t fast_lds);
 hipError_t launch_extract(const ExtractLaunch& a, hipStream_t st);
 hipError_t launch_levels(const ExtractLaunch& a, hipStream_t st, int l_begin, int l_end);
 hipError_t launch_pyr_chain(const ExtractLaunch& a, hipStream_t st);

@@ -250,7 +250,7 @@ def test_capture_beside_cross_stream_wait(orbx_lib, gpu):
     extraction waits on it from its own stream while the left handle's thread re-captures its
     graph (a new image size: new graph key).  The runtime refuses such a wait while the
     event's stream is capturing, so the library orders the two (orbx_capi.hip
-    order_after_last / extract1_graph); every call must succeed and equal the serial result.
+    order_after_last / graph_current); every call must succeed and equal the serial result.
     (The refusal was seen in test_facade_cpp's three-session facade bench, once in four runs;
     this sweep of the right thread's start over the left thread's re-capture did not reproduce
     it on the library without the ordering either, so it guards the scenario, not the timing.)"""

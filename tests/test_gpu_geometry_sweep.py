@@ -1,7 +1,7 @@
 """Image geometry and batch regimes against the CPU restatement, bit for bit.
 
 Everything the pyramid / FAST / octree / stereo kernels index with is built from the image's
-width and height (build_geometry, build_strip_tables, build_chain in orbx_capi.hip) and the
+width and height (build_geometry, build_strip_tables, build_chain in orbx_plan.hip) and the
 launch policy switches on the batch size (extract_launch).  The other parity tests run a
 handful of dataset sizes; here the sizes are picked from the table code:
 
