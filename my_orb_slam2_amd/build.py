@@ -28,7 +28,7 @@ SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_matc
            "orbx_localmap.hip", "orbx_host.hip"]
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
            "orbx_host.h", "orbx_stage.h", "orbx_layout.h", "orbx_extractor.h", "orbx_lm.h",
-           "orbx_match_kernels.h", "orbx_pattern.inc",
+           "orbx_match_kernels.h", "orbx_fast_pretest.h", "orbx_pattern.inc",
            "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
            "../../include/orbx_frame.h", "../../include/orbx_kfdb.h",
            "../../include/orbx_localmap.h"]
@@ -340,3 +340,16 @@ def build_layout_test(force: bool = False, verbose: bool = False) -> pathlib.Pat
     -fsanitize=address,undefined: no HIP, no liborbx and no GPU."""
     return _build_native(LAYOUT_SRC, LAYOUT_BIN, [CSRC / "orbx_layout.h", INCLUDE / "orbx.h"],
                          [CSRC], extra=SANITIZE, force=force, verbose=verbose)
+
+
+# k_fast's 4-pixel compass pre-test, on its own
+FAST_PRETEST_SRC = NATIVE / "fast_pretest_test.cpp"
+FAST_PRETEST_BIN = NATIVE / "fast_pretest_test"
+
+
+def build_fast_pretest_test(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on csrc/orbx_fast_pretest.h (and csrc/orbx_math.h for ORBX_HD) only, with -fsanitize=address,undefined: no HIP, no liborbx
+    and no GPU."""
+    return _build_native(FAST_PRETEST_SRC, FAST_PRETEST_BIN,
+                         [CSRC / "orbx_fast_pretest.h", CSRC / "orbx_math.h"], [CSRC],
+                         extra=SANITIZE, force=force, verbose=verbose)

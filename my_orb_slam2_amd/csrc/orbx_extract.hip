@@ -18,6 +18,7 @@
 #include "orbx_internal.h"
 #include "orbx_math.h"
 #include "orbx_kernels.h"
+#include "orbx_fast_pretest.h"
 
 namespace orbx {
 
@@ -104,114 +105,45 @@ __device__ __forceinline__ void fast_nms_kp2(const uint8_t* mb, int mw, int rr, 
 #define OD_WPE 5       // at most 96 VGPRs: five waves per SIMD (6: spills)
 __device__ __forceinline__ void lds_order() { __asm__ volatile("" ::: "memory"); }
 
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-// Pixels s_abs and s_abs+1 of a byte run held in dwords A[0..3] as two zero-extended u16s
-// (one v_perm: selector bytes s, 0x0C (= 0x00), s+1, 0x0C over the dword pair).
-__device__ __forceinline__ u16x2 pair_u16(const uint32_t* A, int s_abs) {
-    const int k = s_abs >> 2, s = s_abs & 3;
-    const uint32_t sel = (uint32_t)s | 0x0C00u | (uint32_t)(s + 1) << 16 | 0x0C000000u;
-    return __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(A[k + 1], A[k], sel));
+// ROI staging: a row arrives as the aligned source dwords from column ini_x & ~3, one per lane
+// of a 16-lane DPP row, and leaves for LDS with detection column 0 (source byte xo + 3) at
+// byte 0 of output dword 0: lane c holds output dword c - 1 (the three left border pixels are
+// in dword -1), which is source bytes 4c + xo - 1 ..: its own dword and the previous lane's for
+// xo = 0 (X0), else the next lane's and its own.  One DPP move and one v_alignbyte per dword.
+template <bool X0>
+__device__ __forceinline__ uint32_t roi_realign(uint32_t v, int xo) {
+    if (X0) return __builtin_amdgcn_alignbyte(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true), 3);  // row_shr:1
+    return __builtin_amdgcn_alignbyte(__builtin_amdgcn_update_dpp(0, v, 0x101, 0xF, 0xF, true), v, xo - 1);     // row_shl:1
 }
 
-// Pixels s_abs and s_abs+2 as two zero-extended u16s (one v_perm).  A v_and for the pairs
-// that start a dword measured slower (r5c: 77 VGPRs, 1.176 vs 1.165 ms).
-__device__ __forceinline__ uint32_t pair_u16_stride2(const uint32_t* A, int s_abs) {
-    const int k = s_abs >> 2, s = s_abs & 3;
-    const uint32_t sel = (uint32_t)s | 0x0C00u | (uint32_t)(s + 2) << 16 | 0x0C000000u;
-    return __builtin_amdgcn_perm(A[k + 1], A[k], sel);
-}
-
-// Bit positions of pixels 0..3 in the compass4_fr flag word.
-#define CMP_B0 14
-#define CMP_B1 15
-#define CMP_B2 30
-#define CMP_B3 31
-
-// The compass pre-test below on full-rate 32-bit adds and logic only.  With two pixels per
-// dword as u16 halves (pixels j and j+2) and K = (0x4000 - t - 1) in each half:
-//   n > v + t  <=>  bit 14 of n + (K - v)       n < v - t  <=>  bit 14 of (K + v) - n
-// (every half stays inside (0, 0x8000), so no carry or borrow crosses a half), and "two
-// neighbouring compass pixels beyond t on one side" is (b0 | b8) & (b4 | b12) on those bits.
-// Returns the flags of pixels 0..3 at bits CMP_B0..CMP_B3 (all other bits zero).
-template <int XO>
-__device__ __forceinline__ uint32_t compass4_fr(const uint8_t* roi0, int rp, int R, int gx, uint32_t K) {
-    // R * rp as a 24-bit multiply (v_mul_lo_u32 is a quarter-rate instruction)
-    const uint8_t* row = roi0 + __umul24((uint32_t)R, (uint32_t)rp);
-    const uint32_t* rc = (const uint32_t*)row + gx;
-    const uint32_t* rd = (const uint32_t*)(row + 3 * rp) + gx;
-    const uint32_t* ru = (const uint32_t*)(row - 3 * rp) + gx;
-    constexpr int KC = (XO + 9) >> 2;
-    constexpr int K0 = (XO + 3) >> 2, K1 = (XO + 6) >> 2;
-    uint32_t C[5], D[5], U[5];
+// Stage a ROI the prefetch does not take (more than 4 * FAST_PF2D rows) in the prefetch's lane
+// grid: lane (r, c) of 4 x 16 takes source dword c of rows r, r + 4, ..  src is the ROI's first
+// row at column ini_x & ~3, det0 the LDS byte of detection column 0 of ROI row 0, nw the
+// realigned dwords per row (the plan admits only rows of at most 16 dwords, before and after).
+__device__ __forceinline__ void stage_roi(const uint8_t* __restrict__ src, uint32_t pitch, int rows,
+                                          int xo, int ndw, int nw, uint8_t* det0, int lp, int lane) {
+    const int lr = lane >> 4, lc = lane & 15;
+    const uint32_t coff = 4u * (uint32_t)min(lc, ndw - 1);
+    uint32_t* l = (uint32_t*)det0 + lr * lp + lc - 1;
+    for (int j0 = 0; j0 < rows; j0 += 24) {
+        uint32_t v[6];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        C[k] = k <= KC ? rc[k] : 0u;
-        D[k] = (k >= K0 && k <= K1) ? rd[k] : 0u;
-        U[k] = (k >= K0 && k <= K1) ? ru[k] : 0u;
-    }
-    uint32_t F[2];
+        for (int k = 0; k < 6; ++k)   // rows past the ROI re-read its last row
+            v[k] = *(const uint32_t*)(src + __umul24((uint32_t)min(j0 + 4 * k + lr, rows - 1), pitch) + coff);
+        if (xo == 0) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int o = XO + 3 + h;                   // byte of pixel h (centre row): pixels h, h+2
-        const uint32_t V = pair_u16_stride2(C, o);
-        const uint32_t N12 = pair_u16_stride2(C, o - 3), N4 = pair_u16_stride2(C, o + 3);
-        const uint32_t N0 = pair_u16_stride2(D, o), N8 = pair_u16_stride2(U, o);
-        const uint32_t A = K - V, B = K + V;
-        const uint32_t bright = ((N0 + A) | (N8 + A)) & ((N4 + A) | (N12 + A));
-        const uint32_t dark = ((B - N0) | (B - N8)) & ((B - N4) | (B - N12));
-        F[h] = (bright | dark) & 0x40004000u;       // bits 14 (pixel h), 30 (pixel h + 2)
-    }
-    return F[0] | (F[1] << 1);
-}
-
-// One pixel pair of the compass test (u16 halves as in compass4_fr) with the pairs folded
-// first: (b0 | b8) & (b4 | b12) for "brighter than v + t" is min(max(n0, n8), max(n4, n12))
-// > v + t, and the darker side is max(min(n0, n8), min(n4, n12)) < v - t, so six packed u16
-// min / max and one add or subtract per side replace eight adds and six logic ops (r5c,
-// 512 pairs: k_fast 1.218 -> 1.165 ms one-stream, 128.8 k -> 130.2 k pairs/s).
-__device__ __forceinline__ uint32_t compass_pair_mm(uint32_t V, uint32_t N0, uint32_t N4,
-                                                    uint32_t N8, uint32_t N12, uint32_t K) {
-    const u16x2 a0 = __builtin_bit_cast(u16x2, N0), a4 = __builtin_bit_cast(u16x2, N4);
-    const u16x2 a8 = __builtin_bit_cast(u16x2, N8), a12 = __builtin_bit_cast(u16x2, N12);
-    const uint32_t mb = __builtin_bit_cast(uint32_t, __builtin_elementwise_min(
-        __builtin_elementwise_max(a0, a8), __builtin_elementwise_max(a4, a12)));
-    const uint32_t md = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(
-        __builtin_elementwise_min(a0, a8), __builtin_elementwise_min(a4, a12)));
-    return ((mb + (K - V)) | ((K + V) - md)) & 0x40004000u;
-}
-
-// The compass pre-test of 16 adjacent pixels (detection columns 16g .. 16g+15 of ROI row R),
-// the arithmetic of compass4_fr on four 4-pixel groups.  The centre row's 8 dwords and the
-// +-3 rows' 6 are read with 16-byte LDS loads (the ROI rows are 16-byte aligned).  Returns
-// bit i = pixel 16g + i passes.
-template <int XO>
-__device__ __forceinline__ uint32_t compass16_fr(const uint8_t* roi0, int rp, int R, int g, uint32_t K) {
-    const uint8_t* row = roi0 + __umul24((uint32_t)R, (uint32_t)rp);
-    const uint4* rc = (const uint4*)row + g;
-    const uint4* rd = (const uint4*)(row + 3 * rp) + g;
-    const uint4* ru = (const uint4*)(row - 3 * rp) + g;
-    const uint4 c0 = rc[0], c1 = rc[1], d0 = rd[0], u0 = ru[0];
-    const uint2 d1 = *(const uint2*)(rd + 1), u1 = *(const uint2*)(ru + 1);
-    const uint32_t C[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-    const uint32_t D[6] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y};
-    const uint32_t U[6] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y};
-    uint32_t mask = 0;
+            for (int k = 0; k < 6; ++k) v[k] = roi_realign<true>(v[k], xo);
+        } else {
 #pragma unroll
-    for (int h4 = 0; h4 < 4; ++h4) {
-        uint32_t F[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int o = XO + 3 + 4 * h4 + h;      // byte of pixel 4 h4 + h (centre row)
-            const uint32_t V = pair_u16_stride2(C, o);
-            const uint32_t N12 = pair_u16_stride2(C, o - 3), N4 = pair_u16_stride2(C, o + 3);
-            const uint32_t N0 = pair_u16_stride2(D, o), N8 = pair_u16_stride2(U, o);
-            F[h] = compass_pair_mm(V, N0, N4, N8, N12, K);
+            for (int k = 0; k < 6; ++k) v[k] = roi_realign<false>(v[k], xo);
         }
-        const uint32_t f = F[0] | (F[1] << 1);       // bits 14, 15, 30, 31: pixels 0..3
-        mask |= (((f >> 14) & 3u) | ((f >> 28) & 12u)) << (4 * h4);
+        if (lc < nw) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k)
+                if (j0 + 4 * k + lr < rows) l[(j0 + 4 * k) * lp] = v[k];
+        }
     }
-    return mask;
+    vmem_drained();
 }
 
 // Inclusive prefix sum over the wave (DPP row shifts, then the row broadcasts).
@@ -223,6 +155,53 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);   // row_bcast:15
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);   // row_bcast:31
     return v;
+}
+
+// One block of the compass pre-test (orbx_fast_pretest.h) at 4 * DW pixels per lane: detection
+// rows rb .. of the cell, (2 or 4) * 4 / DW lanes per row (lsh4: log2 of the lanes per row at
+// DW = 4), so 64 lanes take 32 / 16 rows at DW = 4, half at 2 and a quarter at 1.  Lane order,
+// then bit order within a lane, is raster order: the survivors are appended to pl in that
+// order as row << 6 | column.  det0 is detection column 0 of ROI row 0 (16-byte aligned, as
+// is the row pitch rp).  Returns the survivors of the block (wave-uniform).
+template <int DW>
+__device__ __forceinline__ int fast_pretest_block(const uint8_t* det0, int rp, int rb, int dh, int dw,
+                                                  int lsh4, int lane, uint32_t T, uint32_t T1,
+                                                  bool all, int16_t* pl) {
+    const int lsh = lsh4 + (DW == 4 ? 0 : DW == 2 ? 1 : 2);
+    const int rr = rb + (lane >> lsh), px0 = 4 * DW * (lane & ((1 << lsh) - 1));
+    const uint8_t* row = det0 + __umul24((uint32_t)(min(rr, dh - 1) + 3), (uint32_t)rp) + px0;
+    uint32_t C[DW + 2], D[DW], U[DW];
+    C[0] = *(const uint32_t*)(row - 4);
+    C[DW + 1] = *(const uint32_t*)(row + 4 * DW);
+    if constexpr (DW == 4) {
+        const uint4 c = *(const uint4*)row, d = *(const uint4*)(row + 3 * rp), u = *(const uint4*)(row - 3 * rp);
+        C[1] = c.x; C[2] = c.y; C[3] = c.z; C[4] = c.w;
+        D[0] = d.x; D[1] = d.y; D[2] = d.z; D[3] = d.w;
+        U[0] = u.x; U[1] = u.y; U[2] = u.z; U[3] = u.w;
+    } else if constexpr (DW == 2) {
+        const uint2 c = *(const uint2*)row, d = *(const uint2*)(row + 3 * rp), u = *(const uint2*)(row - 3 * rp);
+        C[1] = c.x; C[2] = c.y;
+        D[0] = d.x; D[1] = d.y;
+        U[0] = u.x; U[1] = u.y;
+    } else {
+        C[1] = *(const uint32_t*)row;
+        D[0] = *(const uint32_t*)(row + 3 * rp);
+        U[0] = *(const uint32_t*)(row - 3 * rp);
+    }
+    const int rem = min(dw - px0, 4 * DW);
+    const uint32_t colmask = rr < dh && rem > 0 ? (1u << rem) - 1u : 0u;
+    // threshold 0 has no 7-bit form: every pixel is scored
+    uint32_t f = (all ? ~0u : pt_unit<DW>(C, D, U, T, T1)) & colmask;
+    // ordered compaction: lanes are in raster order, bits within a lane too
+    const int cnt = __builtin_popcount(f);
+    const int incl = wave_incl_scan_dpp(cnt);
+    int pos = incl - cnt;
+    const int e0 = (rr << 6) | px0;
+    while (f) {
+        pl[pos++] = (int16_t)(e0 + __builtin_ctz(f));
+        f &= f - 1u;
+    }
+    return __builtin_amdgcn_readlane(incl, 63);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FAST_WPE))) void k_fast(const Geometry* __restrict__ g,
@@ -292,20 +271,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FAST_WPE)))
         int* cnt_out = ccnt + (size_t)b * g->n_cells + ci;
         const int xo = c.ini_x & 3;
         const int ndw = (xo + cols + 3) >> 2;
-        const int lp = fast_lpitch(ndw, dw);   // LDS row pitch of the ROI, dwords
+        const int lp = fast_lpitch(dw);   // LDS row pitch of the ROI, dwords
         const int rp = lp * 4;
+        // detection column 0 of ROI row 0: 16-byte aligned whatever ini_x is (roi_realign)
+        uint8_t* det0 = roi0 + FAST_ROI_LEAD;
         if (dh > 0 && dw > 0) {
+            // realigned dwords per row: the border dword and ceil((cols - 3) / 4) more; with
+            // xo > 0 the source dwords' lanes cover them
+            const int nw = xo == 0 ? (cols + 4) >> 2 : ndw;
             if (pre) {
-                if (lc2 < ndw) {
-                    uint32_t* l = (uint32_t*)roi0 + lr2 * lp + lc2;
+                if (xo == 0) {
+#pragma unroll
+                    for (int j = 0; j < FAST_PF2D; ++j) pf[j] = roi_realign<true>(pf[j], xo);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < FAST_PF2D; ++j) pf[j] = roi_realign<false>(pf[j], xo);
+                }
+                if (lc2 < nw) {
+                    uint32_t* l = (uint32_t*)det0 + lr2 * lp + lc2 - 1;
 #pragma unroll
                     for (int j = 0; j < FAST_PF2D; ++j)
                         l[4 * j * lp] = pf[j];
                 }
             } else {
                 const LevelGeom& L = g->lv[c.level];
-                stage_dwords<64>(pyr_b + L.off + (size_t)c.ini_y * L.pitch + (c.ini_x & ~3),
-                                 L.pitch, rows, ndw, (uint32_t*)roi0, lp, lane);
+                stage_roi(pyr_b + L.off + (size_t)c.ini_y * L.pitch + (c.ini_x & ~3), (uint32_t)L.pitch,
+                          rows, xo, ndw, nw, det0, lp, lane);
             }
         }
         if (k + 1 < ncw) {   // the next cell's ROI loads stay in flight during this cell
@@ -316,26 +307,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FAST_WPE)))
             if (lane == 0) *cnt_out = 0;
             continue;
         }
-        const uint8_t* roi = roi0 + xo;
+        const uint8_t* roi = det0 - 3;   // ROI column 0 of row 0
         const int mw = dw + 2;
         // zero the score map 16 bytes per lane (mb is 16-byte aligned, mb_cap a multiple of 16)
         for (int i = lane; i < ((dh + 2) * mw + 15) >> 4; i += 64) ((uint4*)mb)[i] = make_uint4(0u, 0u, 0u, 0u);
         lds_order();
-        const int gsh = ((dw + 3) >> 2) <= 8 ? 3 : 4;
-        [[maybe_unused]] const int rpp = 64 >> gsh;
-        const int sub = lane >> gsh, gx = lane & ((1 << gsh) - 1);
-        const uint32_t colmask4 = (1u << min(max(dw - 4 * gx, 0), 4)) - 1u;
-        const uint32_t colmask = ((colmask4 & 3u) << CMP_B0) | ((colmask4 & 12u) << (CMP_B2 - 2));
-        [[maybe_unused]] constexpr int PB[4] = {CMP_B0, CMP_B1, CMP_B2, CMP_B3};
-        // 16 pixels per lane: lpr lanes per detection row, 64 / lpr rows per pass; one pass
-        // is one block of the survivor list
+        // 16 pixels per lane: 2 or 4 lanes per detection row, 32 or 16 rows per block; the
+        // cell's last block takes 8 or 4 pixels per lane when its rows fit one such pass
         const int lsh = dw > 32 ? 2 : 1;
-        const int rpp16 = 64 >> lsh;
-        const int sub16 = lane >> lsh, g16 = lane & ((1 << lsh) - 1);
-        const int rem16 = dw - 16 * g16;
-        const uint32_t colmask16 = rem16 >= 16 ? 0xFFFFu : (rem16 > 0 ? (1u << rem16) - 1u : 0u);
-        const int rows_blk = rpp16;
-        (void)colmask; (void)sub; (void)gx;
+        const int rows_blk = 64 >> lsh;
         uint32_t* slot = cand + (size_t)b * g->cand_words + wslot + wpos;
         const int t_ini = g->ini_th, t_min = g->min_th;
         int base = 0;
@@ -344,56 +324,42 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FAST_WPE)))
         // minThFAST (:830-837).
         for (int pass = 0; pass < 2; ++pass) {
         const int tq = pass == 0 ? t_ini : t_min;
-        const uint32_t KT = (uint32_t)(0x4000 - tq - 1) * 0x10001u;
-        // 1. compass pre-test at tq, 4 pixels per lane: 2^gsh lanes per detection row (groups
-        //    of 4 columns), 64 >> gsh rows per pass, so lane order then pixel order within a
-        //    lane is raster order.
-        int ncorner = 0;
-        for (int rb = 0; rb < dh; rb += rows_blk) {
-            int nlist = 0;
-            {
-                const int rr = rb + sub16;
-                const int R = min(rr, dh - 1) + 3;
-                uint32_t f;
-                switch (xo) {
-                    case 0: f = compass16_fr<0>(roi0, rp, R, g16, KT); break;
-                    case 1: f = compass16_fr<1>(roi0, rp, R, g16, KT); break;
-                    case 2: f = compass16_fr<2>(roi0, rp, R, g16, KT); break;
-                    default: f = compass16_fr<3>(roi0, rp, R, g16, KT); break;
-                }
-                f &= rr < dh ? colmask16 : 0u;
-                // ordered compaction: lanes are in raster order, bits within a lane too
-                const int cnt = __builtin_popcount(f);
-                const int incl = wave_incl_scan_dpp(cnt);
-                int pos = incl - cnt;
-                const int e0 = (rr << 6) | (16 * g16);
-                int16_t* pl = list + ncorner;
-                while (f) {
-                    pl[pos++] = (int16_t)(e0 + __builtin_ctz(f));
-                    f &= f - 1u;
-                }
-                nlist = __builtin_amdgcn_readlane(incl, 63);
+        const uint32_t T = pt_T(tq), T1 = pt_T1(tq);
+        // 1. compass pre-test at tq over every block of the cell: the survivor list in raster
+        //    order
+        int nlist = 0;
+        for (int rb = 0; rb < dh;) {
+            const int rem = dh - rb;
+            if (rem <= rows_blk >> 2) {
+                nlist += fast_pretest_block<1>(det0, rp, rb, dh, dw, lsh, lane, T, T1, tq == 0, list + nlist);
+                rb += rows_blk >> 2;
+            } else if (rem <= rows_blk >> 1) {
+                nlist += fast_pretest_block<2>(det0, rp, rb, dh, dw, lsh, lane, T, T1, tq == 0, list + nlist);
+                rb += rows_blk >> 1;
+            } else {
+                nlist += fast_pretest_block<4>(det0, rp, rb, dh, dw, lsh, lane, T, T1, tq == 0, list + nlist);
+                rb += rows_blk;
             }
-            lds_order();
-            // 2. full arc score for the survivors only (dense across lanes); those above the
-            //    lower threshold are appended to the corner list, keeping raster order
-            const int lb = ncorner;
-            for (int j0 = 0; j0 < nlist; j0 += 64) {
-                const int j = j0 + lane;
-                int pe = 0, m = 0;
-                if (j < nlist) {
-                    pe = list[lb + j];
-                    const int rr = pe >> 6, cc = pe & 63;
-                    m = fast_arc_score_pk(roi, rp, rr + 3, cc + 3);
-                    mb[(rr + 1) * mw + cc + 1] = (uint8_t)max(m, 0);
-                }
-                const bool corner = j < nlist && m > tq;
-                const uint64_t cm = __ballot(corner);
-                if (corner) corners[ncorner + lanes_below(cm)] = (int16_t)pe;
-                ncorner += __popcll(cm);
-            }
-            lds_order();
         }
+        lds_order();
+        // 2. full arc score for the survivors only (dense across lanes), once over the whole
+        //    list; those above the threshold are compacted in place, keeping raster order
+        int ncorner = 0;
+        for (int j0 = 0; j0 < nlist; j0 += 64) {
+            const int j = j0 + lane;
+            int pe = 0, m = 0;
+            if (j < nlist) {
+                pe = list[j];
+                const int rr = pe >> 6, cc = pe & 63;
+                m = fast_arc_score_pk(roi, rp, rr + 3, cc + 3);
+                mb[(rr + 1) * mw + cc + 1] = (uint8_t)max(m, 0);
+            }
+            const bool corner = j < nlist && m > tq;
+            const uint64_t cm = __ballot(corner);
+            if (corner) corners[ncorner + lanes_below(cm)] = (int16_t)pe;
+            ncorner += __popcll(cm);
+        }
+        lds_order();
         // 3. cell-local NMS at iniThFAST, or at minThFAST when the cell has no keypoint at
         //    iniThFAST (:833-837); 4. ordered compaction (raster order, as cv::FAST emits).
         const int th_hi = tq, th_lo = tq;

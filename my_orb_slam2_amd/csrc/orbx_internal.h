@@ -188,17 +188,24 @@ struct Geometry {
     LevelGeom lv[ORBX_MAX_LEVELS];
 };
 
-// k_fast ROI row pitch in dwords: a multiple of 4 (16-byte aligned rows for the
-// compass's b128 reads) with room for the widest lane's reads (16 pixels per lane, 2 lanes
-// per detection row up to 32 columns, else 4).  A bank-conflict-free pitch (24 / 48 dwords)
-// was measured slower: the larger ROI costs a workgroup per CU.
+// k_fast ROI in LDS: row r's detection column 0 (ROI column 3) is at byte FAST_ROI_LEAD +
+// r * pitch, a 16-byte boundary, with the three left border pixels in the dword before it (the
+// last dword of the previous row's pitch).  The row pitch in dwords is a multiple of 4 with
+// room for the widest lane's reads (16 pixels per lane and the dword after them, 2 lanes per
+// detection row up to 32 columns, else 4) and the next row's border dword.  A bank-conflict-
+// free pitch (24 / 48 dwords) was measured slower: the larger ROI costs a workgroup per CU.
+#define FAST_ROI_LEAD 16
 #define FAST_NC 4        // k_fast cells per wave at large batches (the next cell's ROI loads
                          // overlap this cell's work); small batches take fewer
 #define FAST_PF2D 10     // its rows per lane: ROIs up to 40 rows are prefetched
-__host__ __device__ inline int fast_lpitch(int ndw, int dw) {
+__host__ __device__ inline int fast_lpitch(int dw) {
     const int lpr = dw > 32 ? 4 : 2;
-    const int need = ndw > 4 * lpr + 4 ? ndw : 4 * lpr + 4;
-    return (need + 3) & ~3;
+    return (4 * lpr + 2 + 3) & ~3;   // detection dwords, the one after them, the border dword
+}
+// LDS bytes of a rows-row ROI (a prefetched ROI writes all 4 * FAST_PF2D rows).
+__host__ __device__ inline int fast_roi_bytes(int rows, int dw) {
+    const int rows_w = rows > 4 * FAST_PF2D ? rows : 4 * FAST_PF2D;
+    return FAST_ROI_LEAD + rows_w * fast_lpitch(dw) * 4;
 }
 
 // Packed candidate / octree survivor: x, y relative to (minBorderX, minBorderY).

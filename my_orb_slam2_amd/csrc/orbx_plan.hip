@@ -377,18 +377,16 @@ orbx_status build_geometry(const orbx_extractor_params& prm, int W, int H, Extra
                     c.slot = (int32_t)cand;
                     cand += c.cap;
                     lcap += c.cap;
-                    // k_fast stages the ROI as aligned dwords: <= cols + 6 bytes per row
-                    {
-                        const int lpc = std::max((c.cols + 6 + 3) / 4, fast_lpitch((3 + c.cols + 3) / 4, dw));
-                        // a prefetched ROI writes all 4 * FAST_PF2D rows
-                        const int rows_w = std::max((int)c.rows, 4 * FAST_PF2D);
-                        G.max_roi_bytes = std::max(G.max_roi_bytes, rows_w * lpc * 4);
-                    }
+                    // k_fast stages the ROI with detection column 0 on a 16-byte boundary
+                    G.max_roi_bytes = std::max(G.max_roi_bytes, fast_roi_bytes(c.rows, dw));
                     if (dh > 0 && dw > 0) {
                         G.max_mbuf_bytes = std::max(G.max_mbuf_bytes, ((dh + 2) * (dw + 2) + 3) & ~3);
                         G.max_cell_px = std::max(G.max_cell_px, dh * dw);
                     }
-                    if (dw > 64 || dh > 511) return ORBX_ERR_UNSUPPORTED;   // k_fast lane mapping
+                    // k_fast lane mapping; its staging takes a ROI row, before and after the
+                    // realignment, in 16 lanes of a dword each (a 30-pixel cell target gives
+                    // cols <= 59)
+                    if (dw > 64 || dh > 511 || c.cols > 60) return ORBX_ERR_UNSUPPORTED;
                     p.cells.push_back(c);
                 }
             }
