@@ -303,7 +303,7 @@ const char* orbx_kernel_name(int id);
 /* The launch geometry a batched call of `batch` images would use after
  * orbx_extractor_prepare (diagnostics; the parity tests pin the benchmarked geometry with
  * it): strip_rows[nlevels] = output rows per k_level strip walk of each level (0: the level
- * runs the tiled kernel), *stereo_split = workgroups per pair of a stereo launch over batch/2
+ * runs the plain fallback kernels), *stereo_split = workgroups per pair of a stereo launch over batch/2
  * pairs (orbx_stereo_frames_device). */
 orbx_status orbx_extractor_launch_info(const orbx_extractor* h, int batch, int* strip_rows,
                                        int* stereo_split);

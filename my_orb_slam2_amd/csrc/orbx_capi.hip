@@ -122,7 +122,7 @@ orbx_status ensure_workspace(orbx_extractor* h, int W, int H, int batch) {
             return ORBX_ERR_DEVICE;
         if (!HIPOK(hipStreamSynchronize(st))) return ORBX_ERR_DEVICE;
         if (!HIPOK(prepare_kernels(std::max(h->octree_lds, h->octree_lds_small), h->stereo_lds,
-                                   std::max(h->level_lds, (size_t)h->hg.chain_lds), fast_lds_bytes(h->hg))))
+                                   (size_t)h->hg.chain_lds, fast_lds_bytes(h->hg))))
             return ORBX_ERR_DEVICE;
         h->have_geom = true;
         h->cap_batch = 0;
@@ -175,7 +175,6 @@ ExtractLaunch extract_launch(orbx_extractor* h, const uint8_t* d_imgs, const uin
     a.d_imgs = d_imgs;
     a.d_imgs2 = d_imgs2 ? d_imgs2 : d_imgs;
     a.split = d_imgs2 ? split : batch;
-    a.level_lds = h->level_lds;
     a.stride = stride;
     a.batch_stride = batch_stride;
     a.batch = batch;

@@ -87,10 +87,8 @@ __device__ __forceinline__ void fast_nms_kp2(const uint8_t* mb, int mw, int rr, 
     k_lo = base && m > t_lo && supp <= t_lo;
 }
 
-#define FAST_PF 6      // prefetched ROI dwords per lane (larger ROIs are staged directly)
-                     // 2.304 -> 2.288 ms per step one-stream (r4e A/B, B=512)
 #define FAST_WPE 6     // minimum waves per SIMD requested from the register allocator (80 VGPRs)
-#define OCT_NT 128         // k_octree threads per list (64 / 128 / 256 / 512) at large batches.
+#define OCT_NT 128         // k_octree threads per list at large batches.
                            // Round 5, 512 pairs (r5v2 / r5v3): 128 threads 0.306 ms one-stream
                            // against 0.265 for 256, but the scheduled step is 1 % faster
                            // (128.5-128.9 k vs 127.2-127.5 k pairs/s): the smaller workgroups
@@ -1420,10 +1418,8 @@ hipError_t launch_extract(const ExtractLaunch& a, hipStream_t st) {
                           (const int*)a.ccnt, (const uint32_t*)a.cand, a.ocnt, a.okp,         \
                           operm, a.kscratch, a.kscratch_per_image, ncap, kcap, level_base,   \
                           a.oct_small ? 0 : 1)
-        if (nt == 64) ORBX_OCT_LAUNCH(64);
-        else if (nt == 128) ORBX_OCT_LAUNCH(128);
-        else if (nt == 512) ORBX_OCT_LAUNCH(512);
-        else ORBX_OCT_LAUNCH(256);
+        if (nt == OCT_NT) ORBX_OCT_LAUNCH(OCT_NT);
+        else ORBX_OCT_LAUNCH(OCT_NT_SMALL);
 #undef ORBX_OCT_LAUNCH
     };
     auto orient = [&](int blk0, int nblk, int nkp_blk, hipStream_t s) {
@@ -1516,13 +1512,13 @@ size_t octree_lds_bytes(int ncap, int kcap, bool packed) {
 
 namespace orbx {
 hipError_t prepare_stereo(size_t lds);
-hipError_t prepare_level(size_t lds);
+hipError_t prepare_pyr_chain(size_t lds);
 // Dynamic LDS above 64 KiB needs the per-kernel opt-in (gfx950 has 160 KiB per CU).
 // hipFuncSetAttribute acts on the current device, so the sizes already set are kept per device
 // (the caller has made the handle's device current) and only ever raised (to the largest size
 // any handle on that device needs), under a lock: handles on several host threads may prepare
 // concurrently.
-hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t level_lds,
+hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t chain_lds,
                            size_t fast_lds) {
     static std::mutex mu;
     static size_t have_dev[ORBX_MAX_DEVICES][4] = {};
@@ -1533,8 +1529,7 @@ hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t level_ld
     std::lock_guard<std::mutex> lk(mu);
     size_t* have = have_dev[dev];
     if (octree_lds > have[0]) {
-        for (const void* k : {(const void*)k_octree<256>, (const void*)k_octree<64>,
-                              (const void*)k_octree<128>, (const void*)k_octree<512>})
+        for (const void* k : {(const void*)k_octree<OCT_NT>, (const void*)k_octree<OCT_NT_SMALL>})
             if (e == hipSuccess)
                 e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)octree_lds);
         if (e == hipSuccess) have[0] = octree_lds;
@@ -1544,9 +1539,9 @@ hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t level_ld
                                 (int)fast_lds);
         if (e == hipSuccess) have[1] = fast_lds;
     }
-    if (e == hipSuccess && level_lds > have[2]) {
-        e = prepare_level(level_lds);
-        if (e == hipSuccess) have[2] = level_lds;
+    if (e == hipSuccess && chain_lds > have[2]) {
+        e = prepare_pyr_chain(chain_lds);
+        if (e == hipSuccess) have[2] = chain_lds;
     }
     if (e == hipSuccess && stereo_lds > have[3]) {
         e = prepare_stereo(stereo_lds);

@@ -26,9 +26,9 @@ struct ExtractPlan {
     Geometry hg;
     std::vector<CellDesc> cells;
     std::vector<int16_t> rtab;
-    std::vector<uint8_t> ltab;   // k_level per-tile tables (LevelColTab / LevelRowTab)
+    std::vector<uint8_t> ltab;   // k_level_strip / k_pyr_chain tables (StripLane, ChainRect, ...)
     int ncap = 0, kcap = 0;
-    size_t octree_lds = 0, stereo_lds = 0, level_lds = 0;
+    size_t octree_lds = 0, stereo_lds = 0;
     int kcap_small = 0;               // small-batch octree: candidates held in LDS
     size_t octree_lds_small = 0;
     long long kscratch_per_image = 0;

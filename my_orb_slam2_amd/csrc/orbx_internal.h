@@ -43,18 +43,15 @@ struct LevelGeom {
     int area2;              // resize at exactly 1/2: INTER_AREA 2x2 fast path
     int copy;               // resize to the same size: plain copy
     int patch_size;         // (int)(31*scale)
-    int ntx, nty;           // k_level tiles of this level
-    int ctab, rowtab;       // k_level: byte offsets of the level's column / row tables
     int stereo_win;         // k_stereo: row half-window of the octave-l buckets (ceil(2 scale) + 2)
     // k_level_strip (orbx_pyramid.hip): column strips walked row by row
-    int strip;              // 1: this level runs k_level_strip, 0: the tiled k_level
+    int strip;              // 1: this level runs k_level_strip, 0: k_level_plain + k_blur_plain
     int snh;                // half-wave strips across (SW_PX output pixels each)
     int snw;                // waves across (ceil(snh / 2)); the strip height (rows per strip)
                             // is a launch argument chosen per call from its batch size
     int stab, srow;         // byte offsets of the strip lane table / row table in ltab
 };
 
-// k_level tiling (orbx_pyramid.hip): 128 x 32 output tile, staged with a 4-byte / 3-row halo.
 #define OD_NK 8               // keypoints per wave in k_orient_desc (<= 64)
 // k_octree: one launch over all levels under one LDS budget per workgroup, the
 // blocks in level-major order so the long level-0 lists start first and the shorter lists of
@@ -81,28 +78,6 @@ __host__ __device__ inline uint32_t blur_off(int x, int y, int pitch, int h) {
     return (uint32_t)(y >> 2) * (uint32_t)(4 * pitch) + ((uint32_t)(x >> 4) << 6) +
            ((uint32_t)(y & 3) << 4) + (uint32_t)(x & 15);
 }
-#define LT_W 128              // output tile width  (32 groups of 4)
-#define LT_H 32               // output tile height
-#define LT_G 34               // halo groups per row: x = X0-4 .. X0+131
-#define LT_HR (LT_H + 6)      // halo rows: y = Y0-3 .. Y0+LT_H+2
-
-// Per-tile-column tables of k_level (host-built, build_geometry): the staged source window's
-// x range and, per halo group of 4 pixels, the source columns, flags and resize alphas.
-struct LevelColTab {
-    int32_t x0, ww, pad0, pad1;
-    uint32_t cgrp[2 * LT_G];  // 4 x u16 source column (window relative)
-    uint32_t cinf[LT_G];      // 2 bits/pixel (xmax, rsimd) | 0x100 contig | 0x200 simple
-                              // | 0x1000 << j: pixel j's taps sit in dwords 1-2
-    uint32_t pad2[2];
-    uint32_t calp[4 * LT_G];  // 4 x (alpha0 | alpha1 << 16); (2048, 0) right of xmax
-    uint32_t csel[4 * LT_G];  // 4 x v_perm selector of the pixel's 2 taps (see k_level)
-};
-// Per-tile-row tables: the window's y range and, per halo row, source rows and betas.
-struct LevelRowTab {
-    int32_t y0, wh, pad0, pad1;
-    uint32_t rinf[2 * LT_HR]; // (ry0 | ry1 << 16, beta0 | beta1 << 16)
-};
-
 // k_pyr_chain: one workgroup per (tile, image) computes its tile of every level.  Per level:
 // the owned output rectangle [ox0, ox1) x [oy0, oy1) (level pixels and blurred pixels it
 // stores; the owned rectangles of a level partition it, ox0 a multiple of 4) and the
@@ -175,8 +150,6 @@ struct Geometry {
     int umax[16];           // src/ORBextractor.cc:454-469
     int ini_th, min_th;     // FAST thresholds, clamped to [0, 255]
     int stereo_ob;          // k_stereo bucket groups: nlevels (octave, row), or 1 (row) if LDS is short
-    int ltw, lth;           // k_level output tile
-    int win_cap;            // k_level: largest staged source window (bytes)
     // k_pyr_chain (small batches: every level in one launch, see orbx_pyramid.hip)
     int chain_ok;           // 1: every level l >= 1 is INTER_LINEAR and the LDS fits
     int chain_gx, chain_gy; // tiles per image (chain_gx * chain_gy workgroups per image)

@@ -45,15 +45,7 @@ struct KernelTimer {
         if (!b) return;
         (void)hipEventRecord(b, st);
         pending.push_back(Rec{id, a, b});
-        last = b;
     }
-    // Start of a kernel launched right after the previous timed one on the same stream: the
-    // previous stop event doubles as this start (one marker between two kernels, not two).
-    hipEvent_t start_after(hipStream_t st) {
-        if (!on) return nullptr;
-        return last ? last : start(st);
-    }
-    hipEvent_t last = nullptr;
     // the last recorded interval counted a second time under `id` (a sub-total)
     void alias(int id) {
         if (!on || pending.empty()) return;
@@ -71,7 +63,6 @@ struct KernelTimer {
         }
         pending.clear();
         used = 0;
-        last = nullptr;
     }
     void destroy() {
         for (auto e : pool) (void)hipEventDestroy(e);
@@ -103,13 +94,12 @@ struct ExtractLaunch {
     const Geometry* dg;        // device copy
     const CellDesc* cells;     // device
     const int16_t* rtab;       // device
-    const uint8_t* ltab;       // device: k_level per-tile tables
+    const uint8_t* ltab;       // device: k_level_strip / k_pyr_chain tables
     const uint8_t* d_imgs;      // images [0, split)
     const uint8_t* d_imgs2;     // images [split, batch) (stereo: right views)
     int split;
     size_t stride, batch_stride;
     int batch;
-    size_t level_lds;
     uint8_t* pyr;
     uint8_t* blur;
     int* ccnt;
@@ -175,12 +165,11 @@ struct StereoLaunch {
 };
 
 // raises the kernels' dynamic-LDS limits on the current device to at least these sizes
-hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t level_lds,
+hipError_t prepare_kernels(size_t octree_lds, size_t stereo_lds, size_t chain_lds,
                            size_t fast_lds);
 hipError_t launch_extract(const ExtractLaunch& a, hipStream_t st);
 hipError_t launch_levels(const ExtractLaunch& a, hipStream_t st, int l_begin, int l_end);
 hipError_t launch_pyr_chain(const ExtractLaunch& a, hipStream_t st);
-size_t level_lds_bytes(int ltw, int lth, int win_cap);
 size_t fast_lds_bytes(const Geometry& g);
 size_t octree_lds_bytes(int ncap, int kcap, bool packed);
 int octree_threads(int batch, int nlevels);   // k_octree threads per list of a call

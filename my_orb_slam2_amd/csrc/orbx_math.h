@@ -11,7 +11,7 @@
 // sincosf_data.c), the double-precision polynomial algorithm.  On x86-64 glibc dispatches
 // by ifunc to a copy built with -mfma (`__sinf_fma`) on FMA-capable CPUs; that copy
 // contracts every `a + b*c` of the polynomial and the range reduction into an fma.  The
-// port below writes those fmas explicitly (ORBX_GLIBC_FMA=1, default) so the result does
+// port below writes those fmas explicitly (glibc_madd) so the result does
 // not depend on the compiler's contraction mode.  tests/test_libm_port.py checks the
 // host build of this port against the real glibc over every float in [0, 2*pi).
 //
@@ -26,8 +26,6 @@
 #else
 #define ORBX_HD static inline
 #endif
-
-#define ORBX_GLIBC_FMA 1
 
 namespace orbx {
 
@@ -135,12 +133,9 @@ ORBX_HD float glibc_cosf(float y) {
     return __builtin_nanf("");
 }
 
-// OpenCV cvRound(float)/cvRound(double) on x86-64 SSE2: cvtss2si / cvtsd2si with the
-// default MXCSR, i.e. round-half-to-even.
+// OpenCV cvRound(float) on x86-64 SSE2: cvtss2si with the default MXCSR, i.e.
+// round-half-to-even.
 ORBX_HD int cv_round(float v) { return (int)rintf(v); }
-ORBX_HD int cv_round_d(double v) { return (int)rint(v); }
-ORBX_HD int cv_floor(float v) { return (int)floorf(v); }
-ORBX_HD int cv_ceil(float v) { return (int)ceilf(v); }
 
 // OpenCV 3.2 cv::fastAtan2 (core/src/mathfuncs.cpp): octant reduction + 7th-order odd
 // polynomial in degrees, every operation a separate float rounding.

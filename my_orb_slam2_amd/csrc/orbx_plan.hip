@@ -31,16 +31,6 @@ int reflect101_h(int p, int len) {
     return p;
 }
 
-void reflected_range_h(int lo, int hi, int len, int& mn, int& mx) {
-    mn = 1 << 30;
-    mx = -1;
-    for (int p = lo; p <= hi; ++p) {
-        const int r = reflect101_h(p, len);
-        mn = std::min(mn, r);
-        mx = std::max(mx, r);
-    }
-}
-
 int vresize_simd_end(int width) {
     int x = 0;
     for (; x <= width - 16; x += 16) {}
@@ -62,8 +52,8 @@ static int strip_default(const LevelGeom& lv, int nimg, int ncu) {
 }
 
 // k_level_strip tables of level l (StripLane per half-strip lane, rows -3 .. h+2); the level
-// keeps the tiled kernel (strip = 0) for modes 1 / 2 or when a group's taps do not fit the
-// 8-byte window the strip kernel reads
+// takes the plain kernels (strip = 0) for modes 1 / 2 or when a group's taps do not fit the
+// 8-byte window the strip kernel reads.  Level 0 (mode 0) always strips.
 void build_strip_tables(ExtractPlan& p, int l, int mode, const int16_t* xofs,
                         const int16_t* alpha, const int16_t* yofs, const int16_t* beta) {
     Geometry& G = p.hg;
@@ -85,10 +75,10 @@ void build_strip_tables(ExtractPlan& p, int l, int mode, const int16_t* xofs,
             if (mode == 0) {
                 const int mn = std::min(std::min(xr[0], xr[1]), std::min(xr[2], xr[3]));
                 e.base = (uint32_t)mn;
-                for (int j = 0; j < 4; ++j) {
-                    if (xr[j] - mn > 4) return;   // + the row address's low 2 bits <= 7
-                    e.sel |= (uint32_t)(xr[j] - mn) << (8 * j);
-                }
+                // offsets <= 3 (+ the row address's low 2 bits <= 7, the bytes one v_perm reads):
+                // BORDER_REFLECT_101 moves by at most 1 per column, so the four columns of a
+                // group lie within 3 of each other at every width
+                for (int j = 0; j < 4; ++j) e.sel |= (uint32_t)(xr[j] - mn) << (8 * j);
             } else {
                 int sx[4];
                 for (int j = 0; j < 4; ++j) sx[j] = xofs[xr[j]];
@@ -307,7 +297,7 @@ void compute_tables(const orbx_extractor_params& prm, ExtractPlan& p) {
 orbx_status build_geometry(const orbx_extractor_params& prm, int W, int H, ExtractPlan& p) {
     Geometry& G = p.hg;
     memset(&G, 0, sizeof(G));
-    // k_level's row pass folds the symmetric Gaussian taps (getGaussianKernel is symmetric)
+    // the blur's column pass folds the symmetric Gaussian taps (getGaussianKernel is symmetric)
     for (int i = 0; i < 3; ++i)
         if (p.taps[i] != p.taps[6 - i]) return ORBX_ERR_UNSUPPORTED;
     p.cells.clear();
@@ -467,133 +457,18 @@ orbx_status build_geometry(const orbx_extractor_params& prm, int W, int H, Extra
             }
         }
     }
-    // k_level tiles (128 x 32): per tile column / row the staged source window and the
-    // group / row tables the kernel reads (LevelColTab / LevelRowTab), and the largest window
-    G.ltw = LT_W;
-    G.lth = LT_H;
-    G.win_cap = 16;
+    // k_level_strip tables of the levels that take the strip walk
     p.ltab.clear();
     for (int l = 0; l < L; ++l) {
-        LevelGeom& lv = G.lv[l];
-        lv.ntx = (lv.w + G.ltw - 1) / G.ltw;
-        lv.nty = (lv.h + G.lth - 1) / G.lth;
+        const LevelGeom& lv = G.lv[l];
         const int mode = l == 0 ? 0 : (lv.copy ? 1 : (lv.area2 ? 2 : 3));
-        const LevelGeom& S = G.lv[l > 0 ? l - 1 : 0];
         const int16_t* xofs = p.rtab.data() + lv.rtab_off;
         const int16_t* alpha = xofs + lv.w;
         const int16_t* yofs = alpha + 2 * lv.w;
         const int16_t* beta = yofs + lv.h;
-        std::vector<LevelColTab> ct(lv.ntx);
-        std::vector<LevelRowTab> rt(lv.nty);
-        for (int tx = 0; tx < lv.ntx; ++tx) {
-            const int X0 = tx * G.ltw, vw = std::min(G.ltw, lv.w - X0);
-            int x0, x1;
-            if (mode == 3) {
-                int mnx, mxx;
-                reflected_range_h(X0 - 3, X0 + vw + 2, lv.w, mnx, mxx);
-                x0 = xofs[mnx] & ~3;
-                x1 = std::min((int)xofs[mxx] + 1, S.w - 1);
-            } else {
-                x0 = std::max(X0 - 4, 0);
-                x1 = std::min(X0 + G.ltw + 3, lv.w - 1);
-            }
-            LevelColTab& c = ct[tx];
-            memset(&c, 0, sizeof(c));
-            c.x0 = x0;
-            c.ww = x1 - x0 + 1;
-            for (int q = 0; q < LT_G; ++q) {
-                int sx[4];
-                uint32_t fl = 0, al[4] = {0, 0, 0, 0};
-                for (int j = 0; j < 4; ++j) {
-                    const int xr = reflect101_h(X0 - 4 + 4 * q + j, lv.w);
-                    if (mode == 3) {
-                        sx[j] = xofs[xr] - x0;
-                        al[j] = (uint32_t)(uint16_t)alpha[2 * xr] |
-                                ((uint32_t)(uint16_t)alpha[2 * xr + 1] << 16);
-                        fl |= (uint32_t)((xr < lv.xmax ? 1 : 0) | (xr < lv.rsimd_end ? 2 : 0))
-                              << (2 * j);
-                    } else {
-                        sx[j] = (mode == 2) ? xr : xr - (X0 - 4);   // window column (modes 0/1)
-                    }
-                    // pixels of a group outside the needed halo may reflect anywhere: keep
-                    // their (unused) reads inside the window
-                    if (mode == 3) sx[j] = std::min(std::max(sx[j], 0), std::max(c.ww - 1, 0));
-                    else if (mode != 2) sx[j] = std::min(std::max(sx[j], 0), LT_G * 4 - 1);
-                }
-                const bool contig = sx[1] == sx[0] + 1 && sx[2] == sx[0] + 2 &&
-                                    sx[3] == sx[0] + 3 && (sx[0] & 3) == 0;
-                const bool simple = sx[1] >= sx[0] && sx[2] >= sx[1] && sx[3] >= sx[2] &&
-                                    sx[3] - sx[0] <= 6;
-                c.cgrp[2 * q] = (uint32_t)sx[0] | ((uint32_t)sx[1] << 16);
-                c.cgrp[2 * q + 1] = (uint32_t)sx[2] | ((uint32_t)sx[3] << 16);
-                for (int j = 0; j < 4; ++j) {
-                    // simple groups: pixel j's taps are bytes k, k+1 of the 8 bytes from sx0
-                    // (the kernel aligns the window to sx0 with v_alignbyte); v_perm picks
-                    // them as u16s
-                    const int k = std::min(std::max(sx[j] - sx[0], 0), 6);
-                    c.csel[4 * q + j] = (uint32_t)k | (0x0Cu << 8) |
-                                        ((uint32_t)(k + 1) << 16) | (0x0Cu << 24);
-                    // right of xmax HResizeLinear uses S[sx] * 2048: the same dot product
-                    // with alphas (2048, 0)
-                    if (mode == 3 && !((fl >> (2 * j)) & 1u)) al[j] = 2048u;
-                }
-                // simple groups carry 16 x the alphas (<= 32768 still a u16): the kernel's
-                // dot product then yields 16 h, whose low byte cleared is (h >> 4) << 8
-                if (mode == 3 && simple)
-                    for (int j = 0; j < 4; ++j)
-                        al[j] = ((al[j] & 0xFFFFu) << 4) | (((al[j] >> 16) << 4) << 16);
-                c.cinf[q] = fl | (contig ? 0x100u : 0u) | (simple ? 0x200u : 0u);
-                for (int j = 0; j < 4; ++j) c.calp[4 * q + j] = al[j];
-            }
-        }
-        for (int ty = 0; ty < lv.nty; ++ty) {
-            const int Y0 = ty * G.lth, vh = std::min(G.lth, lv.h - Y0);
-            int y0, y1;
-            if (mode == 3) {
-                int mny, mxy;
-                reflected_range_h(Y0 - 3, Y0 + vh + 2, lv.h, mny, mxy);
-                y0 = std::min(std::max((int)yofs[mny], 0), S.h - 1);
-                y1 = std::min(std::max((int)yofs[mxy] + 1, 0), S.h - 1);
-            } else {
-                y0 = std::max(Y0 - 3, 0);
-                y1 = std::min(Y0 + G.lth + 2, lv.h - 1);
-            }
-            LevelRowTab& r = rt[ty];
-            memset(&r, 0, sizeof(r));
-            r.y0 = y0;
-            r.wh = y1 - y0 + 1;
-            for (int k = 0; k < LT_HR; ++k) {
-                const int yr = reflect101_h(Y0 - 3 + k, lv.h);
-                if (mode == 3) {
-                    const int sy = yofs[yr];
-                    const uint32_t y0r = (uint32_t)(std::min(std::max(sy, 0), S.h - 1) - y0);
-                    const uint32_t y1r = (uint32_t)(std::min(std::max(sy + 1, 0), S.h - 1) - y0);
-                    r.rinf[2 * k] = y0r | (y1r << 16);
-                    r.rinf[2 * k + 1] = (uint32_t)(uint16_t)beta[2 * yr] |
-                                        ((uint32_t)(uint16_t)beta[2 * yr + 1] << 16);
-                } else {
-                    r.rinf[2 * k] = (uint32_t)(mode == 2 ? yr : yr - y0);
-                }
-            }
-        }
-        for (int ty = 0; ty < lv.nty; ++ty)
-            for (int tx = 0; tx < lv.ntx; ++tx) {
-                int bytes = 0;
-                if (mode == 0 || mode == 1) bytes = (G.ltw + 8) * rt[ty].wh;
-                else if (mode == 3) bytes = ((ct[tx].ww + 3) & ~3) * rt[ty].wh;
-                G.win_cap = std::max(G.win_cap, bytes);
-            }
-        lv.ctab = (int)p.ltab.size();
-        p.ltab.insert(p.ltab.end(), (const uint8_t*)ct.data(),
-                       (const uint8_t*)(ct.data() + ct.size()));
-        lv.rowtab = (int)p.ltab.size();
-        p.ltab.insert(p.ltab.end(), (const uint8_t*)rt.data(),
-                       (const uint8_t*)(rt.data() + rt.size()));
         build_strip_tables(p, l, mode, xofs, alpha, yofs, beta);
     }
     build_chain(p);
-    p.level_lds = level_lds_bytes(G.ltw, G.lth, G.win_cap);
-    if (p.level_lds > 160 * 1024) return ORBX_ERR_UNSUPPORTED;
     G.blur_tile_begin[L] = blur_tiles;
     G.orient_block_begin[L] = oblocks;
     G.blur_tiles = blur_tiles;

@@ -1,15 +1,14 @@
-// orbx_pyramid.hip — one fused kernel per pyramid level: level l from level l-1
-// (ComputePyramid, src/ORBextractor.cc:1129-1154) and its 7x7 Gaussian (operator(),
-// :1106-1108) in the same pass.
-//
-// A 256-thread workgroup owns a 128 x 32 output tile of level l.  It stages the source
-// window of the tile + the 3-pixel blur halo (coordinates reflected as BORDER_REFLECT_101)
-// in LDS with aligned dword loads (all loads of a thread in flight before its first LDS
-// store), computes level l on tile + halo in groups of 4 adjacent pixels (the window bytes
-// of a group come from 3 dword LDS reads per source row; OpenCV INTER_LINEAR fixed-point
-// coefficients from per-group packed tables), writes the tile, then runs the separable
-// blur on 4-pixel groups (3 dword reads per row pass, 7 b64 reads per column pass) and
-// writes the blurred tile.  Level l is read from HBM once (by level l+1's launch).
+// orbx_pyramid.hip — the image pyramid: level l from level l-1 (ComputePyramid,
+// src/ORBextractor.cc:1129-1154) and the 7x7 Gaussian of every level (operator(), :1106-1108),
+// bit for bit as OpenCV's cv::resize and GaussianBlur compute them.  Three forms:
+//   k_level_strip   one launch per level, the level and its blur in one pass: a wave walks a
+//                   column strip down the level row by row (level 0 and the INTER_LINEAR
+//                   levels of every tracked configuration);
+//   k_pyr_chain     every level of a small in-place batch in one launch, a workgroup per
+//                   (tile, image) with the levels' footprints in LDS;
+//   k_level_plain + k_blur_plain   two plain launches per level, for the levels the strip walk
+//                   does not take (copy, exact 2:1 area, scale factors from about 2.3).
+// The blurred pyramid is stored in 16x4 tiles (blur_off, orbx_internal.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,9 +20,6 @@
 #include "orbx_kernels.h"
 
 namespace orbx {
-
-
-#define LT_GW (LT_W / 4)      // output groups per row
 
 __device__ __forceinline__ int reflect101_i(int p, int len) {
     if ((unsigned)p < (unsigned)len) return p;
@@ -52,579 +48,126 @@ __device__ __forceinline__ int vresize(int h0, int h1, int b0, int b1, bool simd
     return sat8((int)((__umul24(h0, b0) + __umul24(h1, b1) + (1u << 21)) >> 22));   // FixedPtCast<int, uchar, 22>
 }
 
+// Row-pass taps of the blur as v_dot4 operands: k0..k3 / k4..k6, 0.
 struct BlurTaps {
-    uint32_t tapA, tapB;   // v_dot4 taps k0..k3 / k4..k6,0 (row pass)
-    uint32_t K4, K5, K6;   // (k, k) u16 pairs (column pass)
-    uint32_t k3;
+    uint32_t tapA, tapB;
 };
 
-// ---- 3. level tile out (output x = X0 + 4g  <->  halo group g + 1) ----
-// ---- 4. blur row pass (RowFilter<uchar,int>: exact; sums <= 257*255 fit u16) ----
-// pixel x = X0+4gq+j needs halo bytes 1+j .. 7+j: two v_dot4_u32_u8 over the byte runs
-// 1+j..4+j (taps k0..k3) and 5+j..8+j (taps k4..k6, 0).  FULL: a 128 x 32 tile, fixed trip
-// counts (no per-item bounds, whole-dword stores).
-template <bool FULL>
-__device__ __forceinline__ void tile_out_rows(const uint32_t* lvl, uint16_t* rows, int tid, int vw,
-                                              int vh, uint8_t* dlev, int X0, int Y0, int pitch,
-                                              const BlurTaps& tp) {
-    const int ng = FULL ? LT_GW : (vw + 3) >> 2;
-    const int n3 = FULL ? LT_H * LT_GW : vh * LT_GW;
-    auto out_item = [&](int i) {
-        const int r = i / LT_GW, gq = i - r * LT_GW;
-        if (!FULL && gq >= ng) return;
-        const uint32_t v = lvl[(r + 3) * LT_G + gq + 1];
-        uint8_t* d = dlev + __umul24(Y0 + r, pitch) + X0 + 4 * gq;
-        if (FULL || 4 * gq + 4 <= vw) *(uint32_t*)d = v;
-        else
-            for (int j = 0; 4 * gq + j < vw; ++j) d[j] = (uint8_t)(v >> (8 * j));
-    };
-    if constexpr (FULL) {
-        static_assert((LT_H * LT_GW) % 256 == 0, "full-tile item count");
-#pragma unroll
-        for (int k = 0; k < LT_H * LT_GW / 256; ++k) out_item(tid + 256 * k);
-    } else {
-        for (int i = tid; i < n3; i += 256) out_item(i);
-    }
-    const int n4 = FULL ? (LT_H + 6) * LT_GW : (vh + 6) * LT_GW;
-    auto row_item = [&](int i) {
-        const int r = i / LT_GW, gq = i - r * LT_GW;
-        if (!FULL && gq >= ng) return;
-        const uint32_t* s = lvl + r * LT_G + gq;   // bytes of x = X0 + 4gq - 4 .. + 7
-        const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
-        uint32_t sum[4];
-        sum[0] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 1), tp.tapA,
-                 __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d2, d1, 1), tp.tapB, 0u, false), false);
-        sum[1] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 2), tp.tapA,
-                 __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d2, d1, 2), tp.tapB, 0u, false), false);
-        sum[2] = __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 3), tp.tapA,
-                 __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d2, d1, 3), tp.tapB, 0u, false), false);
-        sum[3] = __builtin_amdgcn_udot4(d1, tp.tapA, __builtin_amdgcn_udot4(d2, tp.tapB, 0u, false), false);
-        const uint32_t lo = sum[0] | (sum[1] << 16), hi = sum[2] | (sum[3] << 16);
-        *(uint2*)(rows + r * LT_W + 4 * gq) = make_uint2(lo, hi);
-    };
-    if constexpr (FULL) {
-        constexpr int K4 = ((LT_H + 6) * LT_GW) / 256, R4 = ((LT_H + 6) * LT_GW) % 256;
-#pragma unroll
-        for (int k = 0; k < K4; ++k) row_item(tid + 256 * k);
-        if (tid < R4) row_item(tid + 256 * K4);
-    } else {
-        for (int i = tid; i < n4; i += 256) row_item(i);
-    }
-}
-
-// ---- 5. blur column pass (SymmColumnFilter / SymmColumnVec_32s8u) ----
-// The SSE2 float form s = c0*f0 + p1*f1 + p2*f2 + p3*f3 (f = k/65536) is exact here:
-// every product k*v is an integer < 2^24 scaled by a power of two, and every partial
-// sum S = k3*c0 + k4*p1 + ... stays exact while S < 2^24 (partials only grow); at
-// S >= 2^24 both forms give >= 256 and saturate to 255.  So rintf(S/65536) is
+// The blur's column pass for one pixel: SymmColumnFilter / SymmColumnVec_32s8u over its seven
+// row sums e(0) .. e(6) (RowFilter<uchar,int>: exact integers <= 257 * 255) with the taps
+// t = k3 .. k6.  The SSE2 float form s = c0*f0 + p1*f1 + p2*f2 + p3*f3 (f = k/65536) is exact
+// here: every product k*v is an integer < 2^24 scaled by a power of two, and every partial sum
+// of S = k3*c + k4*(r2+r4) + k5*(r1+r5) + k6*(r0+r6) stays exact while S < 2^24 (partials only
+// grow); at S >= 2^24 both forms give >= 256 and saturate to 255.  So an SSE2 pixel (simd) is
 // round-half-even of the integer S, and the scalar tail is (S + 32768) >> 16.
-// S_j = k3*c + k4*(r2+r4) + k5*(r1+r5) + k6*(r0+r6): per pixel three v_perm pair the
-// symmetric rows' u16 sums and four v_dot2_u32_u16 accumulate (S < 2^24: exact).
-template <bool FULL>
-__device__ __forceinline__ void tile_columns(const uint16_t* rows, int tid, int vw, int vh,
-                                             uint8_t* dblur, int X0, int Y0, int pitch, int bh,
-                                             int bsimd_end, const BlurTaps& tp) {
-    const int ng = FULL ? LT_GW : (vw + 3) >> 2;
-    const int n5 = FULL ? LT_H * LT_GW : vh * LT_GW;
-    const uint32_t K3lo = tp.k3, K3hi = tp.k3 << 16;
-    auto col_item = [&](int i) {
-        const int r = i / LT_GW, gq = i - r * LT_GW;
-        if (!FULL && gq >= ng) return;
-        uint2 v[7];
-#pragma unroll
-        for (int kk = 0; kk < 7; ++kk) v[kk] = *(const uint2*)(rows + (r + kk) * LT_W + 4 * gq);
-        const int xg = X0 + 4 * gq;
-        uint32_t packed = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            auto dw = [&](int kk) { return (j < 2) ? v[kk].x : v[kk].y; };
-            const uint32_t sel = (j & 1) ? 0x07060302u : 0x05040100u;   // (a.hi, b.hi) / (a.lo, b.lo)
-            const us2 p06 = __builtin_bit_cast(us2, __builtin_amdgcn_perm(dw(6), dw(0), sel));
-            const us2 p15 = __builtin_bit_cast(us2, __builtin_amdgcn_perm(dw(5), dw(1), sel));
-            const us2 p24 = __builtin_bit_cast(us2, __builtin_amdgcn_perm(dw(4), dw(2), sel));
-            uint32_t S = __builtin_amdgcn_udot2(p06, __builtin_bit_cast(us2, tp.K6), 0u, false);
-            S = __builtin_amdgcn_udot2(p15, __builtin_bit_cast(us2, tp.K5), S, false);
-            S = __builtin_amdgcn_udot2(p24, __builtin_bit_cast(us2, tp.K4), S, false);
-            S = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, dw(3)),
-                                       __builtin_bit_cast(us2, (j & 1) ? K3hi : K3lo), S, false);
-            const bool simd = xg + j < bsimd_end;
-            const uint32_t val = (S + (simd ? 32767u + ((S >> 16) & 1u) : 32768u)) >> 16;
-            packed |= min(val, 255u) << (8 * j);
-        }
-        uint8_t* d = dblur + blur_off(xg, Y0 + r, pitch, bh);
-        if (FULL || 4 * gq + 4 <= vw) *(uint32_t*)d = packed;
-        else
-            for (int j = 0; 4 * gq + j < vw; ++j) d[j] = (uint8_t)(packed >> (8 * j));
-    };
-    if constexpr (FULL) {
-#pragma unroll
-        for (int k = 0; k < LT_H * LT_GW / 256; ++k) col_item(tid + 256 * k);
-    } else {
-        for (int i = tid; i < n5; i += 256) col_item(i);
-    }
+template <typename E>
+__device__ __forceinline__ uint32_t blur_sum(const uint32_t (&t)[4], E e) {
+    return t[0] * e(3) + t[1] * (e(2) + e(4)) + t[2] * (e(1) + e(5)) + t[3] * (e(0) + e(6));
+}
+__device__ __forceinline__ uint32_t blur_round(uint32_t S, bool simd) {
+    const uint32_t val = (S + (simd ? 32767u + ((S >> 16) & 1u) : 32768u)) >> 16;
+    return min(val, 255u);
 }
 
-#define BLUR_SLIDE 4   // full tiles: output rows per thread in the column pass (0: one row per item)
-
-// ---- 4'. blur row pass with float row sums ----
-// Same v_dot4 sums as tile_out_rows; each sum (<= 257 * 255) is stored as an exact float.
-template <bool FULL>
-__device__ __forceinline__ void tile_out_rows_f(const uint32_t* lvl, float* rows, int tid, int vw,
-                                                int vh, uint8_t* dlev, int X0, int Y0, int pitch,
-                                                const BlurTaps& tp) {
-    const int ng = FULL ? LT_GW : (vw + 3) >> 2;
-    const int n3 = FULL ? LT_H * LT_GW : vh * LT_GW;
-    auto out_item = [&](int i) {
-        const int r = i / LT_GW, gq = i - r * LT_GW;
-        if (!FULL && gq >= ng) return;
-        const uint32_t v = lvl[(r + 3) * LT_G + gq + 1];
-        uint8_t* d = dlev + __umul24(Y0 + r, pitch) + X0 + 4 * gq;
-        if (FULL || 4 * gq + 4 <= vw) *(uint32_t*)d = v;
-        else
-            for (int j = 0; 4 * gq + j < vw; ++j) d[j] = (uint8_t)(v >> (8 * j));
-    };
-    if constexpr (FULL) {
-#pragma unroll
-        for (int k = 0; k < LT_H * LT_GW / 256; ++k) out_item(tid + 256 * k);
-    } else {
-        for (int i = tid; i < n3; i += 256) out_item(i);
-    }
-    const int n4 = FULL ? (LT_H + 6) * LT_GW : (vh + 6) * LT_GW;
-    auto row_item = [&](int i) {
-        const int r = i / LT_GW, gq = i - r * LT_GW;
-        if (!FULL && gq >= ng) return;
-        const uint32_t* s = lvl + r * LT_G + gq;
-        const uint32_t d0 = s[0], d1 = s[1], d2 = s[2];
-        float4 o;
-        o.x = (float)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 1), tp.tapA,
-                     __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d2, d1, 1), tp.tapB, 0u, false), false);
-        o.y = (float)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 2), tp.tapA,
-                     __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d2, d1, 2), tp.tapB, 0u, false), false);
-        o.z = (float)__builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d1, d0, 3), tp.tapA,
-                     __builtin_amdgcn_udot4(__builtin_amdgcn_alignbyte(d2, d1, 3), tp.tapB, 0u, false), false);
-        o.w = (float)__builtin_amdgcn_udot4(d1, tp.tapA, __builtin_amdgcn_udot4(d2, tp.tapB, 0u, false), false);
-        *(float4*)(rows + r * LT_W + 4 * gq) = o;
-    };
-    if constexpr (FULL) {
-        constexpr int K4 = ((LT_H + 6) * LT_GW) / 256, R4 = ((LT_H + 6) * LT_GW) % 256;
-#pragma unroll
-        for (int k = 0; k < K4; ++k) row_item(tid + 256 * k);
-        if (tid < R4) row_item(tid + 256 * K4);
-    } else {
-        for (int i = tid; i < n4; i += 256) row_item(i);
-    }
-}
-
-// ---- 5'. blur column pass in float ----
-// S = k3*c + k4*(r2+r4) + k5*(r1+r5) + k6*(r0+r6) with integer taps and integer row sums:
-// every pairwise sum (< 2^17), product (< 2^23) and partial sum (< 2^24, see tile_columns)
-// is exact in float, so Sf == S.  SSE2 pixels take rint(S / 65536) saturated to u8
-// (v_cvt_pk_u8_f32 rounds to nearest even and clamps, as cvtps + packus do); the scalar
-// tail takes (S + 32768) >> 16 from the exact integer.
-template <bool FULL>
-__device__ __forceinline__ void tile_columns_f(const float* rows, int tid, int vw, int vh,
-                                               uint8_t* dblur, int X0, int Y0, int pitch, int bh,
-                                               int bsimd_end, const BlurTaps& tp) {
-    const int ng = FULL ? LT_GW : (vw + 3) >> 2;
-    const int n5 = FULL ? LT_H * LT_GW : vh * LT_GW;
-    // taps k / 65536 (the SSE2 path's own coefficients): power-of-two scaling keeps every
-    // product and partial sum exact, so Sf = S / 65536 exactly
-    const float inv = 1.0f / 65536.0f;
-    const float f3 = (float)tp.k3 * inv, f4 = (float)(tp.K4 & 0xFFFF) * inv,
-                f5 = (float)(tp.K5 & 0xFFFF) * inv, f6 = (float)(tp.K6 & 0xFFFF) * inv;
-    // groups entirely left of bsimd_end take the SSE2 form only
-    const bool tile_simd = X0 + 4 * ng <= bsimd_end;
-    // S for the 4 pixels of one group from its 7 row sums v[0..6]
-    auto col_sums = [&](const float4* v, float* S) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            auto c = [&](int kk) { return j == 0 ? v[kk].x : (j == 1 ? v[kk].y : (j == 2 ? v[kk].z : v[kk].w)); };
-            float a = (c(0) + c(6)) * f6;
-            a = __builtin_fmaf(c(1) + c(5), f5, a);
-            a = __builtin_fmaf(c(2) + c(4), f4, a);
-            S[j] = __builtin_fmaf(c(3), f3, a);
-        }
-    };
-    auto col_store = [&](int r, int gq, const float* S) {
-        const int xg = X0 + 4 * gq;
-        uint32_t packed = 0;
-        if (tile_simd || xg + 4 <= bsimd_end) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) packed = __builtin_amdgcn_cvt_pk_u8_f32(S[j], j, packed);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t Si = (uint32_t)(S[j] * 65536.0f);
-                const bool simd = xg + j < bsimd_end;
-                const uint32_t val = (Si + (simd ? 32767u + ((Si >> 16) & 1u) : 32768u)) >> 16;
-                packed |= min(val, 255u) << (8 * j);
-            }
-        }
-        uint8_t* d = dblur + blur_off(xg, Y0 + r, pitch, bh);
-        if (FULL || 4 * gq + 4 <= vw) *(uint32_t*)d = packed;
-        else
-            for (int j = 0; 4 * gq + j < vw; ++j) d[j] = (uint8_t)(packed >> (8 * j));
-    };
-    auto col_item = [&](int i) {
-        const int r = i / LT_GW, gq = i - r * LT_GW;
-        if (!FULL && gq >= ng) return;
-        float4 v[7];
-#pragma unroll
-        for (int kk = 0; kk < 7; ++kk) v[kk] = *(const float4*)(rows + (r + kk) * LT_W + 4 * gq);
-        float S[4];
-        col_sums(v, S);
-        col_store(r, gq, S);
-    };
-    if constexpr (FULL) {
-        // a thread owns one group and BLUR_SLIDE consecutive output rows: it reads their
-        // BLUR_SLIDE + 6 row sums once (7 per output row in the item form)
-        static_assert(LT_GW == 32 && LT_H * LT_GW == 256 * BLUR_SLIDE, "column-slide mapping");
-        const int gq = tid & (LT_GW - 1), r0 = (tid >> 5) * BLUR_SLIDE;
-        float4 v[BLUR_SLIDE + 6];
-#pragma unroll
-        for (int kk = 0; kk < BLUR_SLIDE + 6; ++kk)
-            v[kk] = *(const float4*)(rows + (r0 + kk) * LT_W + 4 * gq);
-#pragma unroll
-        for (int o = 0; o < BLUR_SLIDE; ++o) {
-            float S[4];
-            col_sums(v + o, S);
-            col_store(r0 + o, gq, S);
-        }
-    } else
-    if constexpr (FULL) {
-#pragma unroll
-        for (int k = 0; k < LT_H * LT_GW / 256; ++k) col_item(tid + 256 * k);
-    } else {
-        for (int i = tid; i < n5; i += 256) col_item(i);
-    }
-}
-
-#define STAGE_MAXK 12  // column-owner window staging: up to 48 rows (0: always the generic form)
-#define LEVEL_WPE 1
-// MODE (host-chosen per level, one instantiation each): 0 level 0 (copy of the input), 1 scale
-// 1 copy, 2 exact 2:1 area, 3 INTER_LINEAR
+// ---- k_level_plain + k_blur_plain: the levels that do not run the strip walk ----
+// Copy levels, exact 2:1 area levels and INTER_LINEAR levels whose 4-pixel groups span more
+// than the strip walk's 8-byte window (scale factors from about 2.3; LevelGeom::strip == 0)
+// take two plain launches: level l from level l-1, then its blur.  One thread per group of 4
+// adjacent pixels, the batch in grid.y; no LDS, no tables beyond cv::resize's own (rtab).
+// MODE 1 scale-1 copy, 2 exact 2:1 area, 3 INTER_LINEAR.  Level 0 always runs the strip walk
+// (build_strip_tables).
 template <int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEVEL_WPE))) void k_level(const Geometry* __restrict__ g,
-                                               const uint8_t* __restrict__ ltab,
-                                               const uint8_t* __restrict__ in0,
-                                               const uint8_t* __restrict__ in1, int split,
-                                               size_t stride, size_t bstride,
-                                               uint8_t* __restrict__ pyr,
-                                               uint8_t* __restrict__ blur, int level) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int bx, b;
-    xcd_block(bx, b);
-    const int tid = threadIdx.x;
+__global__ __launch_bounds__(256) void k_level_plain(const Geometry* __restrict__ g,
+                                                     const int16_t* __restrict__ rtab,
+                                                     uint8_t* __restrict__ pyr, int level) {
+    static_assert(MODE >= 1 && MODE <= 3, "plain kernel: copy, area or INTER_LINEAR levels");
     const LevelGeom& L = g->lv[level];
-    const int tx = bx % L.ntx, ty = bx / L.ntx;
-    const int X0 = tx * LT_W, Y0 = ty * LT_H;
-    const int vw = min(LT_W, L.w - X0), vh = min(LT_H, L.h - Y0);
-
-    uint8_t* p = smem;
-    auto take = [&](size_t n) { uint8_t* r = p; p += (n + 15) & ~(size_t)15; return r; };
-    uint32_t* lvl = (uint32_t*)take((size_t)LT_HR * LT_G * 4);      // [38][34] dwords
-    // the blur's row sums (phases 3-4) share their LDS with the tables and the source window
-    // (phases 1-2, dead after the barrier that ends phase 2): a smaller footprint, so more
-    // workgroups -- and more window loads in flight -- per CU
-    uint16_t* rows = (uint16_t*)p;                                   // [38][128] row sums
-    uint2* cgrp = (uint2*)take((size_t)LT_G * 8);                    // per group: 4 x sx (u16)
-    uint32_t* cinf = (uint32_t*)take((size_t)LT_G * 4);              // per group: flags
-    uint4* calp = (uint4*)take((size_t)LT_G * 16);                   // per group: 4 x (a0, a1)
-    uint4* csel = (uint4*)take((size_t)LT_G * 16);                   // per group: 4 x selector
-    uint2* rinf = (uint2*)take((size_t)LT_HR * 8);                   // per row: ry0, ry1, b0, b1
-    uint8_t* win = p;                                                // source window
-
-    constexpr int mode = MODE;
-    const LevelGeom& S = g->lv[level > 0 ? level - 1 : 0];
-    // needed halo ranges (level coordinates, before reflection)
-    const int nx0 = X0 - 3, nx1 = X0 + vw + 2, ny0 = Y0 - 3, ny1 = Y0 + vh + 2;
-
-    // ---- 1. source window + tables (host-built per tile column / row, build_geometry) ----
-    const LevelColTab* CT = (const LevelColTab*)(ltab + L.ctab) + tx;
-    const LevelRowTab* RT = (const LevelRowTab*)(ltab + L.rowtab) + ty;
-    const int wx0 = CT->x0, WWb = CT->ww, wy0 = RT->y0, WH = RT->wh;
-    // table loads issued before the window loads, so both land in one round trip
-    uint4 tc = make_uint4(0, 0, 0, 0), ta = make_uint4(0, 0, 0, 0), ts = ta;
-    if (mode == 0) {
-        // level 0 reads no tables
-    } else if (tid < LT_G) {
-        tc = make_uint4(CT->cgrp[2 * tid], CT->cgrp[2 * tid + 1], CT->cinf[tid], 0);
-        ta = *(const uint4*)&CT->calp[4 * tid];
-        ts = *(const uint4*)&CT->csel[4 * tid];
-    } else if (tid >= 64 && tid < 64 + LT_HR) {
-        tc = make_uint4(RT->rinf[2 * (tid - 64)], RT->rinf[2 * (tid - 64) + 1], 0, 0);
+    const LevelGeom& S = g->lv[level - 1];
+    const int ng = (L.w + 3) >> 2;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ng * L.h) return;
+    const int y = i / ng, x0 = 4 * (i - y * ng);
+    uint8_t* const img = pyr + (size_t)blockIdx.y * g->pyr_bytes;
+    const uint8_t* const src = img + S.off;
+    // MODE 3: cv::resize's tables of the level (build_geometry): xofs[w], alpha[2w], yofs[h],
+    // beta[2h]; HResizeLinear + VResizeLinear(Vec) per pixel
+    const int16_t* xofs = rtab + L.rtab_off;
+    const int16_t* alpha = xofs + L.w;
+    const int16_t* yofs = alpha + 2 * L.w;
+    const int16_t* beta = yofs + L.h;
+    const uint8_t *r0 = src, *r1 = src;
+    int b0 = 0, b1 = 0;
+    if (MODE == 3) {
+        const int sy = yofs[y];
+        r0 = src + (size_t)min(max(sy, 0), S.h - 1) * S.pitch;
+        r1 = src + (size_t)min(max(sy + 1, 0), S.h - 1) * S.pitch;
+        b0 = beta[2 * y];
+        b1 = beta[2 * y + 1];
     }
-    // window row pitch; modes 0/1 place x at column x - (X0 - 4) so that groups are dword-aligned
-    const int WP = (mode == 3) ? ((WWb + 3) & ~3) : LT_G * 4;
-    const int wcol0 = (mode == 3) ? 0 : wx0 - (X0 - 4);
-    // level 0: the halo tile is the input itself, loaded straight into the level array: two
-    // aligned dwords + v_alignbyte per 4-pixel group, or on border tiles four byte loads per
-    // group (rows and columns reflected per item)
-    constexpr bool direct = mode == 0;
-    if (direct) {
-        const uint8_t* src = (b < split ? in0 + (size_t)b * bstride : in1 + (size_t)(b - split) * bstride);
-        const int W = L.w, H = L.h;
-        constexpr int NI = (LT_HR * LT_G + 255) / 256;
-        static_assert(256 / LT_G == 7 && 256 % LT_G == 18, "halo item stride");
-        uint32_t d0[NI], d1[NI], sh[NI];
-        // inner tiles: every group's aligned dword pair inside its image row (xg >= 4 keeps the
-        // aligned base after the row start, xg + 8 <= W its second dword before the row end)
-        const bool inner = X0 >= 8 && X0 + LT_W + 8 <= W && Y0 >= 3 && Y0 + LT_H + 3 <= H;
-        auto load_items = [&](auto inner_c) {
-            constexpr bool IN = decltype(inner_c)::value;
-            int hr = tid / LT_G, q = tid - hr * LT_G;
-#pragma unroll
-            for (int k = 0; k < NI; ++k) {
-                const int hrc = min(hr, LT_HR - 1);
-                int y = Y0 - 3 + hrc;
-                if (!IN) {   // BORDER_REFLECT_101; rows past the needed halo: any row
-                    y = y < 0 ? -y : (y >= H ? 2 * H - 2 - y : y);
-                    y = min(max(y, 0), H - 1);
-                }
-                const uint8_t* row = src + __umul24(y, (uint32_t)stride);
-                const int xg = X0 - 4 + 4 * q;
-                if constexpr (IN) {
-                    const uintptr_t a = (uintptr_t)(row + xg);
-                    const uint32_t* ab = (const uint32_t*)(a & ~(uintptr_t)3);
-                    sh[k] = (uint32_t)(a & 3);
-                    d0[k] = ab[0];
-                    d1[k] = ab[1];
-                } else {
-                    // border tiles: four byte loads per group, branch-free, all in flight
-                    uint32_t v = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        int x = xg + j;
-                        x = x < 0 ? -x : (x >= W ? 2 * W - 2 - x : x);
-                        x = min(max(x, 0), W - 1);   // pixels past the needed halo: any in-row value
-                        v |= (uint32_t)row[x] << (8 * j);
-                    }
-                    d0[k] = v;
-                    d1[k] = 0;
-                    sh[k] = 0;
-                }
-                hr += 7;
-                q += 18;
-                if (q >= LT_G) { q -= LT_G; ++hr; }
-            }
-        };
-        if (inner) load_items(std::true_type{});
-        else load_items(std::false_type{});
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const int i = tid + 256 * k;
-            if (i < LT_HR * LT_G) lvl[i] = __builtin_amdgcn_alignbyte(d1[k], d0[k], sh[k]);
+    auto pixel = [&](int x) -> int {
+        if (MODE == 1) return src[(size_t)y * S.pitch + x];
+        if (MODE == 2) {
+            const uint8_t* s = src + (size_t)(2 * y) * S.pitch + 2 * x;
+            return (s[0] + s[1] + s[S.pitch] + s[S.pitch + 1] + 2) >> 2;
         }
-    } else if (mode == 1) {
-        const uint8_t* src = pyr + (size_t)b * g->pyr_bytes + S.off;   // wx0 is a multiple of 4
-        if (!stage_dwords_cols<STAGE_MAXK>(src + (size_t)wy0 * S.pitch + wx0, S.pitch, WH,
-                                           (WWb + 3) >> 2, (uint32_t*)(win + wcol0), WP / 4, tid))
-            stage_dwords<256>(src + (size_t)wy0 * S.pitch + wx0, S.pitch, WH, (WWb + 3) >> 2,
-                              (uint32_t*)(win + wcol0), WP / 4, tid);
-    } else if (mode == 3) {
-        const uint8_t* src = pyr + (size_t)b * g->pyr_bytes + S.off;
-        if (!stage_dwords_cols<STAGE_MAXK>(src + (size_t)wy0 * S.pitch + wx0, S.pitch, WH, WP / 4,
-                                           (uint32_t*)win, WP / 4, tid))
-            stage_dwords<256>(src + (size_t)wy0 * S.pitch + wx0, S.pitch, WH, WP / 4,
-                              (uint32_t*)win, WP / 4, tid);
-    }
-    if (mode == 0) {
-    } else if (tid < LT_G) {
-        cgrp[tid] = make_uint2(tc.x, tc.y);
-        cinf[tid] = tc.z;
-        calp[tid] = ta;
-        csel[tid] = ts;
-    } else if (tid >= 64 && tid < 64 + LT_HR) {
-        rinf[tid - 64] = make_uint2(tc.x, tc.y);
-    }
-    __syncthreads();
-
-    // ---- 2. level l on tile + halo, 4 pixels per item ----
-    const uint8_t* src2 = pyr + (size_t)b * g->pyr_bytes + S.off;   // mode 2 only
-    // item i = (halo row hr, group q); 256 = 7 * LT_G + 18, advanced without divisions
-    const bool full_tile = vw == LT_W && vh == LT_H;   // every halo item is needed
-    // mode 3 (generic INTER_LINEAR) on one 4-pixel group: halo row hr, the group's column
-    // tables (cg: source columns, ci: flags, al: alphas, sl: v_perm selectors)
-    auto item3 = [&](int hr, uint2 cg, uint32_t ci, uint4 al, uint4 sl, auto fast_c) -> uint32_t {
-        constexpr bool FASTP = decltype(fast_c)::value;   // simple group, all four pixels SSE2
-        uint32_t out = 0;
-        const uint2 ri = rinf[hr];
-        const int xs[4] = {(int)(cg.x & 0xFFFF), (int)(cg.x >> 16), (int)(cg.y & 0xFFFF),
-                           (int)(cg.y >> 16)};
-        const uint32_t als[4] = {al.x, al.y, al.z, al.w};
-        const int r0 = (int)(ri.x & 0xFFFF), r1 = (int)(ri.x >> 16);
-        const int b0 = (int)(int16_t)(ri.y & 0xFFFF), b1 = (int)(int16_t)(ri.y >> 16);
-        const uint8_t* w0 = win + __umul24(r0, WP);
-        const uint8_t* w1 = win + __umul24(r1, WP);
-        if (FASTP || (ci & 0x200u)) {
-            // branch-free: v_perm gathers each pixel's two taps as u16s, v_dot2 applies
-            // the alphas (HResizeLinear), then VResizeLinear (SSE2 or scalar form)
-            const uint32_t sels[4] = {sl.x, sl.y, sl.z, sl.w};
-            const int base = xs[0] & ~3, o0 = xs[0] & 3;
-            const uint32_t* d0p = (const uint32_t*)(w0 + base);
-            const uint32_t* d1p = (const uint32_t*)(w1 + base);
-            const uint32_t a0 = d0p[0], a1 = d0p[1], a2 = d0p[2];
-            const uint32_t c0 = d1p[0], c1 = d1p[1], c2 = d1p[2];
-            // 8-byte windows starting at the group's first tap column (span <= 7)
-            const uint32_t wa0 = __builtin_amdgcn_alignbyte(a1, a0, o0);
-            const uint32_t wa1 = __builtin_amdgcn_alignbyte(a2, a1, o0);
-            const uint32_t wc0 = __builtin_amdgcn_alignbyte(c1, c0, o0);
-            const uint32_t wc1 = __builtin_amdgcn_alignbyte(c2, c1, o0);
-            // h <= 255*2048, betas in [0, 2048]: the SSE2 clamps never bind; 24-bit
-            // multiplies (full rate): h < 2^19, b <= 2048.  Groups whose 4 pixels all
-            // take the SSE2 form (all but the right edge) skip the scalar form.
-            const bool all_simd = FASTP || ((ci >> 1) & 0x55u) == 0x55u;
-            auto hsum = [&](int j, int& h0, int& h1) {
-                const uint32_t p0 = __builtin_amdgcn_perm(wa1, wa0, sels[j]);
-                const uint32_t p1 = __builtin_amdgcn_perm(wc1, wc0, sels[j]);
-                const us2 al = __builtin_bit_cast(us2, als[j]);
-                h0 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(us2, p0), al, 0u, false);
-                h1 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(us2, p1), al, 0u, false);
-            };
-            // hsum returns H = 16 h (the table alphas are scaled by 16), so
-            // ((h >> 4) * b) >> 16 = mulhi_u24(H & ~0xFF, b << 8): one v_and and one
-            // v_mul_hi_u32_u24 per term.  No saturation: alphas and betas each sum to
-            // 2048, so the two terms are <= (255*2048 >> 4) * 2048 >> 16 = 1020 and
-            // the value <= 255.
-            const uint32_t bs0 = (uint32_t)b0 << 8, bs1 = (uint32_t)b1 << 8;
-            auto mulhi24 = [](uint32_t x, uint32_t y) {
-                return (uint32_t)(((uint64_t)(x & 0xFFFFFFu) * (y & 0xFFFFFFu)) >> 32);
-            };
-            auto vsimd = [&](int H0, int H1) {
-                return (int)((mulhi24((uint32_t)H0 & ~0xFFu, bs0) +
-                              mulhi24((uint32_t)H1 & ~0xFFu, bs1) + 2u) >> 2);
-            };
-            if (all_simd) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int h0, h1;
-                    hsum(j, h0, h1);
-                    out |= (uint32_t)vsimd(h0, h1) << (8 * j);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    int h0, h1;
-                    hsum(j, h0, h1);
-                    const int vs = vsimd(h0, h1);
-                    h0 >>= 4;
-                    h1 >>= 4;
-                    const int vc = min((int)((__umul24(h0, b0) + __umul24(h1, b1) + (1u << 21)) >> 22), 255);
-                    out |= (uint32_t)(((ci >> (2 * j + 1)) & 1u) ? vs : vc) << (8 * j);
-                }
-            }
-        } else {   // reflected border group: bytes one by one
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sxj = xs[j];
-                const int f = (int)(ci >> (2 * j)) & 3;
-                int h0, h1;
-                if (f & 1) {
-                    const int aa = (int)(int16_t)(als[j] & 0xFFFF), ab = (int)(int16_t)(als[j] >> 16);
-                    h0 = w0[sxj] * aa + w0[sxj + 1] * ab;
-                    h1 = w1[sxj] * aa + w1[sxj + 1] * ab;
-                } else {
-                    h0 = w0[sxj] * 2048;
-                    h1 = w1[sxj] * 2048;
-                }
-                out |= (uint32_t)vresize(h0, h1, b0, b1, (f & 2) != 0) << (8 * j);
-            }
+        const int sx = xofs[x];
+        int h0 = r0[sx] * 2048, h1 = r1[sx] * 2048;   // at and right of xmax: S[sx] * ONE
+        if (x < L.xmax) {
+            const int a0 = alpha[2 * x], a1 = alpha[2 * x + 1], sx1 = min(sx + 1, S.w - 1);
+            h0 = r0[sx] * a0 + r0[sx1] * a1;
+            h1 = r1[sx] * a0 + r1[sx1] * a1;
         }
-        return out;
+        return vresize(h0, h1, b0, b1, x < L.rsimd_end);
     };
-    auto level_item = [&](int hr, int q, bool all) {
-        const int y = Y0 - 3 + hr, xg = X0 - 4 + 4 * q;
-        uint32_t out = 0;
-        if (all || (y >= ny0 && y <= ny1 && xg + 3 >= nx0 && xg <= nx1)) {
-            const uint2 cg = cgrp[q];
-            const uint32_t ci = cinf[q];
-            const uint2 ri = rinf[hr];
-            const int xs[4] = {(int)(cg.x & 0xFFFF), (int)(cg.x >> 16), (int)(cg.y & 0xFFFF),
-                               (int)(cg.y >> 16)};
-            if (mode == 3) {
-                out = item3(hr, cg, ci, calp[q], csel[q], std::false_type{});
-            } else if (mode == 2) {
-                const int yr = (int)ri.x;
+    const int n = min(4, L.w - x0);   // the row's last group may be partial
+    uint32_t out = 0;
+    for (int j = 0; j < n; ++j) out |= (uint32_t)pixel(x0 + j) << (8 * j);
+    uint8_t* d = img + L.off + (size_t)y * L.pitch + x0;
+    if (n == 4) *(uint32_t*)d = out;
+    else
+        for (int j = 0; j < n; ++j) d[j] = (uint8_t)(out >> (8 * j));
+}
+
+// The 7x7 Gaussian of level `level` (in the pyramid) into the blurred pyramid's 16x4 tiles:
+// RowFilter<uchar,int> over BORDER_REFLECT_101 rows and columns, then blur_sum / blur_round.
+__global__ __launch_bounds__(256) void k_blur_plain(const Geometry* __restrict__ g,
+                                                    const uint8_t* __restrict__ pyr,
+                                                    uint8_t* __restrict__ blur, int level) {
+    const LevelGeom& L = g->lv[level];
+    const int W = L.w, H = L.h;
+    const int ng = (W + 3) >> 2;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ng * H) return;
+    const int y = i / ng, x0 = 4 * (i - y * ng);
+    const uint8_t* lev = pyr + (size_t)blockIdx.y * g->pyr_bytes + L.off;
+    int xr[10];   // the columns x0 - 3 .. x0 + 6, reflected
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const uint8_t* s0 = src2 + (size_t)(2 * yr) * S.pitch + 2 * xs[j];
-                    out |= (uint32_t)((s0[0] + s0[1] + s0[S.pitch] + s0[S.pitch + 1] + 2) >> 2) << (8 * j);
-                }
-            } else {
-                const uint8_t* wr = win + __umul24(ri.x & 0xFFFF, WP);
-                if (ci & 0x100u) {
-                    out = *(const uint32_t*)(wr + xs[0]);
-                } else {
-                    out = (uint32_t)wr[xs[0]] | ((uint32_t)wr[xs[1]] << 8) |
-                          ((uint32_t)wr[xs[2]] << 16) | ((uint32_t)wr[xs[3]] << 24);
-                }
-            }
-        }
-        lvl[hr * LT_G + q] = out;
-    };
-    if (!direct && mode == 3 && full_tile) {
-        // thread t < 7 LT_G keeps column group q = t % LT_G for halo rows t / LT_G + 7k: the
-        // group's tables are read once, not once per item
-        if (tid < 7 * LT_G) {
-            const int rs = (int)(__umul24((uint32_t)tid, 1928u) >> 16);   // tid / 34, tid < 256
-            const int q = tid - rs * LT_G;
-            const uint2 cg = cgrp[q];
-            const uint32_t ci = cinf[q];
-            const uint4 al = calp[q], sl = csel[q];
-            // interior tiles: every group of the wave is simple and SSE2-only, so the wave takes
-            // the branch-free form with no per-item exec-mask branches
-            const bool fast = (ci & 0x200u) && ((ci >> 1) & 0x55u) == 0x55u;
-            if (__all(fast)) {
+    for (int t = 0; t < 10; ++t) xr[t] = reflect101_i(x0 - 3 + t, W);
+    uint32_t rs[7][4];
 #pragma unroll
-                for (int k = 0; k < (LT_HR + 6) / 7; ++k) {
-                    const int hr = rs + 7 * k;
-                    if (hr < LT_HR) lvl[hr * LT_G + q] = item3(hr, cg, ci, al, sl, std::true_type{});
-                }
-            } else {
+    for (int k = 0; k < 7; ++k) {
+        const uint8_t* row = lev + (size_t)reflect101_i(y - 3 + k, H) * L.pitch;
+        uint32_t p[10];
 #pragma unroll
-                for (int k = 0; k < (LT_HR + 6) / 7; ++k) {
-                    const int hr = rs + 7 * k;
-                    if (hr < LT_HR) lvl[hr * LT_G + q] = item3(hr, cg, ci, al, sl, std::false_type{});
-                }
-            }
-        }
-    } else
-    if (!direct) {
-        int hr = tid / LT_G, q = tid - hr * LT_G;
-        if (full_tile) {
-            constexpr int KF = (LT_HR * LT_G) / 256, RF = (LT_HR * LT_G) % 256;
+        for (int t = 0; t < 10; ++t) p[t] = row[xr[t]];
 #pragma unroll
-            for (int k = 0; k < KF; ++k) {
-                level_item(hr, q, true);
-                hr += 7;
-                q += 18;
-                if (q >= LT_G) { q -= LT_G; ++hr; }
-            }
-            if (tid < RF) level_item(hr, q, true);
-        } else {
-            for (int i = tid; i < LT_HR * LT_G;
-                 i += 256, hr += 7, q += 18, (q >= LT_G ? (q -= LT_G, ++hr) : 0))
-                level_item(hr, q, false);
+        for (int j = 0; j < 4; ++j) {
+            uint32_t s = 0;
+#pragma unroll
+            for (int t = 0; t < 7; ++t) s += (uint32_t)g->taps[t] * p[j + t];
+            rs[k][j] = s;
         }
     }
-    __syncthreads();
-
-    uint8_t* dlev = pyr + (size_t)b * g->pyr_bytes + L.off;
-    uint8_t* dblur = blur + (size_t)b * g->pyr_bytes + L.off;
-    const int k0 = g->taps[0], k1 = g->taps[1], k2 = g->taps[2], k3 = g->taps[3];
-    const int k4 = g->taps[4], k5 = g->taps[5], k6 = g->taps[6];
-    const BlurTaps tp = {(uint32_t)k0 | (uint32_t)k1 << 8 | (uint32_t)k2 << 16 | (uint32_t)k3 << 24,
-                         (uint32_t)k4 | (uint32_t)k5 << 8 | (uint32_t)k6 << 16,
-                         (uint32_t)k4 * 0x10001u, (uint32_t)k5 * 0x10001u, (uint32_t)k6 * 0x10001u,
-                         (uint32_t)k3};
-    // full tiles (all but the right / bottom edge) run the fixed-trip-count form
-    const bool full = vw == LT_W && vh == LT_H;
-    float* rowsf = (float*)rows;
-    if (full) tile_out_rows_f<true>(lvl, rowsf, tid, vw, vh, dlev, X0, Y0, L.pitch, tp);
-    else tile_out_rows_f<false>(lvl, rowsf, tid, vw, vh, dlev, X0, Y0, L.pitch, tp);
-    __syncthreads();
-    if (full) tile_columns_f<true>(rowsf, tid, vw, vh, dblur, X0, Y0, L.pitch, L.h, L.bsimd_end, tp);
-    else tile_columns_f<false>(rowsf, tid, vw, vh, dblur, X0, Y0, L.pitch, L.h, L.bsimd_end, tp);
+    const uint32_t tc[4] = {(uint32_t)g->taps[3], (uint32_t)g->taps[4], (uint32_t)g->taps[5],
+                            (uint32_t)g->taps[6]};
+    uint32_t packed = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        packed |= blur_round(blur_sum(tc, [&](int k) { return rs[k][j]; }), x0 + j < L.bsimd_end) << (8 * j);
+    uint8_t* d = blur + (size_t)blockIdx.y * g->pyr_bytes + L.off + blur_off(x0, y, L.pitch, H);
+    if (x0 + 4 <= W) *(uint32_t*)d = packed;
+    else
+        for (int j = 0; x0 + j < W; ++j) d[j] = (uint8_t)(packed >> (8 * j));
 }
 
 // ---- k_level_strip: level l and its blur by column strips, one row per step ----
@@ -634,12 +177,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LEVEL_WPE))
 // it, takes its neighbours' groups with DPP wave shifts and forms the row sums of the
 // blur; the last 7 rows' sums stay in registers, so the blurred row y - 3 is one
 // symmetric column sum.  No LDS, no barriers: the loads of later rows are in flight while
-// the wave computes.  The arithmetic is item3's (resize, mode 3) and tile_out_rows_f /
-// tile_columns_f's (blur), bit for bit.
+// the wave computes.
+// Resize (mode 3): per pixel one v_perm gathers its two taps as u16s from the 8 bytes at the
+// group's first tap column and one v_dot2 applies the alphas (HResizeLinear); the table alphas
+// are scaled by 16, so the sum is H = 16 h and VResizeLinearVec_32s8u's ((h >> 4) * b) >> 16 is
+// mulhi_u24(H & ~0xFF, b << 8).  No saturation: alphas and betas each sum to 2048, so the two
+// terms are <= (255 * 2048 >> 4) * 2048 >> 16 = 1020 together and the value <= 255.  Pixels past
+// the SSE2 loop's end take the scalar form (vresize).
+// Blur: the row sums (v_dot4, exact integers) are kept as floats and the column sum runs in
+// float: every pairwise sum (< 2^17), product (< 2^23) and partial sum (< 2^24) is exact, so it
+// equals blur_sum's integer S; SSE2 pixels take rint(S / 65536) saturated to u8
+// (v_cvt_pk_u8_f32 rounds to nearest even and clamps, as cvtps + packus do), the scalar tail
+// (S + 32768) >> 16 from the exact integer.
 #define STRIP_PF 2   // mode 3: rows of source loads in flight ahead of the row being computed
 #define STRIP_ST_POLICY 0   // cache-policy bits of the strip walk stores: nt (2) 1.99 ms, sc1 (16) 1.88 ms vs 1.71 ms
 #define STRIP_LEV rlev
-#define STRIP_HREUSE 1   // mode 3: reuse the previous step's HResize of a shared source row
 #define STRIP_HMASK 1   // mode 3, SSE2 waves: horizontal sums masked once per source row
 // One workgroup per strip row (its snw <= 8 waves side by side) with an s_barrier every
 // STRIP_SYNC* blocks of 7 steps (0: 4-wave workgroups, no barrier): the waves of a strip row
@@ -726,8 +278,7 @@ __device__ __forceinline__ void level_strip_wave(const Geometry* __restrict__ g,
     // row sums of the blur (exact integers as floats), last 7 rows
     const BlurTaps tp = {(uint32_t)g->taps[0] | (uint32_t)g->taps[1] << 8 | (uint32_t)g->taps[2] << 16 |
                              (uint32_t)g->taps[3] << 24,
-                         (uint32_t)g->taps[4] | (uint32_t)g->taps[5] << 8 | (uint32_t)g->taps[6] << 16,
-                         0u, 0u, 0u, (uint32_t)g->taps[3]};
+                         (uint32_t)g->taps[4] | (uint32_t)g->taps[5] << 8 | (uint32_t)g->taps[6] << 16};
     const float inv = 1.0f / 65536.0f;
     const float f3 = (float)g->taps[3] * inv, f4 = (float)g->taps[4] * inv,
                 f5 = (float)g->taps[5] * inv, f6 = (float)g->taps[6] * inv;
@@ -1009,10 +560,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MODE != 3 ?
 // ChainRect: the owned rectangle + blur halo + what the next level's footprint reads) from
 // level l - 1's footprint in the other LDS buffer, so the tiles overlap (recomputed halos)
 // instead of waiting for each other.  The owned pixels of each level and their blur go to HBM.
-// Arithmetic per pixel: HResizeLinear + VResizeLinear(Vec) (vresize, as k_level's scalar
-// border path) and RowFilter<uchar,int> + SymmColumnFilter in the exact integer form of
-// tile_columns (S < 2^24, SSE2 pixels round half to even) -- src/ORBextractor.cc:1129-1154,
-// :1107-1108.
+// Arithmetic per pixel: HResizeLinear + VResizeLinear(Vec) in the strip walk's form, and
+// RowFilter<uchar,int> + SymmColumnFilter in the exact integer form of blur_sum (S < 2^24,
+// SSE2 pixels round half to even) -- src/ORBextractor.cc:1129-1154, :1107-1108.
 #define CHAIN_NT 1024
 __device__ __forceinline__ int reflect101_fast(int p, int len) {
     return (unsigned)p < (unsigned)len ? p : reflect101_i(p, len);
@@ -1068,8 +618,7 @@ __device__ __forceinline__ bool chain_fill(const ChainRect& c, const LevelGeom& 
 // Row pass of the blur of level l's owned rectangle (rows oy0 - 3 .. oy1 + 2, reflected) from
 // its footprint in LDS (src: padded rows, chain_pitch P) into rsum (int row sums, RW = 4 ng per
 // row): three aligned dwords per 4-pixel group (bytes xg - 4 .. xg + 7, the left pad and
-// chain_fill's reflected columns included), the sums as v_dot4 on shifted words, as
-// tile_out_rows.
+// chain_fill's reflected columns included), the sums as v_dot4 on shifted words.
 template <int NT>
 __device__ __forceinline__ void chain_rows(const ChainRect& c, const LevelGeom& Lv, const uint8_t* src,
                                            int P, int* rsum, const Geometry* g, int tid) {
@@ -1100,16 +649,15 @@ __device__ __forceinline__ void chain_rows(const ChainRect& c, const LevelGeom& 
 }
 
 // Column pass of the blur of level l's owned rectangle from rsum, stored to the blurred
-// pyramid: SymmColumnFilter in the exact integer form of tile_columns (S < 2^24, SSE2 pixels
-// round half to even).
+// pyramid (blur_sum, blur_round).
 template <int NT>
 __device__ __forceinline__ void chain_cols(const ChainRect& c, const LevelGeom& Lv, const int* rsum,
                                            uint8_t* dblur, const Geometry* g, int tid) {
     const int ow = c.ox1 - c.ox0, oh = c.oy1 - c.oy0;
     if (ow <= 0 || oh <= 0) return;
     const int ng = (ow + 3) >> 2, RW = 4 * ng;
-    const uint32_t t3 = (uint32_t)g->taps[3], t4 = (uint32_t)g->taps[4];
-    const uint32_t t5 = (uint32_t)g->taps[5], t6 = (uint32_t)g->taps[6];
+    const uint32_t tc[4] = {(uint32_t)g->taps[3], (uint32_t)g->taps[4], (uint32_t)g->taps[5],
+                            (uint32_t)g->taps[6]};
     const Div dv(ng);
     for (int i = tid; i < oh * ng; i += NT) {
         const int rr = dv(i), q = i - rr * ng;
@@ -1121,10 +669,7 @@ __device__ __forceinline__ void chain_cols(const ChainRect& c, const LevelGeom& 
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             auto e = [&](int k) { return (uint32_t)((const int*)&v[k])[j]; };
-            const uint32_t S = t3 * e(3) + t4 * (e(2) + e(4)) + t5 * (e(1) + e(5)) + t6 * (e(0) + e(6));
-            const bool simd = xg + j < Lv.bsimd_end;
-            const uint32_t val = (S + (simd ? 32767u + ((S >> 16) & 1u) : 32768u)) >> 16;
-            packed |= min(val, 255u) << (8 * j);
+            packed |= blur_round(blur_sum(tc, e), xg + j < Lv.bsimd_end) << (8 * j);
         }
         uint8_t* d = dblur + blur_off(xg, y, Lv.pitch, Lv.h);
         if (xg + 4 <= c.ox1) *(uint32_t*)d = packed;
@@ -1276,7 +821,7 @@ __global__ __launch_bounds__(NT) void k_pyr_chain(const Geometry* __restrict__ g
         // r0, r0 + R, ... (R = NT / ng rows at a time), two per trip.  Per row and group: three
         // aligned dwords of each source row realigned to the group's first tap (v_alignbyte),
         // each pixel's two taps as u16s by one v_perm and HResizeLinear as one v_dot2 with the
-        // 16x alphas (H = 16 h, exact), as k_level's item3; VResizeLinearVec_32s8u as
+        // 16x alphas (H = 16 h, exact), as the strip walk; VResizeLinearVec_32s8u as
         // v_and + v_mul_hi_u32_u24 per term, or the scalar form past the SSE2 loop's end
         const int R = NT / ng;
         const Div dq(ng);
@@ -1322,7 +867,7 @@ __global__ __launch_bounds__(NT) void k_pyr_chain(const Geometry* __restrict__ g
                         const uint32_t H1 = __builtin_amdgcn_udot2(
                             __builtin_bit_cast(us2, __builtin_amdgcn_perm(wc1, wc0, sels[j])), al, 0u, false);
                         // SSE2 form: ((h >> 4) * b) >> 16 = mulhi_u24((16 h) & ~0xFF, b << 8); the
-                        // two terms are <= 1020 together, so no saturation (see item3)
+                        // two terms are <= 1020 together, so no saturation (see k_level_strip)
                         uint32_t v = (mulhi_u24(H0 & ~0xFFu, bs0) +
                                       mulhi_u24(H1 & ~0xFFu, bs1) + 2u) >> 2;
                         if (!all_simd && !((simd_bits >> j) & 1u))
@@ -1360,31 +905,6 @@ hipError_t launch_pyr_chain(const ExtractLaunch& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-size_t level_lds_bytes(int ltw, int lth, int win_cap) {
-    (void)ltw;
-    (void)lth;
-    auto r = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t tables = r(LT_G * 8) + r(LT_G * 4) + r(LT_G * 16) + r(LT_G * 16) + r(LT_HR * 8);
-    const size_t phase12 = tables + r((size_t)win_cap + 16);
-    const size_t phase34 = r((size_t)LT_HR * LT_W * 4);
-    return r((size_t)LT_HR * LT_G * 4) + (phase12 > phase34 ? phase12 : phase34) + r(64);
-}
-
-static int level_mode(const LevelGeom& L, int l) {
-    return l == 0 ? 0 : (L.copy ? 1 : (L.area2 ? 2 : 3));
-}
-
-typedef void (*LevelKernel)(const Geometry*, const uint8_t*, const uint8_t*, const uint8_t*, int,
-                            size_t, size_t, uint8_t*, uint8_t*, int);
-static LevelKernel level_kernel(int mode) {
-    switch (mode) {
-        case 0: return k_level<0>;
-        case 1: return k_level<1>;
-        case 2: return k_level<2>;
-        default: return k_level<3>;
-    }
-}
-
 // levels [l_begin, l_end) (launch_extract may fork a side branch in between)
 hipError_t launch_levels(const ExtractLaunch& a, hipStream_t st, int l_begin, int l_end) {
     const Geometry& G = *a.hg;
@@ -1392,7 +912,7 @@ hipError_t launch_levels(const ExtractLaunch& a, hipStream_t st, int l_begin, in
     KernelTimer& T = a.timer ? *a.timer : dummy;
     for (int l = l_begin; l < l_end && l < G.nlevels; ++l) {
         const LevelGeom& L = G.lv[l];
-        const int mode = level_mode(L, l);
+        const int mode = l == 0 ? 0 : (L.copy ? 1 : (L.area2 ? 2 : 3));
         if (L.strip) {
             const int sth = a.sth[l], sns = (L.h + sth - 1) / sth;
             const int sync = L.snw <= 8 && ((STRIP_SYNC_LEVELS >> l) & 1) ? (mode == 3 ? STRIP_SYNC3 : STRIP_SYNC0) : 0;
@@ -1402,33 +922,23 @@ hipError_t launch_levels(const ExtractLaunch& a, hipStream_t st, int l_begin, in
                               dim3(sync > 0 ? 64 * L.snw : 256), 0, st, a.dg,
                               a.ltab, a.d_imgs, a.d_imgs2, a.split, a.stride, a.batch_stride,
                               a.pyr, a.blur, l, sth, sync);
-        } else if (l == 0 && a.in_place) {
-            // the tiled level-0 kernel reading the pyramid's own level 0 (its level stores
-            // write back the bytes already there)
-            ORBX_TIMED_LAUNCH(T, K_LEVEL, level_kernel(0), dim3(L.ntx * L.nty, a.batch), dim3(256),
-                              a.level_lds, st, a.dg, a.ltab, (const uint8_t*)(a.pyr + L.off),
-                              (const uint8_t*)(a.pyr + L.off), a.batch, (size_t)L.pitch,
-                              (size_t)G.pyr_bytes, a.pyr, a.blur, l);
         } else {
-            ORBX_TIMED_LAUNCH(T, K_LEVEL, level_kernel(mode), dim3(L.ntx * L.nty, a.batch), dim3(256),
-                              a.level_lds, st, a.dg, a.ltab, a.d_imgs, a.d_imgs2, a.split,
-                              a.stride, a.batch_stride, a.pyr, a.blur, l);
+            // l >= 1: level 0 always strips (build_strip_tables)
+            const dim3 grid((((L.w + 3) >> 2) * L.h + 255) / 256, a.batch);
+            ORBX_TIMED_LAUNCH(T, K_LEVEL,
+                              mode == 1 ? k_level_plain<1> : (mode == 2 ? k_level_plain<2> : k_level_plain<3>),
+                              grid, dim3(256), 0, st, a.dg, a.rtab, a.pyr, l);
+            ORBX_TIMED_LAUNCH(T, K_LEVEL, k_blur_plain, grid, dim3(256), 0, st, a.dg,
+                              (const uint8_t*)a.pyr, a.blur, l);
         }
         if (l == 0) T.alias(K_LEVEL0);
     }
     return hipGetLastError();
 }
 
-
-hipError_t prepare_level(size_t lds) {
-    hipError_t e = hipSuccess;
-    for (int m = 0; m < 4 && e == hipSuccess; ++m)
-        e = hipFuncSetAttribute((const void*)level_kernel(m),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_pyr_chain<CHAIN_NT>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return e;
+hipError_t prepare_pyr_chain(size_t lds) {
+    return hipFuncSetAttribute((const void*)k_pyr_chain<CHAIN_NT>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
 }  // namespace orbx
