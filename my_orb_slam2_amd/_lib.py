@@ -312,3 +312,26 @@ def ptr(a) -> ctypes.c_void_p:
     if a is None:
         return ctypes.c_void_p(0)
     return ctypes.c_void_p(int(a))
+
+
+# ---- what the RANSAC solvers' modules (sim3.py, pnp.py) share -------------------------------------
+RAND_MAX = 2147483647
+
+
+def _sample_minimal_sets(fn: str, K: int, how_many: str, N: int, rand_values) -> np.ndarray:
+    """K raw rand() values per iteration -> (n_its, K) int32 minimal sets, by C function `fn`."""
+    r = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+    if r.size % K:
+        raise ValueError(f"{how_many} rand() values per iteration")
+    out = np.zeros((r.size // K, K), np.int32)
+    check(fn, getattr(load(), fn)(int(N), r.size // K, ptr(r), ptr(out)))
+    return out
+
+
+def _solver_limits(fn: str) -> dict:
+    """The four limits of the C function `fn` (orbx_sim3_limits, orbx_pnp_limits)."""
+    a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    d = ctypes.c_int64()
+    check(fn, getattr(load(), fn)(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c),
+                                  ctypes.byref(d)))
+    return dict(max_n=a.value, max_its=b.value, max_jobs=c.value, max_scratch_bytes=d.value)

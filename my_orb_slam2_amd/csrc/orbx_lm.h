@@ -5,7 +5,8 @@
 // OptimizationAlgorithmLevenberg::solve.  The edge models (error, Jacobian, update of the
 // estimate) stay with the kernels and reach the loop as callables; k_pose_opt runs lm_optimize,
 // k_sim3_opt keeps the same loop written out (it measured slower through the template).  row3 is
-// also orbx_sim3.hip's.
+// also orbx_sim3.hip's; the exactly rounded dv and sq are orbx_ransac.h's, shared with the RANSAC
+// solvers.
 // Built with -ffp-contract=off like the rest of the library: every operation is rounded on its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -13,6 +14,8 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+
+#include "orbx_ransac.h"
 
 namespace orbx {
 
@@ -22,9 +25,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 __device__ __forceinline__ bool uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-// IEEE division and square root whatever the compiler's defaults
-__device__ __forceinline__ double dv(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ double sq(double a) { return __dsqrt_rn(a); }
 
 // cv::gemm's small-matrix path for a 3x3 A (row-major) times a 3-vector: float products and sums
 __device__ __forceinline__ float row3(const float* A, int r, const float* b) {

@@ -17,27 +17,11 @@
 #include "orbx_host.h"
 #include "orbx_kernels.h"
 #include "orbx_match_kernels.h"
+#include "orbx_matcher.h"
 
 using namespace orbx;
 
 static_assert((int)ORBX_MK_COUNT <= (int)orbx::K_COUNT, "the matcher timer shares KernelTimer's slots");
-
-struct orbx_matcher {
-    orbx_matcher_params prm;
-    int ncu = 256;                     // compute units of the device (BF chunk sizing)
-    // d_bf_db: the database of orbx_hamming_bf_top2 (it may be gigabytes: not in a pooled slot)
-    DevBuf d_aux, d_proj, d_bf, d_bf_db, d_sim3, d_pnp;
-    int* d_err = nullptr;              // the capacity word of the *_device forms (orbx_matcher_sync)
-    KernelTimer timer;
-    std::mutex mu;
-    // recorded after the last brute-force launch (its partial-result scratch d_bf is shared by
-    // every call): a call on another stream waits for it before reusing the scratch
-    hipEvent_t bf_done = nullptr;
-    hipStream_t bf_stream = nullptr;
-    bool have_bf = false;
-    int bf_kernel = ORBX_BF_MFMA;
-    int bf_chunk = 0;               // orbx_matcher_set_bf_chunk: 0 = bf_chunk_rows
-};
 
 namespace {
 
@@ -695,112 +679,6 @@ orbx_status orbx_triangulate_matches_batch_device(
     L.err = m->d_err;
     if (!HIPOK(launch_triangulate_points(L, db->max_feat, njobs, (hipStream_t)stream)))
         return ORBX_ERR_DEVICE;
-    return ORBX_OK;
-}
-
-orbx_status orbx_sim3_iterate_batch_device(
-    orbx_matcher* m, const orbx_sim3_job* d_jobs, int32_t njobs, int32_t max_n,
-    int32_t max_call_its, const orbx_frame_pose* d_poses, int32_t nposes,
-    const orbx_sim3_corr* d_corr, int64_t ncorr, const int32_t* d_triples, int64_t ntriples,
-    orbx_sim3_state* d_state, orbx_sim3_result* d_results, uint8_t* d_inliers,
-    int64_t ninlier_bytes, void* stream) {
-    if (!m || njobs < 0 || max_n < 0 || max_call_its < 0 || nposes < 0 || ncorr < 0 ||
-        ntriples < 0 || ninlier_bytes < 0)
-        return ORBX_ERR_INVALID;
-    if (njobs == 0) return ORBX_OK;
-    if (!d_jobs || !d_poses || !d_triples || !d_state || !d_results || (ncorr > 0 && !d_corr) ||
-        (ninlier_bytes > 0 && !d_inliers))
-        return ORBX_ERR_INVALID;
-    if (njobs > SIM3_MAX_JOBS || max_n > SIM3_MAX_N || max_call_its > SIM3_MAX_ITS)
-        return ORBX_ERR_UNSUPPORTED;
-    const size_t bytes = sim3_scratch_bytes(njobs, max_n, max_call_its);
-    if (bytes > SIM3_MAX_SCRATCH) return ORBX_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    if (!m->d_sim3.ensure(bytes)) return ORBX_ERR_DEVICE;
-    Sim3Launch L{};
-    L.jobs = d_jobs;
-    L.njobs = njobs, L.max_n = max_n, L.max_call = max_call_its;
-    L.poses = d_poses;
-    L.nposes = nposes;
-    L.corr = d_corr;
-    L.ncorr = ncorr;
-    L.triples = d_triples;
-    L.ntriples = ntriples;
-    L.state = d_state;
-    L.res = d_results;
-    L.inliers = d_inliers;
-    L.ninliers = ninlier_bytes;
-    L.scratch = m->d_sim3.p;
-    if (!HIPOK(launch_sim3(L, (hipStream_t)stream))) return ORBX_ERR_DEVICE;
-    return ORBX_OK;
-}
-
-orbx_status orbx_pnp_iterate_batch_device(
-    orbx_matcher* m, const orbx_pnp_job* d_jobs, int32_t njobs, int32_t max_n,
-    int32_t max_call_its, const orbx_pnp_corr* d_corr, int64_t ncorr, const int32_t* d_quads,
-    int64_t nquads, orbx_pnp_state* d_state, uint8_t* d_best, int64_t nbest_bytes,
-    orbx_pnp_result* d_results, uint8_t* d_inliers, int64_t ninlier_bytes, void* stream) {
-    if (!m || njobs < 0 || max_n < 0 || max_call_its < 0 || ncorr < 0 || nquads < 0 ||
-        nbest_bytes < 0 || ninlier_bytes < 0)
-        return ORBX_ERR_INVALID;
-    if (njobs == 0) return ORBX_OK;
-    if (!d_jobs || !d_state || !d_results || (ncorr > 0 && !d_corr) || (nquads > 0 && !d_quads) ||
-        (nbest_bytes > 0 && !d_best) || (ninlier_bytes > 0 && !d_inliers))
-        return ORBX_ERR_INVALID;
-    if (njobs > PNP_MAX_JOBS || max_n > PNP_MAX_N || max_call_its > PNP_MAX_ITS)
-        return ORBX_ERR_UNSUPPORTED;
-    const size_t bytes = pnp_scratch_bytes(njobs, max_n, max_call_its);
-    if (bytes > PNP_MAX_SCRATCH) return ORBX_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    if (!m->d_pnp.ensure(bytes)) return ORBX_ERR_DEVICE;
-    PnpLaunch L{};
-    L.jobs = d_jobs;
-    L.njobs = njobs, L.max_n = max_n, L.max_call = max_call_its;
-    L.corr = d_corr;
-    L.ncorr = ncorr;
-    L.quads = d_quads;
-    L.nquads = nquads;
-    L.state = d_state;
-    L.best = d_best;
-    L.nbest = nbest_bytes;
-    L.res = d_results;
-    L.inliers = d_inliers;
-    L.ninliers = ninlier_bytes;
-    L.scratch = m->d_pnp.p;
-    if (!HIPOK(launch_pnp(L, (hipStream_t)stream))) return ORBX_ERR_DEVICE;
-    return ORBX_OK;
-}
-
-orbx_status orbx_sim3_optimize_batch_device(
-    orbx_matcher* m, const orbx_sim3opt_job* d_jobs, int32_t njobs, int32_t max_n,
-    const orbx_frame_pose* d_poses, int32_t nposes, const orbx_sim3opt_corr* d_corr, int64_t ncorr,
-    const void* d_sim3_in, int64_t sim3_in_stride, orbx_sim3opt_result* d_results,
-    uint8_t* d_keep, int64_t nkeep_bytes, void* stream) {
-    if (!m || njobs < 0 || max_n < 0 || nposes < 0 || ncorr < 0 || nkeep_bytes < 0)
-        return ORBX_ERR_INVALID;
-    if (njobs == 0) return ORBX_OK;
-    if (!d_jobs || !d_poses || !d_sim3_in || !d_results || (ncorr > 0 && !d_corr) ||
-        (nkeep_bytes > 0 && !d_keep) || sim3_in_stride < (int64_t)sizeof(orbx_sim3opt_in) ||
-        (sim3_in_stride & 3) || ((uintptr_t)d_sim3_in & 3))
-        return ORBX_ERR_INVALID;
-    if (njobs > SIM3OPT_MAX_JOBS || max_n > SIM3OPT_MAX_N) return ORBX_ERR_UNSUPPORTED;
-    std::lock_guard<std::mutex> lk(m->mu);
-    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
-    Sim3OptLaunch L{};
-    L.jobs = d_jobs;
-    L.njobs = njobs, L.max_n = max_n;
-    L.poses = d_poses;
-    L.nposes = nposes;
-    L.corr = d_corr;
-    L.ncorr = ncorr;
-    L.sim3_in = (const uint8_t*)d_sim3_in;
-    L.in_stride = sim3_in_stride;
-    L.res = d_results;
-    L.keep = d_keep;
-    L.nkeep = nkeep_bytes;
-    if (!HIPOK(launch_sim3_opt(L, (hipStream_t)stream))) return ORBX_ERR_DEVICE;
     return ORBX_OK;
 }
 

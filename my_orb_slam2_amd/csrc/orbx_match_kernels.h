@@ -74,8 +74,8 @@ struct TriPointsLaunch {
 hipError_t launch_triangulate_points(const TriPointsLaunch& a, int max_feat, int njobs,
                                      hipStream_t st);
 
-// Sim3Solver::iterate over njobs solvers (orbx_sim3.hip).  The array lengths bound what a job may
-// point at; scratch holds sim3_scratch_bytes(njobs, max_n, max_call) bytes.
+// Sim3Solver::iterate over njobs solvers (orbx_sim3.hip, which launches it and sizes scratch).  The
+// array lengths bound what a job may point at.
 struct Sim3Launch {
     const orbx_sim3_job* jobs;
     int njobs, max_n, max_call;
@@ -93,8 +93,6 @@ struct Sim3Launch {
 };
 constexpr int SIM3_MAX_N = 8192, SIM3_MAX_ITS = 4096, SIM3_MAX_JOBS = 65535;
 constexpr size_t SIM3_MAX_SCRATCH = (size_t)1 << 30;
-size_t sim3_scratch_bytes(int njobs, int max_n, int max_call);
-hipError_t launch_sim3(const Sim3Launch& a, hipStream_t st);
 
 // Optimizer::OptimizeSim3 over njobs candidates (orbx_sim3opt.hip): one wave per job, no scratch.
 // The array lengths bound what a job may point at.
@@ -112,10 +110,9 @@ struct Sim3OptLaunch {
     long long nkeep;
 };
 constexpr int SIM3OPT_MAX_N = 4096, SIM3OPT_MAX_JOBS = 65535;
-hipError_t launch_sim3_opt(const Sim3OptLaunch& a, hipStream_t st);
 
-// PnPsolver::iterate over njobs solvers (orbx_pnp.hip).  The array lengths bound what a job may
-// point at; scratch holds pnp_scratch_bytes(njobs, max_n, max_call) bytes.
+// PnPsolver::iterate over njobs solvers (orbx_pnp.hip, which launches it and sizes scratch).  The
+// array lengths bound what a job may point at.
 struct PnpLaunch {
     const orbx_pnp_job* jobs;
     int njobs, max_n, max_call;
@@ -133,8 +130,6 @@ struct PnpLaunch {
 };
 constexpr int PNP_MAX_N = 4096, PNP_MAX_ITS = 1024, PNP_MAX_JOBS = 4096;
 constexpr size_t PNP_MAX_SCRATCH = (size_t)1 << 30;
-size_t pnp_scratch_bytes(int njobs, int max_n, int max_call);
-hipError_t launch_pnp(const PnpLaunch& a, hipStream_t st);
 
 // Projection searches (modes of orbx_proj_mode plus PROJ_INIT) over njobs independent jobs
 // (frames).  With t_off == nullptr there is one job: target T, queries [0, nq).  Otherwise

@@ -20,6 +20,10 @@
 // the lanes compute the terms and every lane adds them in index order from lane reads (`ssum`,
 // the row products of the Jacobi sweeps, sum2 of reprojection_error).  Nothing is tree-reduced.
 //
+// What is RANSAC and not EPnP (the sampling, the iteration count, the window of a call, the cursor
+// scratch_of() is written with) is orbx_ransac.h's, shared with orbx_sim3.hip.  Every entry point
+// is here: orbx_pnp_iterate, and the three *_batch_device forms on a handle (orbx_matcher.h).
+//
 // The library is built with -ffp-contract=off: every operation below is rounded on its own as on
 // x86-64.  The forms evaluated inside OpenCV 3.2 (cvMulTransposed, cvSVD / cvInvert / cvSolve over
 // JacobiSVDImpl_<double> and SVBkSb, Mat::convertTo) are restated and PARITY UNPINNED.
@@ -34,6 +38,8 @@
 #include "orbx_host.h"
 #include "orbx_hypot.h"
 #include "orbx_match_kernels.h"
+#include "orbx_matcher.h"
+#include "orbx_ransac.h"
 
 using namespace orbx;
 
@@ -43,9 +49,6 @@ constexpr double DBL_EPS = 2.220446049250313e-16;
 constexpr double DBL_MINV = 2.2250738585072014e-308;
 constexpr int SVD_SWEEPS = 30;        // max(m, 30) with m <= 12 (lapack.cpp, JacobiSVDImpl_)
 constexpr int SVD_COMPLETION_TRIES = 100;
-
-__device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ double dsqrt(double a) { return __dsqrt_rn(a); }
 
 // What k_pnp_hypotheses leaves per iteration (104 bytes).
 struct PnpHyp {
@@ -107,17 +110,17 @@ __device__ __forceinline__ void jacobi_svd(double* At, double* Vt, double* W, co
                 const double ai = ka ? At[i * M + lane] : 0.0, aj = ka ? At[j * M + lane] : 0.0;
                 double a = W[i], b = W[j];
                 double p = ssum<M>(ai * aj);
-                if (fabs(p) <= eps * dsqrt(a * b)) continue;
+                if (fabs(p) <= eps * sq(a * b)) continue;
                 p = p * 2.0;
                 const double beta = a - b, gamma = glibc_hypot(p, beta);
                 double c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;
-                    s = dsqrt(ddiv(delta, gamma));
-                    c = ddiv(p, gamma * s * 2.0);
+                    s = sq(dv(delta, gamma));
+                    c = dv(p, gamma * s * 2.0);
                 } else {
-                    c = dsqrt(ddiv(gamma + beta, gamma * 2.0));
-                    s = ddiv(p, gamma * c * 2.0);
+                    c = sq(dv(gamma + beta, gamma * 2.0));
+                    s = dv(p, gamma * c * 2.0);
                 }
                 const double t0 = c * ai + s * aj, t1 = -s * ai + c * aj;
                 if (ka) At[i * M + lane] = t0, At[j * M + lane] = t1;
@@ -136,7 +139,7 @@ __device__ __forceinline__ void jacobi_svd(double* At, double* Vt, double* W, co
     }
     for (int i = 0; i < N; ++i) {
         const double t = ka ? At[i * M + lane] : 0.0;
-        W[i] = dsqrt(ssum<M>(t * t));
+        W[i] = sq(ssum<M>(t * t));
     }
     for (int i = 0; i < N - 1; ++i) {
         int j = i;
@@ -163,7 +166,7 @@ __device__ __forceinline__ void jacobi_svd(double* At, double* Vt, double* W, co
         double mine = ka ? At[i * M + lane] : 0.0;   // this lane's entry of row i
         for (int ii = 0; ii < SVD_COMPLETION_TRIES && sd <= DBL_MINV; ++ii) {
             flags |= ORBX_PNP_SVD_COMPLETED;
-            const double val0 = ddiv(1.0, (double)M);
+            const double val0 = dv(1.0, (double)M);
 #pragma unroll
             for (int k = 0; k < M; ++k) {
                 const double val = (rng.next() & 256) != 0 ? val0 : -val0;
@@ -177,12 +180,12 @@ __device__ __forceinline__ void jacobi_svd(double* At, double* Vt, double* W, co
                     double asum = 0.0;
 #pragma unroll
                     for (int k = 0; k < M; ++k) asum = asum + fabs(__shfl(mine, k, 64));
-                    asum = asum > eps * 100 ? ddiv(1.0, asum) : 0.0;
+                    asum = asum > eps * 100 ? dv(1.0, asum) : 0.0;
                     mine = mine * asum;
                 }
-            sd = dsqrt(ssum<M>(mine * mine));
+            sd = sq(ssum<M>(mine * mine));
         }
-        const double s = sd > DBL_MINV ? ddiv(1.0, sd) : 0.0;
+        const double s = sd > DBL_MINV ? dv(1.0, sd) : 0.0;
         if (ka) At[i * M + lane] = mine * s;
     }
     __syncthreads();
@@ -219,7 +222,7 @@ __device__ __forceinline__ void solve_6xn(PnpLds& s, const int NC, uint32_t cols
         const double u = lane < 6 ? s.sAt[i * 6 + lane] : 0.0;
         double sum = ssum<6>(u * rl);
         if (fabs(wi) <= thr) continue;
-        wi = ddiv(1.0, wi);
+        wi = dv(1.0, wi);
         sum = sum * wi;
 #pragma unroll
         for (int j = 0; j < 5; ++j)
@@ -241,14 +244,14 @@ __device__ __forceinline__ bool qr_solve_6x4(double (*A)[4], double* b, double* 
             if (eta < elt) eta = elt;
         }
         if (eta == 0) return false;
-        const double inv_eta = ddiv(1.0, eta);
+        const double inv_eta = dv(1.0, eta);
         double sum = 0.0;
 #pragma unroll
         for (int i = k; i < 6; ++i) {
             A[i][k] = A[i][k] * inv_eta;
             sum = sum + A[i][k] * A[i][k];
         }
-        double sigma = dsqrt(sum);
+        double sigma = sq(sum);
         if (A[k][k] < 0) sigma = -sigma;
         A[k][k] = A[k][k] + sigma;
         A1[k] = sigma * A[k][k];
@@ -258,7 +261,7 @@ __device__ __forceinline__ bool qr_solve_6x4(double (*A)[4], double* b, double* 
             double sj = 0.0;
 #pragma unroll
             for (int i = k; i < 6; ++i) sj = sj + A[i][k] * A[i][j];
-            const double tau = ddiv(sj, A1[k]);
+            const double tau = dv(sj, A1[k]);
 #pragma unroll
             for (int i = k; i < 6; ++i) A[i][j] = A[i][j] - tau * A[i][k];
         }
@@ -268,17 +271,17 @@ __device__ __forceinline__ bool qr_solve_6x4(double (*A)[4], double* b, double* 
         double tau = 0.0;
 #pragma unroll
         for (int i = j; i < 6; ++i) tau = tau + A[i][j] * b[i];
-        tau = ddiv(tau, A1[j]);
+        tau = dv(tau, A1[j]);
 #pragma unroll
         for (int i = j; i < 6; ++i) b[i] = b[i] - tau * A[i][j];
     }
-    x[3] = ddiv(b[3], A2[3]);
+    x[3] = dv(b[3], A2[3]);
 #pragma unroll
     for (int i = 2; i >= 0; --i) {
         double sum = 0.0;
 #pragma unroll
         for (int j = i + 1; j < 4; ++j) sum = sum + A[i][j] * x[j];
-        x[i] = ddiv(b[i] - sum, A2[i]);
+        x[i] = dv(b[i] - sum, A2[i]);
     }
     return true;
 }
@@ -354,7 +357,7 @@ __device__ __forceinline__ double pose_of_betas(const PnpPoints& P, const PnpCam
             for (int i = 0; i < n; ++i) acc = acc + pcs[3 * (size_t)i + lane];
         else
             for (int i = 0; i < n; ++i) acc = acc + P.X(i, lane - 3);
-        s.m6[lane] = ddiv(acc, fn);
+        s.m6[lane] = dv(acc, fn);
     }
     __syncthreads();
     const double pc0[3] = {s.m6[0], s.m6[1], s.m6[2]}, pw0[3] = {s.m6[3], s.m6[4], s.m6[5]};
@@ -388,25 +391,25 @@ __device__ __forceinline__ double pose_of_betas(const PnpPoints& P, const PnpCam
         if (i < n) {
             const double pw[3] = {P.X(i, 0), P.X(i, 1), P.X(i, 2)};
             const double Xc = dot3(R, pw) + t[0], Yc = dot3(R + 3, pw) + t[1];
-            const double inv_Zc = ddiv(1.0, dot3(R + 6, pw) + t[2]);
+            const double inv_Zc = dv(1.0, dot3(R + 6, pw) + t[2]);
             const double ue = K.uc + K.fu * Xc * inv_Zc, ve = K.vc + K.fv * Yc * inv_Zc;
             const double u = P.u(i), v = P.v(i);
-            term = dsqrt((u - ue) * (u - ue) + (v - ve) * (v - ve));
+            term = sq((u - ue) * (u - ue) + (v - ve) * (v - ve));
         }
         const int m = n - base < 64 ? n - base : 64;
         for (int k = 0; k < m; ++k) sum2 = sum2 + __shfl(term, k, 64);
     }
     __syncthreads();
-    return ddiv(sum2, fn);
+    return dv(sum2, fn);
 }
 
 // Column i of M's row pair for one correspondence (fill_M, :436-451): comp = i % 3 of control
 // point i / 3; par = 0 the u row, 1 the v row.  The zero entries take part in the products.
-__device__ __forceinline__ double m_entry(double a, int comp, int par, const PnpCam& K, double du,
-                                          double dv) {
+__device__ __forceinline__ double m_entry(double a, int comp, int par, const PnpCam& K, double ud,
+                                          double vd) {
     if (comp == 0) return par == 0 ? a * K.fu : 0.0;
     if (comp == 1) return par == 1 ? a * K.fv : 0.0;
-    return a * (par == 0 ? du : dv);
+    return a * (par == 0 ? ud : vd);
 }
 
 // compute_pose (:477-525) over P by the whole wave: R (row-major) and t in every lane.  alphas
@@ -420,7 +423,7 @@ __device__ __forceinline__ void epnp_pose(const PnpPoints& P, const PnpCam& K, d
     if (lane < 3) {
         double acc = 0.0;
         for (int i = 0; i < n; ++i) acc = acc + P.X(i, lane);
-        s.m6[lane] = ddiv(acc, fn);
+        s.m6[lane] = dv(acc, fn);
     }
     __syncthreads();
     double cw[12];   // cws, row-major
@@ -440,7 +443,7 @@ __device__ __forceinline__ void epnp_pose(const PnpPoints& P, const PnpCam& K, d
     jacobi_svd<3, false>(s.sAt, s.sVt, s.sW, 3, lane, flags);   // dc = sW, uct = sAt
 #pragma unroll
     for (int i = 1; i < 4; ++i) {
-        const double k = dsqrt(ddiv(s.sW[i - 1], fn));
+        const double k = sq(dv(s.sW[i - 1], fn));
 #pragma unroll
         for (int j = 0; j < 3; ++j) cw[3 * i + j] = cw[j] + k * s.sAt[3 * (i - 1) + j];
     }
@@ -478,7 +481,7 @@ __device__ __forceinline__ void epnp_pose(const PnpPoints& P, const PnpCam& K, d
         for (int i = 0; i < 3; ++i) {
             double wi = s.sW[i];
             if (fabs(wi) <= thr) continue;
-            wi = ddiv(1.0, wi);
+            wi = dv(1.0, wi);
             double buf[3];
 #pragma unroll
             for (int j = 0; j < 3; ++j) buf[j] = s.sAt[i * 3 + j] * wi;
@@ -511,9 +514,9 @@ __device__ __forceinline__ void epnp_pose(const PnpPoints& P, const PnpCam& K, d
         double acc = 0.0;
         for (int c = 0; c < n; ++c) {
             const double ai = alphas[4 * (size_t)c + pi], aj = alphas[4 * (size_t)c + pj];
-            const double du = K.uc - P.u(c), dv = K.vc - P.v(c);
-            acc = acc + m_entry(ai, compi, 0, K, du, dv) * m_entry(aj, compj, 0, K, du, dv);
-            acc = acc + m_entry(ai, compi, 1, K, du, dv) * m_entry(aj, compj, 1, K, du, dv);
+            const double ud = K.uc - P.u(c), vd = K.vc - P.v(c);
+            acc = acc + m_entry(ai, compi, 0, K, ud, vd) * m_entry(aj, compj, 0, K, ud, vd);
+            acc = acc + m_entry(ai, compi, 1, K, ud, vd) * m_entry(aj, compj, 1, K, ud, vd);
         }
         s.At12[ri * 12 + rj] = acc;
         s.At12[rj * 12 + ri] = acc;
@@ -549,26 +552,26 @@ __device__ __forceinline__ void epnp_pose(const PnpPoints& P, const PnpCam& K, d
                   flags);
         if (kind == 1) {
             if (b[0] < 0) {
-                betas[0] = dsqrt(-b[0]);
-                betas[1] = ddiv(-b[1], betas[0]);
-                betas[2] = ddiv(-b[2], betas[0]);
-                betas[3] = ddiv(-b[3], betas[0]);
+                betas[0] = sq(-b[0]);
+                betas[1] = dv(-b[1], betas[0]);
+                betas[2] = dv(-b[2], betas[0]);
+                betas[3] = dv(-b[3], betas[0]);
             } else {
-                betas[0] = dsqrt(b[0]);
-                betas[1] = ddiv(b[1], betas[0]);
-                betas[2] = ddiv(b[2], betas[0]);
-                betas[3] = ddiv(b[3], betas[0]);
+                betas[0] = sq(b[0]);
+                betas[1] = dv(b[1], betas[0]);
+                betas[2] = dv(b[2], betas[0]);
+                betas[3] = dv(b[3], betas[0]);
             }
         } else {
             if (b[0] < 0) {
-                betas[0] = dsqrt(-b[0]);
-                betas[1] = (b[2] < 0) ? dsqrt(-b[2]) : 0.0;
+                betas[0] = sq(-b[0]);
+                betas[1] = (b[2] < 0) ? sq(-b[2]) : 0.0;
             } else {
-                betas[0] = dsqrt(b[0]);
-                betas[1] = (b[2] > 0) ? dsqrt(b[2]) : 0.0;
+                betas[0] = sq(b[0]);
+                betas[1] = (b[2] > 0) ? sq(b[2]) : 0.0;
             }
             if (b[1] < 0) betas[0] = -betas[0];
-            betas[2] = kind == 3 ? ddiv(b[3], betas[0]) : 0.0;
+            betas[2] = kind == 3 ? dv(b[3], betas[0]) : 0.0;
             betas[3] = 0.0;
         }
         gauss_newton(s, rho, betas, flags);
@@ -589,7 +592,7 @@ __device__ __forceinline__ bool is_inlier(const orbx_pnp_corr& c, const double* 
     const double x = (double)c.X[0], y = (double)c.X[1], z = (double)c.X[2];
     const float Xc = (float)(R[0] * x + R[1] * y + R[2] * z + t[0]);
     const float Yc = (float)(R[3] * x + R[4] * y + R[5] * z + t[1]);
-    const float invZc = (float)ddiv(1.0, R[6] * x + R[7] * y + R[8] * z + t[2]);
+    const float invZc = (float)dv(1.0, R[6] * x + R[7] * y + R[8] * z + t[2]);
     const double ue = K.uc + K.fu * (double)Xc * (double)invZc;
     const double ve = K.vc + K.fv * (double)Yc * (double)invZc;
     const float distX = (float)((double)c.u - ue);
@@ -605,34 +608,30 @@ __device__ __forceinline__ float max_error_of(const orbx_pnp_job& J, int octave)
 }
 
 struct PnpScratch {
-    uint32_t* info;      // per job: what k_pnp_hypotheses refused
+    uint32_t* info;      // per job: what k_pnp_hypotheses refused; first: launch_pnp zeroes it
     PnpHyp* hyp;         // [njobs][max_call]
     uint64_t* mask;      // [njobs][max_call][words]
     int32_t* idx;        // [njobs][max_n]: Refine's vIndices
     double* work;        // [njobs][7 * max_n]: Refine's alphas, then its pcs
     int words;
+    size_t end;          // the bytes of the whole
 };
 __host__ __device__ inline PnpScratch scratch_of(void* base, int njobs, int max_n, int max_call) {
+    ScratchCursor c{(uint8_t*)base};
     PnpScratch s;
     s.words = (max_n + 63) / 64;
-    uint8_t* p = (uint8_t*)base;
-    s.info = (uint32_t*)p;
-    p += al256(4 * (size_t)njobs);
-    s.hyp = (PnpHyp*)p;
-    p += al256(sizeof(PnpHyp) * (size_t)njobs * (size_t)max_call);
-    s.mask = (uint64_t*)p;
-    p += al256(8 * (size_t)njobs * (size_t)max_call * (size_t)s.words);
-    s.idx = (int32_t*)p;
-    p += al256(4 * (size_t)njobs * (size_t)max_n);
-    s.work = (double*)p;
+    s.info = c.take<uint32_t>(njobs);
+    s.hyp = c.take<PnpHyp>(njobs, max_call);
+    s.mask = c.take<uint64_t>(njobs, max_call, s.words);
+    s.idx = c.take<int32_t>(njobs, max_n);
+    s.work = c.take<double>(7, njobs, max_n);
+    s.end = c.end;
     return s;
 }
 
-// The iterations of this call: [S.iterations, S.iterations + pnp_window(J, S)) (`||` at :182)
+// The iterations of this call: [S.iterations, S.iterations + pnp_window(J, S))
 __device__ __forceinline__ long long pnp_window(const orbx_pnp_job& J, const orbx_pnp_state& S) {
-    long long w = (long long)J.max_its - S.iterations;
-    if (w < J.n_iterations) w = J.n_iterations;
-    return w < 0 ? 0 : w;
+    return ransac_window_or(J.max_its, S.iterations, J.n_iterations);
 }
 
 // What the job record and the state show; the same in both kernels.
@@ -702,18 +701,6 @@ __global__ __launch_bounds__(64) void k_pnp_hypotheses(const PnpLaunch g) {
         H.count = count;
         H.flags = flags;
     }
-}
-
-// Mat::convertTo(CV_32F) of mRi / mti into a 4x4 identity (:217-223, :294-300)
-__device__ __forceinline__ void tcw_of(const double* R, const double* t, float* T) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) T[4 * i + c] = (float)R[3 * i + c];
-        T[4 * i + 3] = (float)t[i];
-        T[12 + i] = 0.0f;
-    }
-    T[15] = 1.0f;
 }
 
 // Grid (njobs), one wave each.
@@ -792,7 +779,7 @@ __global__ __launch_bounds__(64) void k_pnp_select(const PnpLaunch g) {
                 const uint64_t* mask = sc.mask + ((size_t)j * g.max_call + h) * sc.words;
                 for (int i = lane; i < N; i += 64) best[i] = (uint8_t)((mask[i >> 6] >> (i & 63)) & 1);
                 nbest = cnt;
-                tcw_of(hyp[h].R, hyp[h].t, bestT);
+                rt_to_4x4(hyp[h].R, hyp[h].t, bestT);   // mRi / mti into mBestTcw (:217-223)
                 best_written = true;
                 refined_in_vain = false;
                 __syncthreads();
@@ -822,7 +809,7 @@ __global__ __launch_bounds__(64) void k_pnp_select(const PnpLaunch g) {
             }
             if (cnt2 > min_in) {          // :292
                 found = 1, source = 1, n_inliers = cnt2;
-                tcw_of(R2, t2, outT);
+                rt_to_4x4(R2, t2, outT);   // mRefinedTcw (:294-300)
             } else {
                 refined_in_vain = true;
             }
@@ -949,16 +936,8 @@ __global__ __launch_bounds__(256) void k_pnp_apply(
     }
 }
 
-}  // namespace
-
-namespace orbx {
-
 size_t pnp_scratch_bytes(int njobs, int max_n, int max_call) {
-    // the five blocks of scratch_of
-    const size_t words = ((size_t)max_n + 63) / 64;
-    return al256(4 * (size_t)njobs) + al256(sizeof(PnpHyp) * (size_t)njobs * (size_t)max_call) +
-           al256(8 * (size_t)njobs * (size_t)max_call * words) +
-           al256(4 * (size_t)njobs * (size_t)max_n) + al256(56 * (size_t)njobs * (size_t)max_n);
+    return scratch_of(nullptr, njobs, max_n, max_call).end;
 }
 
 hipError_t launch_pnp(const PnpLaunch& a, hipStream_t st) {
@@ -970,27 +949,14 @@ hipError_t launch_pnp(const PnpLaunch& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-hipError_t launch_pnp_correspondences(int njobs, const int32_t* match, long long match_stride,
-                                      const orbx_keypoint* kp, int n_feat,
-                                      const orbx_map_point* mps, const int32_t* mp_off,
-                                      orbx_pnp_corr* corr, long long corr_stride, int32_t* outN,
-                                      int32_t* out_flags, hipStream_t st) {
-    hipLaunchKernelGGL(k_pnp_correspondences, dim3(njobs), dim3(256), 0, st, match, match_stride, kp,
-                       n_feat, mps, mp_off, corr, corr_stride, outN, out_flags);
-    return hipGetLastError();
+// What a launch may ask for, for the host-array and the batch entry alike.  its: the most
+// iterations of a job (its max_its) or of the call.
+bool pnp_within_limits(int njobs, int max_n, long long its) {
+    return njobs <= PNP_MAX_JOBS && max_n <= PNP_MAX_N && its <= PNP_MAX_ITS &&
+           pnp_scratch_bytes(njobs, max_n, (int)its) <= PNP_MAX_SCRATCH;
 }
 
-hipError_t launch_pnp_apply(int njobs, const orbx_pnp_job* jobs, const orbx_pnp_result* results,
-                            const uint8_t* inliers, long long ninliers, const int32_t* match,
-                            long long match_stride, int n_feat, const orbx_frame_pose* tmpl,
-                            orbx_frame_pose* poses, int32_t* mp_of_feat, long long feat_stride,
-                            hipStream_t st) {
-    hipLaunchKernelGGL(k_pnp_apply, dim3(njobs), dim3(256), 0, st, jobs, results, inliers, ninliers,
-                       match, match_stride, n_feat, tmpl, poses, mp_of_feat, feat_stride);
-    return hipGetLastError();
-}
-
-}  // namespace orbx
+}  // namespace
 
 extern "C" {
 
@@ -1005,45 +971,14 @@ orbx_status orbx_pnp_ransac_parameters(double prob, int32_t min_inliers, int32_t
     if (nMinInliers < min_set) nMinInliers = min_set;
     const float ratio = (float)nMinInliers / (float)N;
     if (mRansacEpsilon < ratio) mRansacEpsilon = ratio;
-    int nIterations;
-    if (nMinInliers == N)
-        nIterations = 1;
-    else
-        nIterations = cvtt(::ceil(::log(1 - prob) / ::log(1 - ::pow((double)mRansacEpsilon, 3.0))));
-    const int lo = nIterations < max_its ? nIterations : max_its;
     *min_inliers_out = nMinInliers;
-    *max_its_out = lo > 1 ? lo : 1;
+    *max_its_out = ransac_iterations(prob, mRansacEpsilon, nMinInliers == N, max_its);
     return ORBX_OK;
 }
 
 orbx_status orbx_pnp_sample_quads(int32_t N, int32_t n_its, const int32_t* rand_values,
                                   int32_t* quads) {
-    if (N < 4 || n_its < 0 || (n_its > 0 && (!rand_values || !quads))) return ORBX_ERR_INVALID;
-    for (int64_t k = 0; k < 4 * (int64_t)n_its; ++k)
-        if (rand_values[k] < 0) return ORBX_ERR_INVALID;   // RAND_MAX is INT_MAX
-    // vAvailableIndices starts as 0 .. N-1 in every iteration, so the four swap-with-last steps
-    // touch at most four positions: pos[] / val[] hold the positions overwritten so far
-    for (int32_t it = 0; it < n_its; ++it) {
-        int32_t pos[4], val[4];
-        int nmod = 0;
-        int32_t size = N;
-        for (int i = 0; i < 4; ++i) {
-            const int randi =
-                (int)(((double)rand_values[4 * (size_t)it + i] / ((double)RAND_MAX + 1.0)) * size);
-            auto at = [&](int32_t p) {
-                int32_t v = p;
-                for (int m = 0; m < nmod; ++m)
-                    if (pos[m] == p) v = val[m];
-                return v;
-            };
-            quads[4 * (size_t)it + i] = at(randi);
-            pos[nmod] = randi;
-            val[nmod] = at(size - 1);
-            ++nmod;
-            --size;
-        }
-    }
-    return ORBX_OK;
+    return sample_minimal_sets<4>(N, n_its, rand_values, quads);
 }
 
 orbx_status orbx_pnp_limits(int32_t* max_n, int32_t* max_its, int32_t* max_jobs,
@@ -1062,12 +997,10 @@ orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
     if (job->N < 0 || job->n_matches < 0 || job->max_its < 1 || state->iterations < 0 ||
         (job->N > 0 && (!corr || !best)) || (job->n_matches > 0 && !inliers))
         return ORBX_ERR_INVALID;
-    long long window = (long long)job->max_its - state->iterations;
-    if (window < job->n_iterations) window = job->n_iterations;
-    if (window < 0) window = 0;
+    const long long window = ransac_window_or(job->max_its, state->iterations, job->n_iterations);
     const long long nq = (long long)state->iterations + window;
     if (nq > 0 && !quads) return ORBX_ERR_INVALID;
-    if (job->N > PNP_MAX_N || job->max_its > PNP_MAX_ITS || window > PNP_MAX_ITS ||
+    if (!pnp_within_limits(1, job->N, window < job->max_its ? job->max_its : window) ||
         nq > INT_MAX / 4)
         return ORBX_ERR_UNSUPPORTED;
     HostCall c(device);
@@ -1100,6 +1033,39 @@ orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
     return c.finish(HIPOK(launch_pnp(L, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
 }
 
+orbx_status orbx_pnp_iterate_batch_device(
+    orbx_matcher* m, const orbx_pnp_job* d_jobs, int32_t njobs, int32_t max_n,
+    int32_t max_call_its, const orbx_pnp_corr* d_corr, int64_t ncorr, const int32_t* d_quads,
+    int64_t nquads, orbx_pnp_state* d_state, uint8_t* d_best, int64_t nbest_bytes,
+    orbx_pnp_result* d_results, uint8_t* d_inliers, int64_t ninlier_bytes, void* stream) {
+    if (!m || njobs < 0 || max_n < 0 || max_call_its < 0 || ncorr < 0 || nquads < 0 ||
+        nbest_bytes < 0 || ninlier_bytes < 0)
+        return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_jobs || !d_state || !d_results || (ncorr > 0 && !d_corr) || (nquads > 0 && !d_quads) ||
+        (nbest_bytes > 0 && !d_best) || (ninlier_bytes > 0 && !d_inliers))
+        return ORBX_ERR_INVALID;
+    if (!pnp_within_limits(njobs, max_n, max_call_its)) return ORBX_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
+    if (!m->d_pnp.ensure(pnp_scratch_bytes(njobs, max_n, max_call_its))) return ORBX_ERR_DEVICE;
+    PnpLaunch L{};
+    L.jobs = d_jobs;
+    L.njobs = njobs, L.max_n = max_n, L.max_call = max_call_its;
+    L.corr = d_corr;
+    L.ncorr = ncorr;
+    L.quads = d_quads;
+    L.nquads = nquads;
+    L.state = d_state;
+    L.best = d_best;
+    L.nbest = nbest_bytes;
+    L.res = d_results;
+    L.inliers = d_inliers;
+    L.ninliers = ninlier_bytes;
+    L.scratch = m->d_pnp.p;
+    return HIPOK(launch_pnp(L, (hipStream_t)stream)) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
 orbx_status orbx_pnp_correspondences_batch_device(
     orbx_matcher* m, int32_t njobs, const int32_t* d_match, int64_t match_stride,
     const orbx_keypoint* d_kp, int32_t n_feat, const orbx_map_point* d_mps,
@@ -1112,11 +1078,10 @@ orbx_status orbx_pnp_correspondences_batch_device(
     if (!d_mp_off || !d_N || (n_feat > 0 && (!d_match || !d_kp || !d_mps || !d_corr)))
         return ORBX_ERR_INVALID;
     if (njobs > PNP_MAX_JOBS) return ORBX_ERR_UNSUPPORTED;
-    if (!HIPOK(launch_pnp_correspondences(njobs, d_match, match_stride, d_kp, n_feat, d_mps,
-                                          d_mp_off, d_corr, corr_stride, d_N, d_N_flags,
-                                          (hipStream_t)stream)))
-        return ORBX_ERR_DEVICE;
-    return ORBX_OK;
+    hipLaunchKernelGGL(k_pnp_correspondences, dim3(njobs), dim3(256), 0, (hipStream_t)stream,
+                       d_match, match_stride, d_kp, n_feat, d_mps, d_mp_off, d_corr, corr_stride,
+                       d_N, d_N_flags);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
 orbx_status orbx_pnp_apply_batch_device(
@@ -1132,11 +1097,10 @@ orbx_status orbx_pnp_apply_batch_device(
         (n_feat > 0 && (!d_match || !d_mp_of_feat)) || (ninlier_bytes > 0 && !d_inliers))
         return ORBX_ERR_INVALID;
     if (njobs > PNP_MAX_JOBS) return ORBX_ERR_UNSUPPORTED;
-    if (!HIPOK(launch_pnp_apply(njobs, d_jobs, d_results, d_inliers, ninlier_bytes, d_match,
-                                match_stride, n_feat, d_template, d_poses, d_mp_of_feat,
-                                feat_stride, (hipStream_t)stream)))
-        return ORBX_ERR_DEVICE;
-    return ORBX_OK;
+    hipLaunchKernelGGL(k_pnp_apply, dim3(njobs), dim3(256), 0, (hipStream_t)stream, d_jobs,
+                       d_results, d_inliers, ninlier_bytes, d_match, match_stride, n_feat,
+                       d_template, d_poses, d_mp_of_feat, feat_stride);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
 }  // extern "C"

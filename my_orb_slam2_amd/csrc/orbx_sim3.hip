@@ -10,6 +10,10 @@
 //   k_sim3_select      one wave per job: the iterations' counts walked in order against the running
 //                      best (:183-199), the returned model re-scored for the inlier bytes, the state
 //
+// What is RANSAC and not Horn (the sampling, the iteration count, the window of a call, the cursor
+// scratch_of() is written with) is orbx_ransac.h's, shared with orbx_pnp.hip.  Both entry points
+// are here: orbx_sim3_iterate, and orbx_sim3_iterate_batch_device on a handle (orbx_matcher.h).
+//
 // The library is built with -ffp-contract=off: every operation below is rounded on its own as on
 // x86-64.  The forms evaluated inside OpenCV 3.2 (cv::reduce, Mat::convertTo, cv::gemm's two paths,
 // cv::eigen's JacobiImpl_<float>, cv::norm, cv::Rodrigues, Mat::dot, cv::pow) are restated and
@@ -26,7 +30,9 @@
 #include "orbx_host.h"
 #include "orbx_lm.h"
 #include "orbx_match_kernels.h"
+#include "orbx_matcher.h"
 #include "orbx_math.h"
+#include "orbx_ransac.h"
 
 using namespace orbx;
 
@@ -47,14 +53,6 @@ struct Sim3Hyp {
     float sRinv[9], tinv[3];  // mT21i
     int32_t count;            // mnInliersi
 };
-
-__device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
-__device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ double dsqrt(double a) { return __dsqrt_rn(a); }
-// sqrtf correctly rounded whatever the compiler's defaults (__fsqrt_rn is the native, approximate
-// instruction unless the headers are configured otherwise): the double square root of a float,
-// rounded to float, is the correctly rounded float square root (53 >= 2 * 24 + 2 bits)
-__device__ __forceinline__ float fsqrt(float a) { return (float)__dsqrt_rn((double)a); }
 
 // Mat::convertTo(alpha) on a CV_32F value: a plain copy when |alpha - 1| < DBL_EPSILON, otherwise
 // x * (float)alpha + 0.0f
@@ -259,22 +257,22 @@ __device__ __forceinline__ void compute_sim3(const float (*P1)[3], const float (
     double ss = 0.0;
 #pragma unroll
     for (int k = 1; k < 4; ++k) ss = ss + (double)q[k] * (double)q[k];
-    const double nrm = dsqrt(ss);
+    const double nrm = sq(ss);
     const double ang = orbx_atan2_f64(nrm, (double)q[0]);
-    const double alpha = (2 * ang) * ddiv(1.0, nrm);
+    const double alpha = (2 * ang) * dv(1.0, nrm);
     float vec[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) vec[k] = cvt_scale(q[k + 1], alpha);
     // cv::Rodrigues of the 1x3 float vector
     double rx = vec[0], ry = vec[1], rz = vec[2];
-    const double theta = dsqrt((rx * rx + ry * ry) + rz * rz);
+    const double theta = sq((rx * rx + ry * ry) + rz * rz);
     if (theta < 2.220446049250313e-16) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) H.R[k] = (k == 0 || k == 4 || k == 8) ? 1.0f : 0.0f;
     } else {
         double c, s;
         if (!orbx_sincos_f64(theta, &s, &c)) s = c = (double)NAN;   // theta is NaN (<= 2*pi else)
-        const double c1 = 1. - c, itheta = ddiv(1., theta);
+        const double c1 = 1. - c, itheta = dv(1., theta);
         rx *= itheta, ry *= itheta, rz *= itheta;
         const double rrt[9] = {rx * rx, rx * ry, rx * rz, rx * ry, ry * ry,
                                ry * rz, rx * rz, ry * rz, rz * rz};
@@ -308,7 +306,7 @@ __device__ __forceinline__ void compute_sim3(const float (*P1)[3], const float (
         double den = 0.0;
 #pragma unroll
         for (int i = 0; i < 9; ++i) den = den + (double)(b[i] * b[i]);   // cv::pow(P3, 2) in float
-        H.s = (float)ddiv(nom, den);
+        H.s = (float)dv(nom, den);
     } else {
         H.s = 1.0f;
     }
@@ -318,7 +316,7 @@ __device__ __forceinline__ void compute_sim3(const float (*P1)[3], const float (
     for (int r = 0; r < 3; ++r)
         H.t[r] = (float)((double)row3(H.R, r, O2) * -ds12 + (double)O1[r] * 1.0);
     // sR = ms12i*mR12i, sRinv = (1.0/ms12i)*mR12i.t(): convertTo scalings
-    const double inv_s = ddiv(1.0, ds12);
+    const double inv_s = dv(1.0, ds12);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
@@ -366,26 +364,24 @@ __device__ __forceinline__ float max_error(float sigma2) {
 }
 
 struct Sim3Scratch {
-    uint32_t* info;
-    Sim3Prep* prep;
-    Sim3Hyp* hyp;
+    uint32_t* info;      // per job: what the kernels refused; first: launch_sim3 zeroes it
+    Sim3Prep* prep;      // [njobs][max_n]
+    Sim3Hyp* hyp;        // [njobs][max_call]
+    size_t end;          // the bytes of the whole
 };
 __host__ __device__ inline Sim3Scratch scratch_of(void* base, int njobs, int max_n, int max_call) {
+    ScratchCursor c{(uint8_t*)base};
     Sim3Scratch s;
-    uint8_t* p = (uint8_t*)base;
-    s.info = (uint32_t*)p;
-    p += al256(4 * (size_t)njobs);
-    s.prep = (Sim3Prep*)p;
-    p += al256(sizeof(Sim3Prep) * (size_t)njobs * (size_t)max_n);
-    s.hyp = (Sim3Hyp*)p;
+    s.info = c.take<uint32_t>(njobs);
+    s.prep = c.take<Sim3Prep>(njobs, max_n);
+    s.hyp = c.take<Sim3Hyp>(njobs, max_call);
+    s.end = c.end;
     return s;
 }
 
 // The iterations of this call: [S.iterations, S.iterations + sim3_window(J, S))
 __device__ __forceinline__ int sim3_window(const orbx_sim3_job& J, const orbx_sim3_state& S) {
-    const long long left = (long long)J.max_its - S.iterations;
-    const long long n = left < J.n_iterations ? left : (long long)J.n_iterations;
-    return n < 0 ? 0 : (int)n;
+    return ransac_window_and(J.max_its, S.iterations, J.n_iterations);
 }
 
 // What the job record alone shows; the same in all three kernels.
@@ -553,14 +549,8 @@ __global__ __launch_bounds__(64) void k_sim3_select(const Sim3Launch g) {
 #pragma unroll
             for (int k = 0; k < 9; ++k) res.R12[k] = H.R[k];
 #pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                res.t12[r] = H.t[r];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) res.T12[4 * r + c] = H.sR[3 * r + c];
-                res.T12[4 * r + 3] = H.t[r];
-                res.T12[12 + r] = 0.0f;
-            }
-            res.T12[15] = 1.0f;
+            for (int r = 0; r < 3; ++r) res.t12[r] = H.t[r];
+            rt_to_4x4(H.sR, H.t, res.T12);
             res.s12 = H.s;
         }
         g.state[j].iterations = its;
@@ -578,14 +568,8 @@ __global__ __launch_bounds__(64) void k_sim3_select(const Sim3Launch g) {
         if (is_inlier(prep[i], H, K1, K2)) inl[prep[i].i1] = 1;   // :195-197
 }
 
-}  // namespace
-
-namespace orbx {
-
 size_t sim3_scratch_bytes(int njobs, int max_n, int max_call) {
-    // the three blocks of scratch_of
-    return al256(4 * (size_t)njobs) + al256(sizeof(Sim3Prep) * (size_t)njobs * (size_t)max_n) +
-           al256(sizeof(Sim3Hyp) * (size_t)njobs * (size_t)max_call);
+    return scratch_of(nullptr, njobs, max_n, max_call).end;
 }
 
 hipError_t launch_sim3(const Sim3Launch& a, hipStream_t st) {
@@ -599,50 +583,25 @@ hipError_t launch_sim3(const Sim3Launch& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-}  // namespace orbx
+// What a launch may ask for, for the host-array and the batch entry alike.  its: the most
+// iterations of a job (its max_its) or of the call.
+bool sim3_within_limits(int njobs, int max_n, int its) {
+    return njobs <= SIM3_MAX_JOBS && max_n <= SIM3_MAX_N && its <= SIM3_MAX_ITS &&
+           sim3_scratch_bytes(njobs, max_n, its) <= SIM3_MAX_SCRATCH;
+}
+
+}  // namespace
 
 extern "C" {
 
 int32_t orbx_sim3_ransac_iterations(double prob, int32_t min_inliers, int32_t max_its, int32_t N) {
     const float epsilon = (float)min_inliers / N;
-    int nIterations;
-    if (min_inliers == N) {
-        nIterations = 1;
-    } else {
-        nIterations = cvtt(::ceil(::log(1 - prob) / ::log(1 - ::pow((double)epsilon, 3.0))));
-    }
-    const int lo = nIterations < max_its ? nIterations : max_its;
-    return lo > 1 ? lo : 1;
+    return ransac_iterations(prob, epsilon, min_inliers == N, max_its);
 }
 
 orbx_status orbx_sim3_sample_triples(int32_t N, int32_t n_its, const int32_t* rand_values,
                                      int32_t* triples) {
-    if (N < 3 || n_its < 0 || (n_its > 0 && (!rand_values || !triples))) return ORBX_ERR_INVALID;
-    for (int64_t k = 0; k < 3 * (int64_t)n_its; ++k)
-        if (rand_values[k] < 0) return ORBX_ERR_INVALID;   // RAND_MAX is INT_MAX
-    // vAvailableIndices starts as 0 .. N-1 in every iteration, so the three swap-with-last steps
-    // touch at most three positions: pos[] / val[] hold the positions overwritten so far
-    for (int32_t it = 0; it < n_its; ++it) {
-        int32_t pos[3], val[3];
-        int nmod = 0;
-        int32_t size = N;
-        for (int i = 0; i < 3; ++i) {
-            const int randi =
-                (int)(((double)rand_values[3 * (size_t)it + i] / ((double)RAND_MAX + 1.0)) * size);
-            auto at = [&](int32_t p) {
-                int32_t v = p;
-                for (int m = 0; m < nmod; ++m)
-                    if (pos[m] == p) v = val[m];
-                return v;
-            };
-            triples[3 * (size_t)it + i] = at(randi);
-            pos[nmod] = randi;
-            val[nmod] = at(size - 1);
-            ++nmod;
-            --size;
-        }
-    }
-    return ORBX_OK;
+    return sample_minimal_sets<3>(N, n_its, rand_values, triples);
 }
 
 orbx_status orbx_sim3_limits(int32_t* max_n, int32_t* max_its, int32_t* max_jobs,
@@ -662,12 +621,13 @@ orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pos
     if (job->N < 0 || job->mN1 < 0 || job->n_iterations < 0 || job->max_its < 1 ||
         (job->N > 0 && !corr) || (job->mN1 > 0 && !inliers))
         return ORBX_ERR_INVALID;
-    if (job->N > SIM3_MAX_N || job->max_its > SIM3_MAX_ITS) return ORBX_ERR_UNSUPPORTED;
+    if (!sim3_within_limits(1, job->N, job->max_its)) return ORBX_ERR_UNSUPPORTED;
     HostCall c(device);
     if (!c.ok()) return ORBX_ERR_DEVICE;
     StagePlan& p = c.plan();
     const int N = job->N, mN1 = job->mN1, max_its = job->max_its;
-    const int max_call = job->n_iterations < max_its ? job->n_iterations : max_its;
+    // a fresh solver's window: no later call of the same solver runs more
+    const int max_call = ransac_window_and(max_its, 0, job->n_iterations);
     const orbx_frame_pose poses[2] = {*pose1, *pose2};
     orbx_sim3_job hj = *job;
     hj.kf1 = 0, hj.kf2 = 1, hj.corr_off = 0, hj.inlier_off = 0, hj.triple_off = 0;
@@ -694,6 +654,40 @@ orbx_status orbx_sim3_iterate(const orbx_frame_pose* pose1, const orbx_frame_pos
     L.ninliers = mN1;
     L.scratch = c.dev<uint8_t>(p_scratch);
     return c.finish(HIPOK(launch_sim3(L, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
+}
+
+orbx_status orbx_sim3_iterate_batch_device(
+    orbx_matcher* m, const orbx_sim3_job* d_jobs, int32_t njobs, int32_t max_n,
+    int32_t max_call_its, const orbx_frame_pose* d_poses, int32_t nposes,
+    const orbx_sim3_corr* d_corr, int64_t ncorr, const int32_t* d_triples, int64_t ntriples,
+    orbx_sim3_state* d_state, orbx_sim3_result* d_results, uint8_t* d_inliers,
+    int64_t ninlier_bytes, void* stream) {
+    if (!m || njobs < 0 || max_n < 0 || max_call_its < 0 || nposes < 0 || ncorr < 0 ||
+        ntriples < 0 || ninlier_bytes < 0)
+        return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_jobs || !d_poses || !d_triples || !d_state || !d_results || (ncorr > 0 && !d_corr) ||
+        (ninlier_bytes > 0 && !d_inliers))
+        return ORBX_ERR_INVALID;
+    if (!sim3_within_limits(njobs, max_n, max_call_its)) return ORBX_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
+    if (!m->d_sim3.ensure(sim3_scratch_bytes(njobs, max_n, max_call_its))) return ORBX_ERR_DEVICE;
+    Sim3Launch L{};
+    L.jobs = d_jobs;
+    L.njobs = njobs, L.max_n = max_n, L.max_call = max_call_its;
+    L.poses = d_poses;
+    L.nposes = nposes;
+    L.corr = d_corr;
+    L.ncorr = ncorr;
+    L.triples = d_triples;
+    L.ntriples = ntriples;
+    L.state = d_state;
+    L.res = d_results;
+    L.inliers = d_inliers;
+    L.ninliers = ninlier_bytes;
+    L.scratch = m->d_sim3.p;
+    return HIPOK(launch_sim3(L, (hipStream_t)stream)) ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@
 #include "orbx_host.h"
 #include "orbx_lm.h"
 #include "orbx_match_kernels.h"
+#include "orbx_matcher.h"
 #include "orbx_math.h"
 
 using namespace orbx;
@@ -560,17 +561,13 @@ __global__ __launch_bounds__(64 * SO_WAVES) void k_sim3_opt(const Sim3OptLaunch 
     finish(est, N - nbad - nfail, N, nbad, word());
 }
 
-}  // namespace
-
-namespace orbx {
-
 hipError_t launch_sim3_opt(const Sim3OptLaunch& a, hipStream_t st) {
     hipLaunchKernelGGL(k_sim3_opt, dim3((a.njobs + SO_WAVES - 1) / SO_WAVES), dim3(64 * SO_WAVES),
                        0, st, a);
     return hipGetLastError();
 }
 
-}  // namespace orbx
+}  // namespace
 
 extern "C" {
 
@@ -613,6 +610,36 @@ orbx_status orbx_sim3_optimize(const orbx_frame_pose* pose1, const orbx_frame_po
     L.keep = c.dev<uint8_t>(p_keep);
     L.nkeep = mN1;
     return c.finish(HIPOK(launch_sim3_opt(L, c.st())) ? ORBX_OK : ORBX_ERR_DEVICE);
+}
+
+orbx_status orbx_sim3_optimize_batch_device(
+    orbx_matcher* m, const orbx_sim3opt_job* d_jobs, int32_t njobs, int32_t max_n,
+    const orbx_frame_pose* d_poses, int32_t nposes, const orbx_sim3opt_corr* d_corr, int64_t ncorr,
+    const void* d_sim3_in, int64_t sim3_in_stride, orbx_sim3opt_result* d_results,
+    uint8_t* d_keep, int64_t nkeep_bytes, void* stream) {
+    if (!m || njobs < 0 || max_n < 0 || nposes < 0 || ncorr < 0 || nkeep_bytes < 0)
+        return ORBX_ERR_INVALID;
+    if (njobs == 0) return ORBX_OK;
+    if (!d_jobs || !d_poses || !d_sim3_in || !d_results || (ncorr > 0 && !d_corr) ||
+        (nkeep_bytes > 0 && !d_keep) || sim3_in_stride < (int64_t)sizeof(orbx_sim3opt_in) ||
+        (sim3_in_stride & 3) || ((uintptr_t)d_sim3_in & 3))
+        return ORBX_ERR_INVALID;
+    if (njobs > SIM3OPT_MAX_JOBS || max_n > SIM3OPT_MAX_N) return ORBX_ERR_UNSUPPORTED;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!HIPOK(hipSetDevice(m->prm.device))) return ORBX_ERR_DEVICE;
+    Sim3OptLaunch L{};
+    L.jobs = d_jobs;
+    L.njobs = njobs, L.max_n = max_n;
+    L.poses = d_poses;
+    L.nposes = nposes;
+    L.corr = d_corr;
+    L.ncorr = ncorr;
+    L.sim3_in = (const uint8_t*)d_sim3_in;
+    L.in_stride = sim3_in_stride;
+    L.res = d_results;
+    L.keep = d_keep;
+    L.nkeep = nkeep_bytes;
+    return HIPOK(launch_sim3_opt(L, (hipStream_t)stream)) ? ORBX_OK : ORBX_ERR_DEVICE;
 }
 
 }  // extern "C"

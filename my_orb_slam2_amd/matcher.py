@@ -138,6 +138,11 @@ def _u8(mask, n):
     return m
 
 
+def _nbytes(t) -> int:
+    """The bytes of a device tensor (None: 0), for the array lengths of the *_batch_device forms."""
+    return 0 if t is None else int(t.numel() * t.element_size())
+
+
 def _queries(q) -> np.ndarray:
     q = np.ascontiguousarray(q)
     if q.dtype != PROJ_QUERY_DTYPE:
@@ -430,15 +435,13 @@ class ORBmatcher:
         from .features import FRAME_POSE_DTYPE
         from .sim3 import SIM3_CORR_DTYPE
 
-        def nbytes(t):
-            return 0 if t is None else int(t.numel() * t.element_size())
         check("orbx_sim3_iterate_batch_device",
               self._lib.orbx_sim3_iterate_batch_device(
                   self._h, ptr(d_jobs), int(njobs), int(max_n), int(max_call_its), ptr(d_poses),
-                  nbytes(d_poses) // FRAME_POSE_DTYPE.itemsize, ptr(d_corr),
-                  nbytes(d_corr) // SIM3_CORR_DTYPE.itemsize, ptr(d_triples),
-                  nbytes(d_triples) // 12, ptr(d_state), ptr(d_results), ptr(d_inliers),
-                  nbytes(d_inliers), ctypes.c_void_p(stream)))
+                  _nbytes(d_poses) // FRAME_POSE_DTYPE.itemsize, ptr(d_corr),
+                  _nbytes(d_corr) // SIM3_CORR_DTYPE.itemsize, ptr(d_triples),
+                  _nbytes(d_triples) // 12, ptr(d_state), ptr(d_results), ptr(d_inliers),
+                  _nbytes(d_inliers), ctypes.c_void_p(stream)))
 
     # ---- Optimizer::OptimizeSim3 for many candidates (Optimizer.cc:1070-1265) -----------------
     def sim3_optimize_batch_device(self, d_jobs, njobs: int, max_n: int, d_poses, d_corr,
@@ -455,12 +458,11 @@ class ORBmatcher:
         from .features import FRAME_POSE_DTYPE
         from .sim3 import SIM3OPT_CORR_DTYPE, SIM3OPT_IN_DTYPE
 
-        def nbytes(t):
-            return 0 if t is None else int(t.numel() * t.element_size())
         stride = SIM3OPT_IN_DTYPE.itemsize if sim3_in_stride is None else int(sim3_in_stride)
         if njobs > 0 and d_sim3_in is not None and (
                 sim3_in_offset < 0 or stride < SIM3OPT_IN_DTYPE.itemsize or
-                sim3_in_offset + (njobs - 1) * stride + SIM3OPT_IN_DTYPE.itemsize > nbytes(d_sim3_in)):
+                sim3_in_offset + (njobs - 1) * stride + SIM3OPT_IN_DTYPE.itemsize >
+                _nbytes(d_sim3_in)):
             raise ValueError("d_sim3_in is too short for njobs records of this stride and offset")
         p_in = ptr(d_sim3_in)
         if p_in is not None and sim3_in_offset:
@@ -468,9 +470,9 @@ class ORBmatcher:
         check("orbx_sim3_optimize_batch_device",
               self._lib.orbx_sim3_optimize_batch_device(
                   self._h, ptr(d_jobs), int(njobs), int(max_n), ptr(d_poses),
-                  nbytes(d_poses) // FRAME_POSE_DTYPE.itemsize, ptr(d_corr),
-                  nbytes(d_corr) // SIM3OPT_CORR_DTYPE.itemsize, p_in, stride, ptr(d_results),
-                  ptr(d_keep), nbytes(d_keep), ctypes.c_void_p(stream)))
+                  _nbytes(d_poses) // FRAME_POSE_DTYPE.itemsize, ptr(d_corr),
+                  _nbytes(d_corr) // SIM3OPT_CORR_DTYPE.itemsize, p_in, stride, ptr(d_results),
+                  ptr(d_keep), _nbytes(d_keep), ctypes.c_void_p(stream)))
 
     # ---- PnPsolver::iterate for many solvers (PnPsolver.cc:165-258) ----------------------------
     def pnp_iterate_batch_device(self, d_jobs, njobs: int, max_n: int, max_call_its: int, d_corr,
@@ -482,14 +484,12 @@ class ORBmatcher:
         points outside them is refused in its info word."""
         from .pnp import PNP_CORR_DTYPE
 
-        def nbytes(t):
-            return 0 if t is None else int(t.numel() * t.element_size())
         check("orbx_pnp_iterate_batch_device",
               self._lib.orbx_pnp_iterate_batch_device(
                   self._h, ptr(d_jobs), int(njobs), int(max_n), int(max_call_its), ptr(d_corr),
-                  nbytes(d_corr) // PNP_CORR_DTYPE.itemsize, ptr(d_quads), nbytes(d_quads) // 16,
-                  ptr(d_state), ptr(d_best), nbytes(d_best), ptr(d_results), ptr(d_inliers),
-                  nbytes(d_inliers), ctypes.c_void_p(stream)))
+                  _nbytes(d_corr) // PNP_CORR_DTYPE.itemsize, ptr(d_quads), _nbytes(d_quads) // 16,
+                  ptr(d_state), ptr(d_best), _nbytes(d_best), ptr(d_results), ptr(d_inliers),
+                  _nbytes(d_inliers), ctypes.c_void_p(stream)))
 
     def pnp_correspondences_batch_device(self, njobs: int, d_match, match_stride: int, d_keys_un,
                                          n_feat: int, d_mps, d_mp_off, d_corr, corr_stride: int,
@@ -510,12 +510,10 @@ class ORBmatcher:
         (the template's camera half, Rcw / tcw / Ow from the result's Tcw) and the MapPoint of
         every feature (the match where the solver kept it, else -1), as PoseOptimization reads
         them; a job without a pose gets the template and -1."""
-        def nbytes(t):
-            return 0 if t is None else int(t.numel() * t.element_size())
         check("orbx_pnp_apply_batch_device",
               self._lib.orbx_pnp_apply_batch_device(
                   self._h, int(njobs), ptr(d_jobs), ptr(d_results), ptr(d_inliers),
-                  nbytes(d_inliers), ptr(d_match), int(match_stride), int(n_feat),
+                  _nbytes(d_inliers), ptr(d_match), int(match_stride), int(n_feat),
                   ptr(d_template), ptr(d_poses), ptr(d_mp_of_feat), int(feat_stride),
                   ctypes.c_void_p(stream)))
 

@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check, load, ptr
+from ._lib import RAND_MAX, _sample_minimal_sets, _solver_limits, check, load, ptr
 
 PNP_CORR_DTYPE = np.dtype([("i", "<i4"), ("X", "<f4", 3), ("u", "<f4"), ("v", "<f4"),
                            ("octave", "<i4")])
@@ -39,8 +39,6 @@ PNP_REFUSED_ANY = 0x1f << 24
 PNP_QR_SINGULAR = 1 << 29
 PNP_SVD_COMPLETED = 1 << 30
 
-RAND_MAX = 2147483647
-
 
 def pnp_ransac_parameters(prob: float, min_inliers: int, max_its: int, min_set: int,
                           epsilon: float, N: int) -> tuple[int, int]:
@@ -57,22 +55,12 @@ def pnp_ransac_parameters(prob: float, min_inliers: int, max_its: int, min_set: 
 def pnp_sample_quads(N: int, rand_values) -> np.ndarray:
     """The minimal sets (:188-201) of len(rand_values) / 4 iterations from raw rand() values, as
     an (n_its, 4) int32 array; host only."""
-    r = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
-    if r.size % 4:
-        raise ValueError("four rand() values per iteration")
-    out = np.zeros((r.size // 4, 4), np.int32)
-    check("orbx_pnp_sample_quads",
-          load().orbx_pnp_sample_quads(int(N), r.size // 4, ptr(r), ptr(out)))
-    return out
+    return _sample_minimal_sets("orbx_pnp_sample_quads", 4, "four", N, rand_values)
 
 
 def pnp_limits() -> dict:
     """The largest N, max_its / iterations per call and jobs per call, and the scratch bound."""
-    a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    d = ctypes.c_int64()
-    check("orbx_pnp_limits", load().orbx_pnp_limits(ctypes.byref(a), ctypes.byref(b),
-                                                    ctypes.byref(c), ctypes.byref(d)))
-    return dict(max_n=a.value, max_its=b.value, max_jobs=c.value, max_scratch_bytes=d.value)
+    return _solver_limits("orbx_pnp_limits")
 
 
 def pnp_window(max_its: int, iterations: int, n_iterations: int) -> int:

@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check, load, ptr
+from ._lib import RAND_MAX, _sample_minimal_sets, _solver_limits, check, load, ptr
 from .features import FRAME_POSE_DTYPE
 
 SIM3_CORR_DTYPE = np.dtype([("i1", "<i4"), ("X1w", "<f4", 3), ("X2w", "<f4", 3),
@@ -37,8 +37,6 @@ SIM3_REFUSED_LIMIT = 1 << 27
 SIM3_REFUSED_RANGE = 1 << 28
 SIM3_REFUSED_ANY = 0x1f << 24
 
-RAND_MAX = 2147483647
-
 
 def sim3_ransac_iterations(prob: float, min_inliers: int, max_its: int, N: int) -> int:
     """mRansacMaxIts after SetRansacParameters (Sim3Solver.cc:114-138); host only."""
@@ -49,22 +47,12 @@ def sim3_ransac_iterations(prob: float, min_inliers: int, max_its: int, N: int) 
 def sim3_sample_triples(N: int, rand_values) -> np.ndarray:
     """The minimal sets (:163-177) of len(rand_values) / 3 iterations from raw rand() values, as
     an (n_its, 3) int32 array; host only."""
-    r = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
-    if r.size % 3:
-        raise ValueError("three rand() values per iteration")
-    out = np.zeros((r.size // 3, 3), np.int32)
-    check("orbx_sim3_sample_triples",
-          load().orbx_sim3_sample_triples(int(N), r.size // 3, ptr(r), ptr(out)))
-    return out
+    return _sample_minimal_sets("orbx_sim3_sample_triples", 3, "three", N, rand_values)
 
 
 def sim3_limits() -> dict:
     """The largest N, max_its / iterations per call and jobs per call, and the scratch bound."""
-    a, b, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-    d = ctypes.c_int64()
-    check("orbx_sim3_limits", load().orbx_sim3_limits(ctypes.byref(a), ctypes.byref(b),
-                                                      ctypes.byref(c), ctypes.byref(d)))
-    return dict(max_n=a.value, max_its=b.value, max_jobs=c.value, max_scratch_bytes=d.value)
+    return _solver_limits("orbx_sim3_limits")
 
 
 def sim3_job(sigma2_1, sigma2_2, mN1: int, N: int, fix_scale: bool, min_inliers: int,
