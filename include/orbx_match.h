@@ -462,9 +462,10 @@ orbx_status orbx_compute_distinctive_descriptors_device(orbx_matcher* m, const u
  * first / second featureset (nq unused); ORBX_VK_INIT with n_a / n_b = the feature counts of
  * F1 / F2; ORBX_VK_PROJ + an orbx_proj_mode with n_b = the target's feature count and nq the
  * query count (n_a unused).  Returns 0 for the on-chip variant (SearchByBoW: the second set's
- * descriptors staged in LDS; claim-mode projections: an owner word per target feature in the
- * greedy replay; also every kind that has a single variant), 1 for the fallback (descriptors
- * read from global memory; one query per replay round), or the ORBX_ERR_INVALID /
+ * descriptors staged in LDS; claim-mode projections: an owner word per target feature in
+ * k_proj_claim; also every kind that has a single variant, such as ORBX_VK_INIT's k_proj_init), 1
+ * for the fallback (descriptors read from global memory; one query per replay round), or the
+ * ORBX_ERR_INVALID /
  * ORBX_ERR_UNSUPPORTED the entry point itself returns for these sizes. */
 enum { ORBX_VK_BOW_KF_FRAME = 0, ORBX_VK_BOW_KF_KF = 1, ORBX_VK_INIT = 2, ORBX_VK_PROJ = 16 };
 int32_t orbx_matcher_variant(int32_t kind, int32_t n_a, int32_t n_b, int32_t nq);
@@ -819,7 +820,9 @@ orbx_status orbx_pnp_iterate(const orbx_pnp_job* job, const orbx_pnp_corr* corr,
  * tie the solver to the searches around it, are declared in orbx_frame.h next to the records
  * they read and write. */
 
-/* ---- per-kernel timing for the matcher handle ------------------------------------------ */
+/* ---- per-kernel timing for the matcher handle ------------------------------------------
+ * ORBX_MK_PROJ_RESOLVE ("k_proj_resolve") times the replay after k_proj_search, k_proj_claim or
+ * k_proj_init. */
 typedef enum {
     ORBX_MK_BOW = 0, ORBX_MK_TRIANGULATE, ORBX_MK_PROJ_SEARCH, ORBX_MK_PROJ_RESOLVE,
     ORBX_MK_DISTINCTIVE, ORBX_MK_BF, ORBX_MK_COUNT

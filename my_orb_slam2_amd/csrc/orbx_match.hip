@@ -10,13 +10,14 @@
 //   k_triangulate    one workgroup per keyframe pair, one wave per KF1 node; every idx1 is
 //                    independent (vbMatched2 is never set, :722), so each is a wave-min over
 //                    (distance, reversed position) keys = the reference's last-wins ties.
-//   k_proj_search    one wave per projected MapPoint: the grid window is a set of contiguous
-//                    CSR spans (one per grid column), scanned 64 candidates at a time; yields
-//                    the static top-2 (or the final answer for the claim-free modes).
-//   k_proj_resolve   one wave replays the greedy claims in MapPoint order; a query whose
-//                    static best/second are still unclaimed is decided from them (exact:
-//                    the dynamic candidate set is a subset), otherwise the wave re-scans
-//                    its window against the claim state in LDS.
+//   k_proj_search    one 16-lane DPP row per projected MapPoint scans the grid window, a set of
+//                    contiguous CSR spans (one per grid column); yields the PROJ_K best (claim
+//                    modes), the static top-2 (SearchForInitialization) or the final answer.
+//   k_proj_claim     one wave replays the greedy claims in MapPoint order, 64 queries a batch:
+//                    each round, the queries whose best two free candidates no earlier pending
+//                    one claims decide together; a list that ran out re-scans its window.
+//   k_proj_init      one wave walks SearchForInitialization's F1 features in order; a query whose
+//                    static top-2 still pass the matched distances in LDS is decided from them.
 //   k_proj_finish    rotation-consistency filter (ComputeThreeMaxima) and count.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -518,20 +519,21 @@ struct ModeInfo {
     bool kf_level;     // octave in [pred-1, pred] (matcher-side)
     bool fuse;         // reprojection chi2 test (:968-992)
     bool rot;          // rotation-consistency filter
-    bool greedy;       // sequential claims
+    ProjReplay replay; // the sequential kernel after the search
     int th;            // acceptance threshold on the best distance
 };
 
-__device__ __forceinline__ ModeInfo mode_info(int mode, int orb_dist) {
+__host__ __device__ __forceinline__ ModeInfo mode_info(int mode, int orb_dist) {
     switch (mode) {
-        case ORBX_PROJ_FRAME_MAPPOINTS: return {true, true, true, false, false, false, true, TH_HIGH};
-        case ORBX_PROJ_KF_SCW:          return {false, true, false, true, false, false, true, TH_LOW};
-        case ORBX_PROJ_LAST_FRAME:      return {true, true, true, false, false, true, true, TH_HIGH};
-        case ORBX_PROJ_KEYFRAME:        return {true, true, false, false, false, true, true, orb_dist};
-        case ORBX_PROJ_FUSE:            return {false, true, false, true, true, false, false, TH_LOW};
-        case ORBX_PROJ_FUSE_SCW:        return {false, false, false, true, false, false, false, TH_LOW};
-        case ORBX_PROJ_SIM3:            return {false, false, false, true, false, false, false, TH_HIGH};
-        default:                        return {true, false, false, false, false, true, true, TH_LOW};
+        case ORBX_PROJ_FRAME_MAPPOINTS: return {true, true, true, false, false, false, REPLAY_CLAIM, TH_HIGH};
+        case ORBX_PROJ_KF_SCW:          return {false, true, false, true, false, false, REPLAY_CLAIM, TH_LOW};
+        case ORBX_PROJ_LAST_FRAME:      return {true, true, true, false, false, true, REPLAY_CLAIM, TH_HIGH};
+        case ORBX_PROJ_KEYFRAME:        return {true, true, false, false, false, true, REPLAY_CLAIM, orb_dist};
+        case ORBX_PROJ_FUSE:            return {false, true, false, true, true, false, REPLAY_NONE, TH_LOW};
+        case ORBX_PROJ_FUSE_SCW:        return {false, false, false, true, false, false, REPLAY_NONE, TH_LOW};
+        case ORBX_PROJ_SIM3:            return {false, false, false, true, false, false, REPLAY_NONE, TH_HIGH};
+        case PROJ_INIT:   // (and no other: the entry points refuse what is not a mode)
+        default:                        return {true, false, false, false, false, true, REPLAY_INIT, TH_LOW};
     }
 }
 
@@ -733,6 +735,9 @@ __device__ __forceinline__ Cand decode_key(const orbx_featureset& T, const ModeI
 __device__ __forceinline__ int pack_cand(const Cand& c) {
     return c.d | (c.lvl & 0xF) << 9 | c.bin << 13;
 }
+__device__ __forceinline__ Cand unpack_cand(int i, int w) {
+    return {i, w & 0x1FF, (w >> 9) & 0xF, (w >> 13) & 0x1F};
+}
 
 __global__ __launch_bounds__(256) void k_proj_search(ProjLaunch g) {
     // one 16-lane group (a DPP row) per query, 16 queries per block
@@ -740,11 +745,12 @@ __global__ __launch_bounds__(256) void k_proj_search(ProjLaunch g) {
     const int qi = blockIdx.x * (256 / G) + (threadIdx.x / G), lane = lane_id() & (G - 1);
     if (qi >= g.nq) return;
     const ModeInfo mi = mode_info(g.mode, g.orb_dist);
+    const bool for_claim = mi.replay == REPLAY_CLAIM, for_init = mi.replay == REPLAY_INIT;
     const orbx_proj_query q = g.q[qi];
     if (!(q.radius >= 0)) {
         if (lane == 0) {
-            if (mi.greedy && g.mode != PROJ_INIT) g.ncand[qi] = 0;
-            else if (mi.greedy) g.top2[qi] = make_int4(-1, -1, 0, 0);
+            if (for_claim) g.ncand[qi] = 0;
+            else if (for_init) g.top2[qi] = make_int4(-1, -1, 0, 0);
             else g.out[qi] = -1;
         }
         return;
@@ -752,9 +758,8 @@ __global__ __launch_bounds__(256) void k_proj_search(ProjLaunch g) {
     const Desc qd = load_desc(g.qdesc, qi);
     const int job = job_of_query(g, qi);
     const orbx_featureset T = job_target(g, job);
-    uint32_t m1, m2;
-    if (mi.greedy && g.mode != PROJ_INIT) {
-        // claim modes: the PROJ_K best candidates, sorted, for the replay.  Features claimed
+    if (for_claim) {
+        // k_proj_claim's input: the PROJ_K best candidates, sorted.  Features claimed
         // before the call are out for every query and are filtered here.
         uint32_t mine;
         int count;
@@ -771,56 +776,65 @@ __global__ __launch_bounds__(256) void k_proj_search(ProjLaunch g) {
         if (lane == 0) g.ncand[qi] = more ? PROJ_K + 1 : count;
         return;
     }
+    uint32_t m1, m2;
     window_top2<G>(g, T, mi, q, qd, NoDyn{}, m1, m2);
     if (lane != 0) return;
-    if (mi.greedy) {
+    if (for_init) {                   // k_proj_init's input: the static best and second
         const Cand c1 = decode_key(T, mi, m1, q.angle), c2 = decode_key(T, mi, m2, q.angle);
         g.top2[qi] = make_int4(c1.i, c2.i, pack_cand(c1), pack_cand(c2));
-    } else {
+    } else {                          // no replay: the answer
         g.out[qi] = (m1 != INF && (int)(m1 >> 23) <= mi.th) ? T.grid_feat[m1 & POS_MASK] : -1;
     }
 }
 
-// Claim-mode replays keep an owner word per target feature when it fits in the LDS.
-__host__ __device__ inline bool proj_resolve_parallel(int max_t) {
-    return 4 * 32 + 5 * (size_t)max_t + 16 <= MATCH_MAX_LDS;
+// The accept rule of the claim modes on the best and second free candidates (absent: i < 0).
+__device__ __forceinline__ bool proj_accept(int mode, const Cand& b, const Cand& c, float ratio, int th) {
+    if (mode == ORBX_PROJ_FRAME_MAPPOINTS) {   // :121-124
+        const int bestDist = b.i >= 0 ? b.d : 256, bestLevel = b.i >= 0 ? b.lvl : -1;
+        const int bestDist2 = c.i >= 0 ? c.d : 256, bestLevel2 = c.i >= 0 ? c.lvl : -1;
+        return bestDist <= TH_HIGH &&
+               !(bestLevel == bestLevel2 && (float)bestDist > ratio * (float)bestDist2);
+    }
+    return b.i >= 0 && b.d <= th;
 }
 
-// Greedy replay in MapPoint order (one wave per job).
-__global__ __launch_bounds__(64) void k_proj_resolve(ProjLaunch g) {
+// SearchForInitialization's (:500-502).
+__device__ __forceinline__ bool init_accept(const Cand& b, const Cand& c, float ratio) {
+    const int bestDist = b.i >= 0 ? b.d : INT_MAX, bestDist2 = c.i >= 0 ? c.d : INT_MAX;
+    return bestDist <= TH_LOW && (float)bestDist < (float)bestDist2 * ratio;
+}
+
+// Both replay kernels: a job whose target outgrew the LDS sized for max_t is flagged, no matches.
+__device__ bool replay_refuses(const ProjLaunch& g, int job, int nT, int q0, int q1) {
+    if (nT <= g.max_t) return false;
+    const int lane = lane_id();
+    if (lane == 0) atomicOr(g.err, 1);
+    for (int i = q0 + lane; i < q1; i += 64) g.out[i] = -1;
+    if (lane < 32) g.hist[32 * job + lane] = 0;
+    return true;
+}
+
+// Greedy claim replay in MapPoint order (one wave per job).
+__global__ __launch_bounds__(64) void k_proj_claim(ProjLaunch g) {
     extern __shared__ int lds[];
     const int lane = lane_id(), job = blockIdx.x;
     const ModeInfo mi = mode_info(g.mode, g.orb_dist);
-    const bool init = g.mode == PROJ_INIT;
     const orbx_featureset T = job_target(g, job);
     const int q0 = job_first_query(g, job), q1 = job_end_query(g, job);
     const int nT = T.n, nq = q1 - q0;
     const uint8_t* claimed_in = g.claimed_in ? g.claimed_in + (g.t_off ? g.t_off[job] : 0) : nullptr;
-    if (nT > g.max_t) {   // the LDS was sized for max_t: flag the job, no matches
-        if (lane == 0) atomicOr(g.err, 1);
-        for (int i = q0 + lane; i < q1; i += 64) g.out[i] = -1;
-        if (lane < 32) g.hist[32 * job + lane] = 0;
-        return;
-    }
-    int* hist = lds;                         // 32
-    const bool par = proj_resolve_parallel(g.max_t);
-    int* owner = lds + 32;                   // nT (claim modes, par): earliest acceptor lane
-    uint8_t* claimed = (uint8_t*)(lds + 32 + (par ? g.max_t : 0));   // nT (claim modes)
-    int* mdist = lds + 32;                   // nT (init): vMatchedDistance
-    int* m21 = mdist + nT;                   // nT (init): vnMatches21
-    int* m12 = m21 + nT;                     // nq (init): vnMatches12
+    if (replay_refuses(g, job, nT, q0, q1)) return;
+    const ClaimCarve carve(g.max_t);
+    int* hist = lds + carve.hist;                      // 32
+    int* owner = lds + carve.owner;                    // nT (owner_words): earliest acceptor lane
+    uint8_t* claimed = (uint8_t*)(lds + carve.claimed);   // nT
     if (lane < 32) hist[lane] = 0;
-    if (init) {
-        for (int i = lane; i < nT; i += 64) { mdist[i] = INT_MAX; m21[i] = -1; }
-        for (int i = lane; i < nq; i += 64) m12[i] = -1;
-    } else {
-        for (int i = lane; i < nT; i += 64) claimed[i] = claimed_in ? (claimed_in[i] != 0) : 0;
-        if (par)
-            for (int i = lane; i < nT; i += 64) owner[i] = 64;
-    }
+    for (int i = lane; i < nT; i += 64) claimed[i] = claimed_in ? (claimed_in[i] != 0) : 0;
+    if (carve.owner_words)
+        for (int i = lane; i < nT; i += 64) owner[i] = 64;
     __syncthreads();
-    for (int qb = 0; qb < nq && !init; qb += 64) {
-        // Claim modes, 64 queries at a time.  Lane t holds query t's list of its PROJ_K best
+    for (int qb = 0; qb < nq; qb += 64) {
+        // 64 queries at a time.  Lane t holds query t's list of its PROJ_K best
         // candidates (sorted by key, pre-claimed features already out).  Each round every
         // pending lane decides against the current claims; a lane whose best or second is
         // also accepted by an earlier pending lane (owner[] holds the earliest acceptor), or
@@ -848,33 +862,23 @@ __global__ __launch_bounds__(64) void k_proj_resolve(ProjLaunch g) {
                 L[2 * k + 1] = make_int2(v.z, v.w);
             }
         }
-        int res = -1, rbin = 0;
-        int start = 0;
+        int res = -1, rbin = 0, start = 0;
         while (start < cnt) {
             Cand b = {-1, 0, -1, 0}, c = {-1, 0, -1, 0};
             int nfree = 0;
 #pragma unroll
             for (int k = 0; k < PROJ_K; ++k) {
                 const bool fr = k < nv && claimed[max(L[k].x, 0)] == 0;
-                const Cand x = {L[k].x, L[k].y & 0x1FF, (L[k].y >> 9) & 0xF, (L[k].y >> 13) & 0x1F};
+                const Cand x = unpack_cand(L[k].x, L[k].y);
                 if (fr && nfree == 0) b = x;
                 else if (fr && nfree == 1) c = x;
                 nfree += fr;
             }
             const bool act = lane >= start && lane < cnt;
             const bool rescan = act && nfree < 2 && nc > PROJ_K;
-            bool acc;
-            if (g.mode == ORBX_PROJ_FRAME_MAPPOINTS) {   // :121-124
-                const int bestDist = b.i >= 0 ? b.d : 256, bestLevel = b.i >= 0 ? b.lvl : -1;
-                const int bestDist2 = c.i >= 0 ? c.d : 256, bestLevel2 = c.i >= 0 ? c.lvl : -1;
-                acc = bestDist <= TH_HIGH &&
-                      !(bestLevel == bestLevel2 && (float)bestDist > g.ratio * (float)bestDist2);
-            } else {
-                acc = b.i >= 0 && b.d <= mi.th;
-            }
-            acc = acc && act && !rescan;
+            const bool acc = proj_accept(g.mode, b, c, g.ratio, mi.th) && act && !rescan;
             int f = start + 1;
-            if (par) {
+            if (carve.owner_words) {
                 if (acc && claims) atomicMin(&owner[b.i], lane);
                 bool wait = rescan && lane > start;
                 if (act && lane > start) {
@@ -893,15 +897,7 @@ __global__ __launch_bounds__(64) void k_proj_resolve(ProjLaunch g) {
                 uint32_t m1, m2;
                 window_top2(g, T, mi, q, qd, ClaimDyn{claimed}, m1, m2);
                 const Cand rb = decode_key(T, mi, m1, q.angle), rc = decode_key(T, mi, m2, q.angle);
-                bool racc;
-                if (g.mode == ORBX_PROJ_FRAME_MAPPOINTS) {
-                    const int bestDist = rb.i >= 0 ? rb.d : 256, bestLevel = rb.i >= 0 ? rb.lvl : -1;
-                    const int bestDist2 = rc.i >= 0 ? rc.d : 256, bestLevel2 = rc.i >= 0 ? rc.lvl : -1;
-                    racc = bestDist <= TH_HIGH &&
-                           !(bestLevel == bestLevel2 && (float)bestDist > g.ratio * (float)bestDist2);
-                } else {
-                    racc = rb.i >= 0 && rb.d <= mi.th;
-                }
+                const bool racc = proj_accept(g.mode, rb, rc, g.ratio, mi.th);
                 if (lane == start) {
                     res = racc ? rb.i : -1;
                     if (racc) {
@@ -928,72 +924,60 @@ __global__ __launch_bounds__(64) void k_proj_resolve(ProjLaunch g) {
             if (res >= 0) g.out_bin[qi] = (int8_t)rbin;
         }
     }
-    for (int qb = 0; qb < nq && init; qb += 64) {
+    __syncthreads();
+    if (lane < 32) g.hist[32 * job + lane] = hist[lane];
+}
+
+// SearchForInitialization's loop over the F1 features in order (one wave per job): a query whose
+// static best and second still pass vMatchedDistance is decided from them (exact: the dynamic
+// candidate set is a subset), otherwise the wave re-scans its window against the state in LDS.
+__global__ __launch_bounds__(64) void k_proj_init(ProjLaunch g) {
+    extern __shared__ int lds[];
+    const int lane = lane_id(), job = blockIdx.x;
+    const ModeInfo mi = mode_info(PROJ_INIT, g.orb_dist);
+    const orbx_featureset T = job_target(g, job);
+    const int q0 = job_first_query(g, job), q1 = job_end_query(g, job);
+    const int nT = T.n, nq = q1 - q0;
+    if (replay_refuses(g, job, nT, q0, q1)) return;
+    const InitCarve carve(nT, nq);
+    int* hist = lds + carve.hist;     // 32
+    int* mdist = lds + carve.mdist;   // nT: vMatchedDistance
+    int* m21 = lds + carve.m21;       // nT: vnMatches21
+    int* m12 = lds + carve.m12;       // nq: vnMatches12
+    if (lane < 32) hist[lane] = 0;
+    for (int i = lane; i < nT; i += 64) { mdist[i] = INT_MAX; m21[i] = -1; }
+    for (int i = lane; i < nq; i += 64) m12[i] = -1;
+    __syncthreads();
+    for (int qb = 0; qb < nq; qb += 64) {
         const int cnt = min(64, nq - qb);
         const int4 s = (lane < cnt) ? g.top2[q0 + qb + lane] : make_int4(-1, -1, 0, 0);
         for (int t = 0; t < cnt; ++t) {
             const int qj = qb + t, qi = q0 + qj;   // job-local / global query index
-            Cand b = {__builtin_amdgcn_readlane(s.x, t), 0, -1, 0};
-            Cand c = {__builtin_amdgcn_readlane(s.y, t), 0, -1, 0};
-            const int w1 = __builtin_amdgcn_readlane(s.z, t), w2 = __builtin_amdgcn_readlane(s.w, t);
-            b.d = w1 & 0x1FF; b.lvl = (w1 >> 9) & 0xF; b.bin = (w1 >> 13) & 0x1F;
-            c.d = w2 & 0x1FF; c.lvl = (w2 >> 9) & 0xF; c.bin = (w2 >> 13) & 0x1F;
-            if (b.i < 0) {
-                if (lane == 0 && !init) g.out[qi] = -1;
-                continue;   // no static candidate: none under any claim state either
-            }
-            auto pass = [&](const Cand& x) {
-                return init ? (mdist[x.i] > x.d) : (claimed[x.i] == 0);
-            };
-            const bool fast = pass(b) && (c.i < 0 || pass(c));
-            if (!fast) {
+            Cand b = unpack_cand(__builtin_amdgcn_readlane(s.x, t), __builtin_amdgcn_readlane(s.z, t));
+            Cand c = unpack_cand(__builtin_amdgcn_readlane(s.y, t), __builtin_amdgcn_readlane(s.w, t));
+            if (b.i < 0) continue;   // no static candidate: none under any state either
+            if (!(mdist[b.i] > b.d && (c.i < 0 || mdist[c.i] > c.d))) {
                 // The static best or second is gone: re-scan the window against the state.
                 const orbx_proj_query q = g.q[qi];
                 const Desc qd = load_desc(g.qdesc, qi);
                 uint32_t m1, m2;
-                if (init) window_top2(g, T, mi, q, qd, InitDyn{mdist}, m1, m2);
-                else window_top2(g, T, mi, q, qd, ClaimDyn{claimed}, m1, m2);
+                window_top2(g, T, mi, q, qd, InitDyn{mdist}, m1, m2);
                 b = decode_key(T, mi, m1, q.angle);
                 c = decode_key(T, mi, m2, q.angle);
             }
-            bool acc;
-            if (g.mode == ORBX_PROJ_FRAME_MAPPOINTS) {   // :121-124
-                const int bestDist = b.i >= 0 ? b.d : 256, bestLevel = b.i >= 0 ? b.lvl : -1;
-                const int bestDist2 = c.i >= 0 ? c.d : 256, bestLevel2 = c.i >= 0 ? c.lvl : -1;
-                acc = bestDist <= TH_HIGH &&
-                      !(bestLevel == bestLevel2 && (float)bestDist > g.ratio * (float)bestDist2);
-            } else if (init) {                           // :500-502
-                const int bestDist = b.i >= 0 ? b.d : INT_MAX;
-                const int bestDist2 = c.i >= 0 ? c.d : INT_MAX;
-                acc = bestDist <= TH_LOW && (float)bestDist < (float)bestDist2 * g.ratio;
-            } else {
-                acc = b.i >= 0 && b.d <= mi.th;
-            }
-            if (lane == 0) {
-                if (init) {
-                    if (acc) {   // :504-512 (re-assignment)
-                        const int prev = m21[b.i];
-                        if (prev >= 0) m12[prev] = -1;
-                        m12[qj] = b.i;
-                        m21[b.i] = qj;
-                        mdist[b.i] = b.d;
-                        g.out_bin[qi] = (int8_t)b.bin;
-                        if (g.check_ori) hist[b.bin] += 1;
-                    }
-                } else {
-                    g.out[qi] = acc ? b.i : -1;
-                    if (acc) {
-                        claimed[b.i] = 1;
-                        g.out_bin[qi] = (int8_t)b.bin;
-                        if (mi.rot && g.check_ori) hist[b.bin] += 1;
-                    }
-                }
+            if (lane == 0 && init_accept(b, c, g.ratio)) {   // :504-512 (re-assignment)
+                const int prev = m21[b.i];
+                if (prev >= 0) m12[prev] = -1;
+                m12[qj] = b.i;
+                m21[b.i] = qj;
+                mdist[b.i] = b.d;
+                g.out_bin[qi] = (int8_t)b.bin;
+                if (g.check_ori) hist[b.bin] += 1;
             }
         }
     }
     __syncthreads();
-    if (init)
-        for (int i = lane; i < nq; i += 64) g.out[q0 + i] = m12[i];
+    for (int i = lane; i < nq; i += 64) g.out[q0 + i] = m12[i];
     if (lane < 32) g.hist[32 * job + lane] = hist[lane];
 }
 
@@ -1093,11 +1077,6 @@ size_t distinctive_lds_bytes() {
     return (size_t)ORBX_MAX_OBSERVATIONS * 32 + 64 * (ORBX_MAX_OBSERVATIONS + 1) * 2;
 }
 
-bool proj_mode_greedy(int mode) {
-    return mode == ORBX_PROJ_FRAME_MAPPOINTS || mode == ORBX_PROJ_KF_SCW ||
-           mode == ORBX_PROJ_LAST_FRAME || mode == ORBX_PROJ_KEYFRAME || mode == PROJ_INIT;
-}
-
 static size_t bow_lds_raw(const BowLaunch& a, bool blds) {
     const size_t am = (size_t)a.A.max_feat, bm = (size_t)a.B.max_feat;
     const size_t sm = a.kf_kf ? am : bm;
@@ -1161,11 +1140,11 @@ hipError_t launch_triangulate(const TriLaunch& a, hipStream_t st) {
     return hipGetLastError();
 }
 
-bool proj_resolve_owner_words(int max_t) { return proj_resolve_parallel(max_t); }
+ProjReplay proj_replay(int mode) { return mode_info(mode, 0).replay; }
 
-size_t proj_resolve_lds_bytes(int mode, int n_target, int nq) {
-    if (mode == PROJ_INIT) return 4 * (32 + 2 * (size_t)n_target + (size_t)nq);
-    return 4 * 32 + (proj_resolve_parallel(n_target) ? 5 : 1) * (size_t)n_target + 16;
+size_t proj_replay_lds_bytes(int mode, int max_t, int nq) {
+    const ProjReplay r = proj_replay(mode);
+    return r == REPLAY_CLAIM ? ClaimCarve(max_t).bytes : r == REPLAY_INIT ? InitCarve(max_t, nq).bytes : 0;
 }
 
 hipError_t launch_proj(const ProjLaunch& a, hipStream_t st, KernelTimer* timer) {
@@ -1175,11 +1154,11 @@ hipError_t launch_proj(const ProjLaunch& a, hipStream_t st, KernelTimer* timer) 
     if (timer) timer->stop(ORBX_MK_PROJ_SEARCH, e, st);
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return err;
-    if (proj_mode_greedy(a.mode)) {
+    if (const ProjReplay replay = proj_replay(a.mode)) {
         e = timer ? timer->start(st) : nullptr;
-        // LDS per job: the largest target, and (init) the largest query list = nq bound
-        hipLaunchKernelGGL(k_proj_resolve, dim3(a.njobs), dim3(64),
-                           proj_resolve_lds_bytes(a.mode, a.max_t, a.nq), st, a);
+        const size_t lds = proj_replay_lds_bytes(a.mode, a.max_t, a.nq);
+        if (replay == REPLAY_CLAIM) hipLaunchKernelGGL(k_proj_claim, dim3(a.njobs), dim3(64), lds, st, a);
+        else hipLaunchKernelGGL(k_proj_init, dim3(a.njobs), dim3(64), lds, st, a);
         if (timer) timer->stop(ORBX_MK_PROJ_RESOLVE, e, st);
         err = hipGetLastError();
         if (err != hipSuccess) return err;
@@ -1189,13 +1168,12 @@ hipError_t launch_proj(const ProjLaunch& a, hipStream_t st, KernelTimer* timer) 
 }
 
 hipError_t prepare_match_kernels() {
-    const int lds = (int)MATCH_MAX_LDS;
-    hipError_t e;
-    if ((e = hipFuncSetAttribute((const void*)k_bow<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_bow<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_triangulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRI_MAX_LDS)) != hipSuccess) return e;
-    if ((e = hipFuncSetAttribute((const void*)k_distinctive, hipFuncAttributeMaxDynamicSharedMemorySize, lds)) != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_proj_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    const void* full[] = {(const void*)k_bow<true>, (const void*)k_bow<false>, (const void*)k_distinctive,
+                          (const void*)k_proj_claim, (const void*)k_proj_init};
+    for (const void* k : full)
+        if (hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MATCH_MAX_LDS))
+            return e;
+    return hipFuncSetAttribute((const void*)k_triangulate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TRI_MAX_LDS);
 }
 
 }  // namespace orbx

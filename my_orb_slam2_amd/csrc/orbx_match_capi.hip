@@ -191,7 +191,7 @@ orbx_featureset dev_feat(const orbx_featureset* f, const FeatParts& o, uint8_t* 
 }
 
 // The capacity word of one host-array call: a part of its own, zeroed on the device too because
-// k_bow, k_triangulate, k_proj_resolve and k_distinctive only ever OR into it.  The handle's
+// k_bow, k_triangulate, k_proj_claim / k_proj_init and k_distinctive only ever OR into it.  The handle's
 // d_err belongs to the *_device forms alone.
 size_t err_part(StagePlan& P) { return P.out(nullptr, sizeof(int), /*zeroed=*/true); }
 
@@ -256,8 +256,9 @@ orbx_status run_tri(orbx_matcher* m, const orbx_kf_db& db, int njobs, const int3
 }
 
 // The scratch of one projection search over njobs targets and nq queries in all: offsets from a
-// 256-byte aligned base.  A kernel writes every region before one reads it (k_proj_search top2 /
-// cand / ncand; k_proj_resolve bins and hist, counted from zero in its LDS), so none is zeroed.
+// 256-byte aligned base.  A kernel writes every region before one reads it, so none is zeroed:
+// k_proj_search writes cand / ncand for k_proj_claim, top2 for k_proj_init; either replay writes
+// the bins of its matches and hist (counted from zero in its LDS) for k_proj_finish.
 struct ProjScratch {
     size_t hist, top2, bins, cand, ncand, end;
 };
@@ -311,8 +312,7 @@ orbx_status run_proj(orbx_matcher* m, int mode, const orbx_featureset& T, int nj
     L.hist = (int32_t*)(scratch + s.hist);
     L.nmatches = nmatches;
     L.err = err;
-    if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, L.max_t, nq) > MATCH_MAX_LDS)
-        return ORBX_ERR_UNSUPPORTED;
+    if (proj_replay_lds_bytes(mode, L.max_t, nq) > MATCH_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
     if (nq == 0)   // every job: no queries, no matches
         return HIPOK(hipMemsetAsync(nmatches, 0, 4 * (size_t)njobs, st)) ? ORBX_OK : ORBX_ERR_DEVICE;
     return HIPOK(launch_proj(L, st, &m->timer)) ? ORBX_OK : ORBX_ERR_DEVICE;
@@ -342,8 +342,7 @@ orbx_status bow_common(orbx_matcher* m, const orbx_featureset* a, const uint8_t*
 // apply them (valid_feat, proj_common, run_proj), for orbx_matcher_variant.
 orbx_status proj_size_status(int mode, int n_target, int nq) {
     if (nq < 0 || nq > (1 << 22) || n_target < 0 || n_target > MAX_FEAT) return ORBX_ERR_INVALID;
-    if (proj_mode_greedy(mode) && proj_resolve_lds_bytes(mode, n_target, nq) > MATCH_MAX_LDS)
-        return ORBX_ERR_UNSUPPORTED;
+    if (proj_replay_lds_bytes(mode, n_target, nq) > MATCH_MAX_LDS) return ORBX_ERR_UNSUPPORTED;
     return ORBX_OK;
 }
 
@@ -940,7 +939,7 @@ int32_t orbx_matcher_variant(int32_t kind, int32_t n_a, int32_t n_b, int32_t nq)
     if (mode < 0 || mode >= ORBX_PROJ_MODE_COUNT) return ORBX_ERR_INVALID;
     const orbx_status s = proj_size_status(mode, n_b, nq);
     if (s != ORBX_OK) return s;
-    return (!proj_mode_greedy(mode) || proj_resolve_owner_words(n_b)) ? 0 : 1;
+    return (proj_replay(mode) != REPLAY_CLAIM || ClaimCarve(n_b).owner_words) ? 0 : 1;
 }
 
 const char* orbx_match_kernel_name(int id) {

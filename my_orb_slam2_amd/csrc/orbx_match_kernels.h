@@ -143,7 +143,7 @@ struct ProjLaunch {
     const int32_t* t_off;
     const int32_t* g_off;
     const int32_t* q_off;
-    int max_t;                   // largest target (LDS sizing of the resolve phase)
+    int max_t;                   // largest target (LDS sizing of the replay kernels)
     const uint8_t* qdesc;
     const orbx_proj_query* q;
     int nq;
@@ -164,21 +164,23 @@ struct ProjLaunch {
     int* err;
 };
 
-bool proj_mode_greedy(int mode);
 hipError_t launch_bow(const BowLaunch& a, hipStream_t st);
 size_t bow_lds_bytes(const BowLaunch& a);
 // launch_bow's choice: k_bow<true> (B descriptors staged in LDS) or k_bow<false> (global reads)
 bool bow_b_in_lds(const BowLaunch& a);
 hipError_t launch_triangulate(const TriLaunch& a, hipStream_t st);
 size_t tri_lds_bytes(int max_feat);
-// Phase A (window search, static top-2), B (sequential greedy claims), C (rotation filter
-// and count).  launch_proj runs the phases the mode needs; `timer` ids ORBX_MK_*.
+// Phase A (k_proj_search: window search), B (the mode's sequential replay, if it has one), C
+// (k_proj_finish: rotation filter and count).  launch_proj runs the phases the mode needs;
+// `timer` ids ORBX_MK_*, both replay kernels under ORBX_MK_PROJ_RESOLVE.
 struct KernelTimer;
 hipError_t launch_proj(const ProjLaunch& a, hipStream_t st, KernelTimer* timer);
-size_t proj_resolve_lds_bytes(int mode, int n_target, int nq);
-// k_proj_resolve's choice for a largest target of max_t features: owner words (many queries
-// per round) or, when they do not fit in the LDS, one query per round
-bool proj_resolve_owner_words(int max_t);
+// The replay after k_proj_search in a mode: none (the search's answer is final), k_proj_claim
+// (greedy claims of target features) or k_proj_init (SearchForInitialization).
+enum ProjReplay { REPLAY_NONE, REPLAY_CLAIM, REPLAY_INIT };
+ProjReplay proj_replay(int mode);
+// Its dynamic LDS (0 without one); above MATCH_MAX_LDS the search is unsupported.
+size_t proj_replay_lds_bytes(int mode, int max_t, int nq);
 hipError_t prepare_match_kernels();
 // Brute-force Hamming top-2 (orbx_bf.hip): q nq x 32, db ndb x 32 (device); part = scratch of
 // bf_partial_bytes(ndb, nq, chunk) bytes.
@@ -210,7 +212,6 @@ struct BfGeometry {
 };
 BfGeometry bf_geometry(long long ndb, int nq, int chunk, int kernel);
 size_t bf_partial_bytes(long long ndb, int nq, int chunk);
-struct KernelTimer;
 hipError_t launch_bf_top2(const BfLaunch& a, hipStream_t st, KernelTimer* timer);
 const char* bf_kernel_name(int kernel);
 hipError_t launch_distinctive(const uint8_t* desc, const int32_t* off, int np, int32_t* best,
@@ -220,5 +221,26 @@ size_t distinctive_lds_bytes();
 constexpr size_t MATCH_MAX_LDS = 160 * 1024 - 256;
 // k_triangulate also holds 12 KiB of static LDS (one staged KF2 node slice per wave)
 constexpr size_t TRI_MAX_LDS = MATCH_MAX_LDS - 16 * 1024;
+
+// The dynamic LDS of the replay kernels in ints from its base, for their pointers and the host's
+// sizes.  k_proj_claim, for a largest target of max_t features: hist, an owner word per feature
+// while that fits (many queries per round; else one), a claimed byte per feature, 16 spare bytes.
+struct ClaimCarve {
+    bool owner_words;
+    int hist = 0, owner = 32, claimed;
+    size_t bytes;
+    __host__ __device__ explicit ClaimCarve(int max_t, bool ow = true) : owner_words(ow) {
+        claimed = owner + (ow ? max_t : 0);
+        bytes = 4 * (size_t)claimed + (size_t)max_t + 16;
+        if (ow && bytes > MATCH_MAX_LDS) *this = ClaimCarve(max_t, false);
+    }
+};
+// k_proj_init: hist, vMatchedDistance and vnMatches21 per F2 feature, vnMatches12 per F1 feature.
+struct InitCarve {
+    int hist = 0, mdist = 32, m21, m12;
+    size_t bytes;
+    __host__ __device__ InitCarve(int n_target, int nq)
+        : m21(mdist + n_target), m12(m21 + n_target), bytes(4 * ((size_t)m12 + (size_t)nq)) {}
+};
 
 }  // namespace orbx

@@ -343,6 +343,64 @@ def test_initialization_cases(oracle_mod, orbx_lib, gpu, order):
         np.testing.assert_array_equal(p_g.view(np.int32), p_o.view(np.int32), err_msg=c.name)
 
 
+INIT_LIMIT_SEED, INIT_LIMIT_WINDOW, INIT_LIMIT_PLANTS = 3, 30, 24
+
+
+def init_limit_case(n):
+    """(f1, f2, prev) with n features a side.  feature_pair gives every F2 feature at most one
+    near F1 descriptor, so nothing is ever re-assigned; the case plants later (and, for the
+    re-scan, earlier) exact copies of matched F2 descriptors into unmatched level-0 F1 features."""
+    f1, f2, truth = synth.feature_pair(INIT_LIMIT_SEED, n1=n, n2=n)
+    prev = np.ascontiguousarray(np.stack([f1.keys["x"], f1.keys["y"]], 1), np.float32)
+    lvl0 = f1.keys["octave"] == 0
+    free, held = np.nonzero(lvl0 & (truth < 0))[0], np.nonzero(lvl0 & (truth >= 0))[0]
+    for k in range(INIT_LIMIT_PLANTS):
+        i = held[len(held) // 4 + 7 * k]
+        side = free[free > i] if k % 3 else free[free < i]
+        i2, j = side[k], truth[i]
+        f1.desc[i2] = f2.desc[j]
+        prev[i2] = f2.keys["x"][j], f2.keys["y"][j]
+    return f1, f2, prev
+
+
+def test_initialization_at_lds_limit_between_claim_searches(oracle_mod, orbx_lib, gpu):
+    """k_proj_init at the largest size its LDS carve allows (above 64 KiB: the kernel's raised
+    dynamic-LDS limit is what lets it launch), between two k_proj_claim searches on the same
+    handle."""
+    import test_oracle_match as ref
+    from my_orb_slam2_amd.matcher import VK_INIT, matcher_variant
+    from oracle import matcher as om
+    n = mc.scan_regimes(matcher_variant, VK_INIT)["last_on_chip"]
+    assert 4 * (32 + 3 * n) > 64 * 1024 and matcher_variant(VK_INIT, n, n) == 0
+    c = {c.name: c for c in mc.proj_cases()}["proj_frame_mappoints_claims"]
+    assert c.mode == PROJ_FRAME_MAPPOINTS and c.qflags is None
+    ratio, ori = c.ratio, True          # FRAME_MAPPOINTS has no rotation filter
+    m = matcher(ratio, ori)
+
+    def claim_search():
+        n_o, m_o = om.search_by_projection(c.mode, c.target, c.q, c.qdesc, c.claimed, ISG,
+                                           orb_dist=c.orb_dist, nnratio=ratio, check_ori=ori)
+        n_g, m_g = m.search_by_projection(c.mode, c.target, c.q, c.qdesc, c.claimed, ISG,
+                                          orb_dist=c.orb_dist)
+        assert n_g == n_o > 0
+        np.testing.assert_array_equal(m_g, m_o)
+
+    f1, f2, prev = init_limit_case(n)
+    p_g, p_o, p_r = prev.copy(), prev.copy(), prev.copy()
+    n_o, m_o = om.search_for_initialization(f1, f2, p_o, INIT_LIMIT_WINDOW, ratio, ori)
+    codes = ref.initialization_py(f1, f2, p_r, INIT_LIMIT_WINDOW, ratio, ori)[2]
+    rescans = sum("+rescan" in k for k in codes)
+    print(f"n={n}: {n_o} matches, {codes.count('taken_over')} re-assigned, {rescans} re-scans, "
+          f"{codes.count('rotation_removed')} rotated out")
+    assert n_o > 100 and codes.count("taken_over") >= 1 and rescans >= 1   # CPU run: 943, 8, 382
+    claim_search()
+    n_g, m_g = m.SearchForInitialization(f1, f2, p_g, INIT_LIMIT_WINDOW)
+    claim_search()
+    assert n_g == n_o
+    np.testing.assert_array_equal(m_g, m_o)
+    np.testing.assert_array_equal(p_g.view(np.int32), p_o.view(np.int32))
+
+
 def test_initialization_first_unsupported_size(orbx_lib, gpu):
     from my_orb_slam2_amd import OrbxError
     from my_orb_slam2_amd.matcher import VK_INIT, matcher_variant

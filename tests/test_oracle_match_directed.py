@@ -313,6 +313,7 @@ def test_variant_query_reaches_both_variants(orbx_lib):
     r = mc.scan_regimes(matcher_variant, VK_INIT)
     assert r["first_fallback"] is None and r["error"] == UNSUPPORTED
     assert r["first_error"] == r["last_on_chip"] + 1
+    assert (r["last_on_chip"], r["first_error"]) == (13621, 13622)   # 4 * (32 + 3n) bytes of LDS
     assert matcher_variant(VK_PROJ + 7, 0, 10, 10) == INVALID
     assert matcher_variant(VK_PROJ - 1, 0, 10, 10) == INVALID
 
