@@ -29,7 +29,7 @@ SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_matc
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
            "orbx_host.h", "orbx_stage.h", "orbx_layout.h", "orbx_extractor.h", "orbx_lm.h",
            "orbx_match_kernels.h", "orbx_matcher.h", "orbx_ransac.h", "orbx_fast_pretest.h",
-           "orbx_pattern.inc",
+           "orbx_pattern.inc", "orbx_cv.h",
            "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
            "../../include/orbx_frame.h", "../../include/orbx_kfdb.h",
            "../../include/orbx_localmap.h"]

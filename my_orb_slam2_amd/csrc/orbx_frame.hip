@@ -25,6 +25,7 @@
 #include <mutex>
 
 #include "../../include/orbx_frame.h"
+#include "orbx_cv.h"
 #include "orbx_device.h"
 #include "orbx_host.h"
 #include "orbx_math.h"
@@ -82,11 +83,6 @@ __global__ __launch_bounds__(256) void k_undistort(UndistParams P, const orbx_ke
     orbx_keypoint kp = in[i];
     if (!copy) undistort_pt(P, kp.x, kp.y, kp.x, kp.y);
     out[i] = kp;
-}
-
-// (int) of a float as x86 cvttss2si: INT_MIN when out of range or NaN
-__device__ __forceinline__ int x86_trunc(float f) {
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
 }
 
 // PosInGrid (Frame.cc:407-417): round((x - mnMinX) * inv) in float, half away from zero, then
@@ -202,47 +198,28 @@ __global__ __launch_bounds__(256) void k_gray(const uint8_t* __restrict__ src, i
 // and the query SearchByProjection(Frame&, vpMapPoints, th) forms from its outputs
 // (ORBmatcher.cc:55-80).  The float / double steps follow the reference's types (see
 // include/orbx_frame.h); the library is built with -ffp-contract=off, so every float op is
-// rounded on its own as on x86.
+// rounded on its own as on x86.  The OpenCV forms are orbx_cv.h's.
 __device__ __forceinline__ bool frustum_query(const orbx_frame_pose& F, const orbx_map_point& M,
                                               float cos_lim, float th, orbx_proj_query& q) {
-    // Pc = mRcw*P + mtcw: cv::gemm(Rcw, P, 1, tcw, 1) small-matrix path (len 3, one column):
-    // t_r = a_r0*b0 + a_r1*b1 + a_r2*b2 in float, d_r = (float)(t_r*1.0 + c_r*1.0)
     float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        float t = __fmul_rn(F.Rcw[3 * r], M.pos[0]);
-        t = __fadd_rn(t, __fmul_rn(F.Rcw[3 * r + 1], M.pos[1]));
-        t = __fadd_rn(t, __fmul_rn(F.Rcw[3 * r + 2], M.pos[2]));
-        Pc[r] = (float)((double)t + (double)F.tcw[r]);
-    }
+    gemm3(F.Rcw, M.pos, F.tcw, Pc);                       // Pc = mRcw*P + mtcw
     if (Pc[2] < 0.0f) return false;                       // positive depth
     const float invz = __fdiv_rn(1.0f, Pc[2]);
-    const float u = __fadd_rn(__fmul_rn(__fmul_rn(F.fx, Pc[0]), invz), F.cx);
-    const float v = __fadd_rn(__fmul_rn(__fmul_rn(F.fy, Pc[1]), invz), F.cy);
+    const float u = pinhole_frame(F.fx, F.cx, Pc[0], invz);
+    const float v = pinhole_frame(F.fy, F.cy, Pc[1], invz);
     if (u < F.min_x || u > F.max_x) return false;
     if (v < F.min_y || v > F.max_y) return false;
     const float maxD = __fmul_rn(1.2f, M.max_dist), minD = __fmul_rn(0.8f, M.min_dist);
-    // PO = P - mOw; dist = cv::norm(PO): squares accumulated in double (normL2Sqr<float,
-    // double>), sqrt, stored in a float
+    // PO = P - mOw; dist = cv::norm(PO), stored in a float
     const float PO[3] = {__fsub_rn(M.pos[0], F.Ow[0]), __fsub_rn(M.pos[1], F.Ow[1]),
                          __fsub_rn(M.pos[2], F.Ow[2])};
-    double ss = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ss = __dadd_rn(ss, __dmul_rn((double)PO[k], (double)PO[k]));
-    const float dist = (float)__dsqrt_rn(ss);
+    const float dist = norm3(PO);
     if (dist < minD || dist > maxD) return false;
-    // viewCos = PO.dot(Pn) / dist: Mat::dot in double (dotProd_), / dist in double
-    double dot = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) dot = __dadd_rn(dot, __dmul_rn((double)PO[k], (double)M.normal[k]));
-    const float viewCos = (float)__ddiv_rn(dot, (double)dist);
+    // viewCos = PO.dot(Pn) / dist: / dist in double
+    const float viewCos = (float)__ddiv_rn(dot3(PO, M.normal), (double)dist);
     if (viewCos < cos_lim) return false;
-    // PredictScale: ceil(log(ratio) / mfLogScaleFactor) on floats (std::log / std::ceil)
-    const float ratio = __fdiv_rn(M.max_dist, dist);
-    const float qf = ceilf(__fdiv_rn(glibc_logf(ratio), F.log_scale_factor));
-    int lvl = x86_trunc(qf);
-    if (lvl < 0) lvl = 0;
-    else if (lvl >= F.nlevels) lvl = F.nlevels - 1;
+    const int lvl = predict_level(glibc_logf(__fdiv_rn(M.max_dist, dist)), F.log_scale_factor,
+                                  F.nlevels);
     // SearchByProjection: r = RadiusByViewingCos (viewCos > 0.998 in double), * th if th != 1
     float r = (double)viewCos > 0.998 ? 2.5f : 4.0f;
     if ((double)th != 1.0) r = __fmul_rn(r, th);
@@ -336,23 +313,7 @@ __global__ __launch_bounds__(256) void k_rgbd_depth(UndistParams P, int copy,
     }
 }
 
-// Frame::UnprojectStereo (src/Frame.cc:713-727) / KeyFrame::UnprojectStereo (KeyFrame.cc:629-645)
-// for z > 0: x = (u - cx) * z * invfx, y likewise, x3D = Rwc * (x, y, z) + Ow as cv::gemm's
-// small-matrix path evaluates it (see frustum_query); Rwc is the transpose of F.Rcw.
-__device__ __forceinline__ void unproject_pt(const orbx_frame_pose& F, float u, float v, float z,
-                                             float* out) {
-    const float invfx = __fdiv_rn(1.0f, F.fx), invfy = __fdiv_rn(1.0f, F.fy);
-    const float c[3] = {__fmul_rn(__fmul_rn(__fsub_rn(u, F.cx), z), invfx),
-                        __fmul_rn(__fmul_rn(__fsub_rn(v, F.cy), z), invfy), z};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        float t = __fmul_rn(F.Rcw[r], c[0]);
-        t = __fadd_rn(t, __fmul_rn(F.Rcw[3 + r], c[1]));
-        t = __fadd_rn(t, __fmul_rn(F.Rcw[6 + r], c[2]));
-        out[r] = (float)((double)t + (double)F.Ow[r]);
-    }
-}
-
+// Frame / KeyFrame::UnprojectStereo (orbx_cv.h's unproject) for every keypoint with z > 0
 __global__ __launch_bounds__(256) void k_unproject(const orbx_frame_pose* __restrict__ poses,
                                                    const orbx_keypoint* __restrict__ keys,
                                                    int kp_stride, const float* __restrict__ depth,
@@ -365,7 +326,7 @@ __global__ __launch_bounds__(256) void k_unproject(const orbx_frame_pose* __rest
     const float z = depth[k];
     if (z > 0.0f) {
         float o[3];
-        unproject_pt(poses[f], keys[k].x, keys[k].y, z, o);
+        unproject(poses[f], keys[k].x, keys[k].y, z, o);
         x3d[3 * k] = o[0];
         x3d[3 * k + 1] = o[1];
         x3d[3 * k + 2] = o[2];
@@ -457,7 +418,7 @@ __global__ __launch_bounds__(1024) void k_close_points(
         if (j < V) {
             create[base + j] = has_point ? !has_point[base + i] : 1;
             float o[3];
-            unproject_pt(F, keys[base + i].x, keys[base + i].y, __uint_as_float((unsigned)(key >> 32)), o);
+            unproject(F, keys[base + i].x, keys[base + i].y, __uint_as_float((unsigned)(key >> 32)), o);
             x3d[3 * (base + j)] = o[0];
             x3d[3 * (base + j) + 1] = o[1];
             x3d[3 * (base + j) + 2] = o[2];
@@ -486,26 +447,6 @@ bool close_prepare() {
 }
 
 // ---- the projection loops of the other six SearchByProjection modes ---------------------------
-
-// cv::gemm(R, P, 1, t, 1) small-matrix path, as in frustum_query
-__device__ __forceinline__ void gemm3(const float* __restrict__ R, const float* P,
-                                      const float* __restrict__ t, float* out) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        float s = __fmul_rn(R[3 * r], P[0]);
-        s = __fadd_rn(s, __fmul_rn(R[3 * r + 1], P[1]));
-        s = __fadd_rn(s, __fmul_rn(R[3 * r + 2], P[2]));
-        out[r] = (float)((double)s + (double)t[r]);
-    }
-}
-
-// (float)cv::norm(a): squares accumulated in double, sqrt, stored in a float
-__device__ __forceinline__ float norm3(const float* a) {
-    double ss = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) ss = __dadd_rn(ss, __dmul_rn((double)a[k], (double)a[k]));
-    return (float)__dsqrt_rn(ss);
-}
 
 // The per-MapPoint body of the reference's loop for MODE (include/orbx_frame.h lists the steps;
 // ORBmatcher.cc LAST_FRAME :1402-1458, KEYFRAME :1544-1596, KF_SCW :321-390, FUSE :881-946,
@@ -537,11 +478,13 @@ __device__ __forceinline__ bool project_query(const orbx_proj_job& J, const floa
     if (MODE == ORBX_PROJ_LAST_FRAME && invz < 0.0f) return false;
     float u, v;
     if (FRAME) {
-        u = __fadd_rn(__fmul_rn(__fmul_rn(F.fx, Pc[0]), invz), F.cx);
-        v = __fadd_rn(__fmul_rn(__fmul_rn(F.fy, Pc[1]), invz), F.cy);
+        u = pinhole_frame(F.fx, F.cx, Pc[0], invz);
+        v = pinhole_frame(F.fy, F.cy, Pc[1], invz);
         if (u < F.min_x || u > F.max_x) return false;
         if (v < F.min_y || v > F.max_y) return false;
     } else {
+        // orbx_cv.h's pinhole_kf written out, both quotients ahead of both coordinates: through
+        // the calls k_project<SIM3> comes out with the operands of one packed add exchanged
         const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
         u = __fadd_rn(__fmul_rn(F.fx, x), F.cx);
         v = __fadd_rn(__fmul_rn(F.fy, y), F.cy);
@@ -564,17 +507,8 @@ __device__ __forceinline__ bool project_query(const orbx_proj_job& J, const floa
         }
         const float maxD = __fmul_rn(1.2f, max_dist), minD = __fmul_rn(0.8f, min_dist);
         if (dist < minD || dist > maxD) return false;
-        if (NORMAL) {
-            double dot = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                dot = __dadd_rn(dot, __dmul_rn((double)PO[k], (double)Pn[k]));
-            if (dot < __dmul_rn(0.5, (double)dist)) return false;
-        }
-        const float ratio = __fdiv_rn(max_dist, dist);
-        lvl = x86_trunc(ceilf(__fdiv_rn(glibc_logf(ratio), F.log_scale_factor)));
-        if (lvl < 0) lvl = 0;
-        else if (lvl >= nlevels) lvl = nlevels - 1;
+        if (NORMAL && dot3(PO, Pn) < __dmul_rn(0.5, (double)dist)) return false;
+        lvl = predict_level(glibc_logf(__fdiv_rn(max_dist, dist)), F.log_scale_factor, nlevels);
     }
     q.u = u;
     q.v = v;

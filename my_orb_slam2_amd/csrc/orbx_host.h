@@ -50,10 +50,6 @@ struct DevBuf {
 // Sizes inside a device block, rounded as StagePlan rounds its parts (also used on the device).
 __host__ __device__ inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// (int) of a double as x86-64 converts it (cvttsd2si; cvttss2si for a widened float): NaN and
-// everything outside int's range give INT_MIN
-inline int cvtt(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
-
 // Device staging of the host-array entry points: a pool of (device, non-blocking stream,
 // growable device buffer, staging plan) slots taken for the length of one call.  After warm-up a
 // call allocates nothing, and it waits only for its own stream, never for the device (the

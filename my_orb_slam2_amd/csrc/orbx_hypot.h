@@ -3,19 +3,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-namespace orbx_hypot_detail {
-__device__ __forceinline__ double dm(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double da(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double ds(double a, double b) { return __dsub_rn(a, b); }
-__device__ __forceinline__ double dd(double a, double b) { return __ddiv_rn(a, b); }
-}  // namespace orbx_hypot_detail
+#include "orbx_cv.h"
 
+namespace orbx {
 // glibc 2.35 __hypot for finite and non-finite doubles (e_hypot.c: kernel() without
 // __FP_FAST_FMA, SCALE 0x1p-600, LARGE_VAL 0x1p+511, TINY_VAL 0x1p-459, EPS 0x1p-54)
 __device__ __forceinline__ double hypot_kernel(double ax, double ay) {
-    using namespace orbx_hypot_detail;
     double t1, t2;
-    double h = __dsqrt_rn(da(dm(ax, ax), dm(ay, ay)));
+    double h = sq(da(dm(ax, ax), dm(ay, ay)));
     if (h <= dm(2.0, ay)) {
         const double delta = ds(h, ay);
         t1 = dm(ax, ds(dm(2.0, delta), ax));
@@ -25,10 +20,9 @@ __device__ __forceinline__ double hypot_kernel(double ax, double ay) {
         t1 = dm(dm(2.0, delta), ds(ax, dm(2.0, ay)));
         t2 = da(dm(ds(dm(4.0, delta), ay), ay), dm(delta, delta));
     }
-    return ds(h, dd(da(t1, t2), dm(2.0, h)));
+    return ds(h, dv(da(t1, t2), dm(2.0, h)));
 }
 __device__ __forceinline__ double glibc_hypot(double x, double y) {
-    using namespace orbx_hypot_detail;
     if (!isfinite(x) || !isfinite(y)) {
         if (isinf(x) || isinf(y)) return INFINITY;
         return da(x, y);
@@ -38,12 +32,13 @@ __device__ __forceinline__ double glibc_hypot(double x, double y) {
     const double ax = x < y ? y : x, ay = x < y ? x : y;
     if (ax > 0x1p+511) {
         if (ay <= dm(ax, 0x1p-54)) return da(ax, ay);
-        return dd(hypot_kernel(dm(ax, 0x1p-600), dm(ay, 0x1p-600)), 0x1p-600);
+        return dv(hypot_kernel(dm(ax, 0x1p-600), dm(ay, 0x1p-600)), 0x1p-600);
     }
     if (ay < 0x1p-459) {
-        if (ax >= dd(ay, 0x1p-54)) return da(ax, ay);
-        return dm(hypot_kernel(dd(ax, 0x1p-600), dd(ay, 0x1p-600)), 0x1p-600);
+        if (ax >= dv(ay, 0x1p-54)) return da(ax, ay);
+        return dm(hypot_kernel(dv(ax, 0x1p-600), dv(ay, 0x1p-600)), 0x1p-600);
     }
-    if (ax >= dd(ay, 0x1p-54)) return da(ax, ay);
+    if (ax >= dv(ay, 0x1p-54)) return da(ax, ay);
     return hypot_kernel(ax, ay);
 }
+}  // namespace orbx

@@ -4,9 +4,8 @@
 // product, pivoted LDLT) [unverified-Eigen], RobustKernelHuber, and the whole of
 // OptimizationAlgorithmLevenberg::solve.  The edge models (error, Jacobian, update of the
 // estimate) stay with the kernels and reach the loop as callables; k_pose_opt runs lm_optimize,
-// k_sim3_opt keeps the same loop written out (it measured slower through the template).  row3 is
-// also orbx_sim3.hip's; the exactly rounded dv and sq are orbx_ransac.h's, shared with the RANSAC
-// solvers.
+// k_sim3_opt keeps the same loop written out (it measured slower through the template).  The
+// exactly rounded dv and sq are orbx_cv.h's, as are the OpenCV forms both kernels call.
 // Built with -ffp-contract=off like the rest of the library: every operation is rounded on its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -15,7 +14,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "orbx_ransac.h"
+#include "orbx_cv.h"
 
 namespace orbx {
 
@@ -25,13 +24,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 __device__ __forceinline__ bool uniform(bool v) { return __builtin_amdgcn_readfirstlane((int)v) != 0; }
-
-// cv::gemm's small-matrix path for a 3x3 A (row-major) times a 3-vector: float products and sums
-__device__ __forceinline__ float row3(const float* A, int r, const float* b) {
-    float t = A[3 * r] * b[0];
-    t = t + A[3 * r + 1] * b[1];
-    return t + A[3 * r + 2] * b[2];
-}
 
 // Eigen's Quaternion(Matrix3) for one position of the largest diagonal entry
 template <int I>

@@ -27,6 +27,7 @@
 #include "orbx_device.h"
 #include "orbx_kernels.h"
 #include "orbx_match_kernels.h"
+#include "orbx_math.h"
 
 namespace orbx {
 namespace {
@@ -116,12 +117,6 @@ __device__ __forceinline__ Top3 three_maxima(const int* h) {
         ind3 = -1;
     }
     return {ind1, ind2, ind3};
-}
-
-// float -> int as the x86-64 reference converts (int)floor(v): cvttss2si yields INT_MIN for
-// NaN and out-of-range values (the GPU's v_cvt_i32_f32 saturates instead).
-__device__ __forceinline__ int x86_int(float f) {
-    return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -607,13 +602,13 @@ __device__ __forceinline__ void window_scan(const ProjLaunch& g, const orbx_feat
                                             const Desc& qd, Dyn dyn, Sink& sink) {
     const int lane = lane_id() & (G - 1);
     const float x = q.u, y = q.v, r = q.radius;
-    const int nMinCellX = max(0, x86_int(floorf((x - T.min_x - r) * T.grid_inv_w)));
+    const int nMinCellX = max(0, x86_trunc(floorf((x - T.min_x - r) * T.grid_inv_w)));
     if (nMinCellX >= T.grid_cols) return;
-    const int nMaxCellX = min(T.grid_cols - 1, x86_int(ceilf((x - T.min_x + r) * T.grid_inv_w)));
+    const int nMaxCellX = min(T.grid_cols - 1, x86_trunc(ceilf((x - T.min_x + r) * T.grid_inv_w)));
     if (nMaxCellX < 0) return;
-    const int nMinCellY = max(0, x86_int(floorf((y - T.min_y - r) * T.grid_inv_h)));
+    const int nMinCellY = max(0, x86_trunc(floorf((y - T.min_y - r) * T.grid_inv_h)));
     if (nMinCellY >= T.grid_rows) return;
-    const int nMaxCellY = min(T.grid_rows - 1, x86_int(ceilf((y - T.min_y + r) * T.grid_inv_h)));
+    const int nMaxCellY = min(T.grid_rows - 1, x86_trunc(ceilf((y - T.min_y + r) * T.grid_inv_h)));
     if (nMaxCellY < 0) return;
     const bool checkLevels = mi.frame_grid && ((q.min_level > 0) || (q.max_level >= 0));
     for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {

@@ -17,6 +17,7 @@
 //
 // Everything here is compiled with -ffp-contract=off (host and device).
 #pragma once
+#include <limits.h>
 #include <stdint.h>
 #include <string.h>
 #include <math.h>
@@ -133,9 +134,19 @@ ORBX_HD float glibc_cosf(float y) {
     return __builtin_nanf("");
 }
 
+// (int) of a float as x86-64 converts it (cvttss2si): toward zero; NaN and everything outside
+// int's range give INT_MIN (the GPU's v_cvt_i32_f32 saturates instead and turns NaN into 0).
+ORBX_HD int x86_trunc(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN; }
+// (int) of a double likewise (cvttsd2si; cvttss2si for a widened float)
+ORBX_HD int x86_trunc(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
+
 // OpenCV cvRound(float) on x86-64 SSE2: cvtss2si with the default MXCSR, i.e.
-// round-half-to-even.
-ORBX_HD int cv_round(float v) { return (int)rintf(v); }
+// round-half-to-even; NaN and values outside int's range give INT_MIN.
+// tests/native/x86_cvt_check.cpp checks the three against the instructions.
+ORBX_HD int cv_round(float v) {
+    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return INT_MIN;
+    return (int)rintf(v);
+}
 
 // OpenCV 3.2 cv::fastAtan2 (core/src/mathfuncs.cpp): octant reduction + 7th-order odd
 // polynomial in degrees, every operation a separate float rounding.

@@ -8,11 +8,12 @@
 #include <cmath>
 
 #include "orbx_extractor.h"
+#include "orbx_math.h"
 
 namespace orbx {
 namespace {
 
-inline int cvRound(float v) { return (int)lrintf(v); }
+inline int cvRound(float v) { return cv_round(v); }
 inline int cvRound(double v) { return (int)lrint(v); }
 inline int cvFloor(float v) { int i = cvRound(v); float d = (float)(v - i); return i - (d < 0); }
 inline int cvCeil(float v) { int i = cvRound(v); float d = (float)(i - v); return i + (d < 0); }

@@ -35,6 +35,7 @@
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
+#include "orbx_cv.h"
 #include "orbx_host.h"
 #include "orbx_hypot.h"
 #include "orbx_match_kernels.h"
@@ -913,7 +914,6 @@ __global__ __launch_bounds__(256) void k_pnp_apply(
         orbx_frame_pose P = *tmpl;
         if (found) {
             // Tcw.copyTo(mCurrentFrame.mTcw) and Frame::UpdatePoseMatrices: mOw = -mRcw.t() * mtcw
-            // in cv::gemm's small-matrix form, as k_pose_opt writes it
             float R[9], t[3];
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
@@ -924,13 +924,8 @@ __global__ __launch_bounds__(256) void k_pnp_apply(
 #pragma unroll
             for (int k = 0; k < 9; ++k) P.Rcw[k] = R[k];
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                P.tcw[a] = t[a];
-                float acc = R[a] * t[0];
-                acc = acc + R[3 + a] * t[1];
-                acc = acc + R[6 + a] * t[2];
-                P.Ow[a] = -acc;
-            }
+            for (int a = 0; a < 3; ++a) P.tcw[a] = t[a];
+            camera_centre(R, t, P.Ow);
         }
         poses[j] = P;
     }
@@ -966,7 +961,7 @@ orbx_status orbx_pnp_ransac_parameters(double prob, int32_t min_inliers, int32_t
     if (N < 0 || !min_inliers_out || !max_its_out) return ORBX_ERR_INVALID;
     if (min_set != 4) return ORBX_ERR_UNSUPPORTED;
     float mRansacEpsilon = epsilon;
-    int nMinInliers = cvtt((double)((float)N * mRansacEpsilon));
+    int nMinInliers = x86_trunc((double)((float)N * mRansacEpsilon));
     if (nMinInliers < min_inliers) nMinInliers = min_inliers;
     if (nMinInliers < min_set) nMinInliers = min_set;
     const float ratio = (float)nMinInliers / (float)N;

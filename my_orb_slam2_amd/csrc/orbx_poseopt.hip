@@ -424,7 +424,7 @@ __global__ __launch_bounds__(64 * PO_WAVES) void k_pose_opt(const PoseOptLaunch 
     }
 
     // Converter::toCvMat(SE3Quat) + Frame::SetPose: the quaternion's matrix, rounded to float,
-    // then mOw = -mRcw.t() * mtcw in cv::gemm's small-matrix form
+    // then mOw = -mRcw.t() * mtcw
     if (lane == 0) {
         const double tx = 2.0 * est.qx, ty = 2.0 * est.qy, tz = 2.0 * est.qz;
         const double twx = tx * est.qw, twy = ty * est.qw, twz = tz * est.qw;
@@ -440,10 +440,7 @@ __global__ __launch_bounds__(64 * PO_WAVES) void k_pose_opt(const PoseOptLaunch 
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             Po->tcw[r] = t[r];
-            float s = R[r] * t[0];
-            s = s + R[3 + r] * t[1];
-            s = s + R[6 + r] * t[2];
-            Po->Ow[r] = -s;
+            Po->Ow[r] = camera_centre_row(R, t, r);
         }
         g.ngood[f] = nedges - nbad;
         g.info[f] = (uint32_t)rounds | (iters << ORBX_POSEOPT_ITERS_SHIFT) |

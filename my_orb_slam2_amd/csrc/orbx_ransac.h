@@ -1,10 +1,10 @@
 // orbx_ransac.h — what the RANSAC solvers (orbx_sim3.hip, orbx_pnp.hip) share: everything that is
 // the reference's RANSAC loop and not Horn or EPnP.  On the host the minimal-set sampling and the
 // iteration count of SetRansacParameters; on both sides the window of one iterate() call and the
-// cursor the scratch layouts are written with; on the device the 4x4 of a pose.  The exactly
-// rounded division and square root are here for orbx_lm.h as well.  The inlier counts (lanes
-// stride over N, ballot, popcount) stay written out in the kernels: through a helper that takes
-// the test as a callable k_sim3_hypotheses and k_pnp_select compiled to other code.
+// cursor the scratch layouts are written with; on the device the 4x4 of a pose.  The inlier counts
+// (lanes stride over N, ballot, popcount) stay written out in the kernels: through a helper that
+// takes the test as a callable k_sim3_hypotheses and k_pnp_select compiled to other code.  The
+// exactly rounded one-line wrappers (dv, sq, fdiv, fsqrt) are orbx_cv.h's.
 // Built with -ffp-contract=off like the rest of the library: every operation is rounded on its own.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,17 +14,9 @@
 #include <cstdlib>
 
 #include "orbx_host.h"
+#include "orbx_math.h"
 
 namespace orbx {
-
-// IEEE division and square root whatever the compiler's defaults
-__device__ __forceinline__ double dv(double a, double b) { return __ddiv_rn(a, b); }
-__device__ __forceinline__ double sq(double a) { return __dsqrt_rn(a); }
-__device__ __forceinline__ float fdiv(float a, float b) { return __fdiv_rn(a, b); }
-// sqrtf correctly rounded whatever the compiler's defaults (__fsqrt_rn is the native, approximate
-// instruction unless the headers are configured otherwise): the double square root of a float,
-// rounded to float, is the correctly rounded float square root (53 >= 2 * 24 + 2 bits)
-__device__ __forceinline__ float fsqrt(float a) { return (float)__dsqrt_rn((double)a); }
 
 // The minimal sets of n_its iterations from K raw rand() values each (Sim3Solver.cc:163-177,
 // PnPsolver.cc:188-201): DUtils::Random::RandomInt(0, size - 1) on vAvailableIndices, which is
@@ -63,7 +55,7 @@ orbx_status sample_minimal_sets(int32_t N, int32_t n_its, const int32_t* rand_va
 // epsilon is the caller's, all_inliers its mRansacMinInliers == N
 inline int ransac_iterations(double prob, float epsilon, bool all_inliers, int max_its) {
     const int nIterations =
-        all_inliers ? 1 : cvtt(::ceil(::log(1 - prob) / ::log(1 - ::pow((double)epsilon, 3.0))));
+        all_inliers ? 1 : x86_trunc(::ceil(::log(1 - prob) / ::log(1 - ::pow((double)epsilon, 3.0))));
     const int lo = nIterations < max_its ? nIterations : max_its;
     return lo > 1 ? lo : 1;
 }

@@ -39,6 +39,7 @@
 
 #include "../../include/orbx_frame.h"
 #include "orbx_host.h"
+#include "orbx_math.h"
 
 using namespace orbx;
 
@@ -179,11 +180,6 @@ __global__ __launch_bounds__(256) void k_remap(RemapSide L, RemapSide R, int dst
     }
 }
 
-// cvRound(float) on x86 (cvtss2si): round half to even; NaN and values outside int: INT_MIN.
-inline int cv_round(float v) {
-    if (!(v >= -2147483648.0f && v < 2147483648.0f)) return INT_MIN;
-    return (int)std::nearbyintf(v);   // the default rounding mode: to nearest, ties to even
-}
 inline int sat_short(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
 
 orbx_status side_args(const orbx_rectifier* r, const uint8_t* d_src, size_t srs, size_t sis,

@@ -27,8 +27,8 @@
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
+#include "orbx_cv.h"
 #include "orbx_host.h"
-#include "orbx_lm.h"
 #include "orbx_match_kernels.h"
 #include "orbx_matcher.h"
 #include "orbx_math.h"
@@ -53,13 +53,6 @@ struct Sim3Hyp {
     float sRinv[9], tinv[3];  // mT21i
     int32_t count;            // mnInliersi
 };
-
-// Mat::convertTo(alpha) on a CV_32F value: a plain copy when |alpha - 1| < DBL_EPSILON, otherwise
-// x * (float)alpha + 0.0f
-__device__ __forceinline__ float cvt_scale(float x, double alpha) {
-    if (fabs(alpha - 1.0) < 2.220446049250313e-16) return x;
-    return x * (float)alpha + 0.0f;
-}
 
 // lapack.cpp's hypot<float>
 __device__ __forceinline__ float cv_hypotf(float a, float b) {
@@ -333,12 +326,10 @@ __device__ __forceinline__ void compute_sim3(const float (*P1)[3], const float (
 __device__ __forceinline__ void project(const float* R, const float* t, const float* X, float fx,
                                         float fy, float cx, float cy, float* uv) {
     float P[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) P[r] = (float)((double)row3(R, r, X) + (double)t[r]);
+    gemm3(R, X, t, P);
     const float invz = fdiv(1.0f, P[2]);
-    const float x = P[0] * invz, y = P[1] * invz;
-    uv[0] = fx * x + cx;
-    uv[1] = fy * y + cy;
+    uv[0] = pinhole_kf(fx, cx, P[0], invz);
+    uv[1] = pinhole_kf(fy, cy, P[1], invz);
 }
 
 // CheckInliers' body (:350-356) for one correspondence
@@ -425,15 +416,15 @@ __global__ __launch_bounds__(256) void k_sim3_prepare(const Sim3Launch g) {
     Sim3Prep q;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        q.X1[r] = (float)((double)row3(F1.Rcw, r, c.X1w) + (double)F1.tcw[r]);
-        q.X2[r] = (float)((double)row3(F2.Rcw, r, c.X2w) + (double)F2.tcw[r]);
+        q.X1[r] = gemm3_row(F1.Rcw, r, c.X1w, F1.tcw);
+        q.X2[r] = gemm3_row(F2.Rcw, r, c.X2w, F2.tcw);
     }
     // FromCameraToImage (:405-423)
     const float iz1 = fdiv(1.0f, q.X1[2]), iz2 = fdiv(1.0f, q.X2[2]);
-    q.p1[0] = F1.fx * (q.X1[0] * iz1) + F1.cx;
-    q.p1[1] = F1.fy * (q.X1[1] * iz1) + F1.cy;
-    q.p2[0] = F2.fx * (q.X2[0] * iz2) + F2.cx;
-    q.p2[1] = F2.fy * (q.X2[1] * iz2) + F2.cy;
+    q.p1[0] = pinhole_kf(F1.fx, F1.cx, q.X1[0], iz1);
+    q.p1[1] = pinhole_kf(F1.fy, F1.cy, q.X1[1], iz1);
+    q.p2[0] = pinhole_kf(F2.fx, F2.cx, q.X2[0], iz2);
+    q.p2[1] = pinhole_kf(F2.fy, F2.cy, q.X2[1], iz2);
     q.m1 = max_error(J.sigma2_1[c.octave1]);
     q.m2 = max_error(J.sigma2_2[c.octave2]);
     q.i1 = c.i1;

@@ -188,8 +188,8 @@ __device__ __forceinline__ void load_pair(const JobCtx& c, int i, PairIn& p) {
     const orbx_sim3opt_corr q = c.corr[i];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        p.X1[r] = (double)(float)((double)row3(c.F1->Rcw, r, q.X1w) + (double)c.F1->tcw[r]);
-        p.X2[r] = (double)(float)((double)row3(c.F2->Rcw, r, q.X2w) + (double)c.F2->tcw[r]);
+        p.X1[r] = (double)gemm3_row(c.F1->Rcw, r, q.X1w, c.F1->tcw);
+        p.X2[r] = (double)gemm3_row(c.F2->Rcw, r, q.X2w, c.F2->tcw);
     }
     p.o1[0] = (double)q.kp1[0], p.o1[1] = (double)q.kp1[1];
     p.o2[0] = (double)q.kp2[0], p.o2[1] = (double)q.kp2[1];

@@ -21,6 +21,7 @@
 
 #include "../../include/orbx_frame.h"
 #include "../../include/orbx_match.h"
+#include "orbx_cv.h"
 #include "orbx_host.h"
 #include "orbx_hypot.h"
 #include "orbx_match_kernels.h"
@@ -30,14 +31,6 @@ using namespace orbx;
 namespace {
 
 constexpr int SVD_MAX_SWEEPS = 30;   // max(m, 30) with m = 4 (lapack.cpp, JacobiSVDImpl_)
-
-__device__ __forceinline__ float fm(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float fa(float a, float b) { return __fadd_rn(a, b); }
-__device__ __forceinline__ float fs(float a, float b) { return __fsub_rn(a, b); }
-__device__ __forceinline__ double dm(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double da(double a, double b) { return __dadd_rn(a, b); }
-__device__ __forceinline__ double ds(double a, double b) { return __dsub_rn(a, b); }
-__device__ __forceinline__ double dd(double a, double b) { return __ddiv_rn(a, b); }
 
 // cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV) on a 4x4 CV_32F A, reduced to vt.row(3)
 // [unverified-OpenCV]: _SVDcompute transposes A into At (row i = column i of A) and runs
@@ -76,11 +69,11 @@ __device__ __forceinline__ void svd4_vt_row3(const float* A, float* v) {
                 float c, s;
                 if (beta < 0.0) {
                     const double delta = dm(ds(gamma, beta), 0.5);
-                    s = (float)__dsqrt_rn(dd(delta, gamma));
-                    c = (float)dd(p, dm(dm(gamma, (double)s), 2.0));
+                    s = (float)__dsqrt_rn(dv(delta, gamma));
+                    c = (float)dv(p, dm(dm(gamma, (double)s), 2.0));
                 } else {
-                    c = (float)__dsqrt_rn(dd(da(gamma, beta), dm(gamma, 2.0)));
-                    s = (float)dd(p, dm(dm(gamma, (double)c), 2.0));
+                    c = (float)__dsqrt_rn(dv(da(gamma, beta), dm(gamma, 2.0)));
+                    s = (float)dv(p, dm(dm(gamma, (double)c), 2.0));
                 }
                 a = b = 0.0;
 #pragma unroll
@@ -145,35 +138,7 @@ __device__ __forceinline__ void svd4_vt_row3(const float* A, float* v) {
 
 // Rcw.row(r).dot(x3Dt) + tcw(r): Mat::dot in double, + the float in double, stored in a float
 __device__ __forceinline__ float row_dot(const orbx_frame_pose& F, int r, const float* X) {
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) s = da(s, dm((double)F.Rcw[3 * r + k], (double)X[k]));
-    return (float)da(s, (double)F.tcw[r]);
-}
-
-// (float)cv::norm(X - Ow)
-__device__ __forceinline__ float dist_to(const float* X, const float* Ow) {
-    double ss = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float d = fs(X[k], Ow[k]);
-        ss = da(ss, dm((double)d, (double)d));
-    }
-    return (float)__dsqrt_rn(ss);
-}
-
-// KeyFrame::UnprojectStereo for z > 0 (KeyFrame.cc:629-645), as k_unproject evaluates it
-__device__ __forceinline__ void unproject_kf(const orbx_frame_pose& F, float u, float v, float z,
-                                             float* out) {
-    const float invfx = __fdiv_rn(1.0f, F.fx), invfy = __fdiv_rn(1.0f, F.fy);
-    const float c[3] = {fm(fm(fs(u, F.cx), z), invfx), fm(fm(fs(v, F.cy), z), invfy), z};
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        float t = fm(F.Rcw[r], c[0]);
-        t = fa(t, fm(F.Rcw[3 + r], c[1]));
-        t = fa(t, fm(F.Rcw[6 + r], c[2]));
-        out[r] = (float)da((double)t, (double)F.Ow[r]);
-    }
+    return (float)da(dot3(F.Rcw + 3 * r, X), (double)F.tcw[r]);
 }
 
 // One feature of a keyframe as the loop reads it.
@@ -192,9 +157,9 @@ __device__ __forceinline__ bool reproj_ok(const orbx_frame_pose& F, const TriFea
                                           float mbf, float z, const float* X) {
     const float sigma2 = fm(F.scale[f.octave], F.scale[f.octave]);
     const float x = row_dot(F, 0, X), y = row_dot(F, 1, X);
-    const float invz = (float)dd(1.0, (double)z);
-    const float u = fa(fm(fm(F.fx, x), invz), F.cx);
-    const float v = fa(fm(fm(F.fy, y), invz), F.cy);
+    const float invz = (float)dv(1.0, (double)z);
+    const float u = pinhole_frame(F.fx, F.cx, x, invz);
+    const float v = pinhole_frame(F.fy, F.cy, y, invz);
     const float ex = fs(u, f.x), ey = fs(v, f.y);
     if (!stereo)
         return !((double)fa(fm(ex, ex), fm(ey, ey)) > dm(5.991, (double)sigma2));
@@ -212,13 +177,12 @@ __device__ __forceinline__ int triangulate_one(const orbx_frame_pose& F1,
                           fm(fs(f1.y, F1.cy), __fdiv_rn(1.0f, F1.fy)), 1.0f};
     const float xn2[3] = {fm(fs(f2.x, F2.cx), __fdiv_rn(1.0f, F2.fx)),
                           fm(fs(f2.y, F2.cy), __fdiv_rn(1.0f, F2.fy)), 1.0f};
-    // ray = Rwc * xn: cv::gemm's small-matrix form without an added term
+    // ray = Rwc * xn; cosParallaxRays = ray1.dot(ray2) / (cv::norm(ray1) * cv::norm(ray2)).  The
+    // three sums are those of orbx_cv.h's dot3 and norm3 written out, a step of each in turn:
+    // through calls the kernel's instructions come out in another order.
     float ray1[3], ray2[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        ray1[r] = fa(fa(fm(F1.Rcw[r], xn1[0]), fm(F1.Rcw[3 + r], xn1[1])), fm(F1.Rcw[6 + r], xn1[2]));
-        ray2[r] = fa(fa(fm(F2.Rcw[r], xn2[0]), fm(F2.Rcw[3 + r], xn2[1])), fm(F2.Rcw[6 + r], xn2[2]));
-    }
+    gemm3t(F1.Rcw, xn1, ray1);
+    gemm3t(F2.Rcw, xn2, ray2);
     double dot = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -226,7 +190,7 @@ __device__ __forceinline__ int triangulate_one(const orbx_frame_pose& F1,
         s1 = da(s1, dm((double)ray1[k], (double)ray1[k]));
         s2 = da(s2, dm((double)ray2[k], (double)ray2[k]));
     }
-    const float cos_rays = (float)dd(dot, dm(__dsqrt_rn(s1), __dsqrt_rn(s2)));
+    const float cos_rays = (float)dv(dot, dm(sq(s1), sq(s2)));
     const float cps0 = fa(cos_rays, 1.0f);
     float cps1 = cps0, cps2 = cps0;
     if (st1) cps1 = f1.cos_stereo;          // :386-389: `else if`, so never both
@@ -252,9 +216,10 @@ __device__ __forceinline__ int triangulate_one(const orbx_frame_pose& F1,
         float v[4];
         svd4_vt_row3(A, v);
         if (v[3] == 0.0f) return ORBX_TRI_W_ZERO;
-        // x3D.rowRange(0,3) / w: convertTo(alpha = 1.0 / w): x * (float)alpha + 0.0f, a plain copy
-        // when |alpha - 1| < DBL_EPSILON  [unverified-OpenCV]
-        const double alpha = dd(1.0, (double)v[3]);
+        // x3D.rowRange(0,3) / w: convertTo(alpha = 1.0 / w)
+        const double alpha = dv(1.0, (double)v[3]);
+        // (orbx_cv.h's cvt_scale written out: through the call the kernel comes out four
+        // instructions shorter and in another order)
         if (fabs(ds(alpha, 1.0)) < 2.220446049250313e-16) {
             X[0] = v[0], X[1] = v[1], X[2] = v[2];
         } else {
@@ -265,11 +230,11 @@ __device__ __forceinline__ int triangulate_one(const orbx_frame_pose& F1,
         code = ORBX_TRI_OK_TRIANGULATED;
     } else if (st1 && cps1 < cps2) {
         if (!(f1.depth > 0.0f)) return ORBX_TRI_LOW_PARALLAX;   // UnprojectStereo returns no point
-        unproject_kf(F1, f1.rx, f1.ry, f1.depth, X);
+        unproject(F1, f1.rx, f1.ry, f1.depth, X);
         code = ORBX_TRI_OK_STEREO1;
     } else if (st2 && cps2 < cps1) {
         if (!(f2.depth > 0.0f)) return ORBX_TRI_LOW_PARALLAX;
-        unproject_kf(F2, f2.rx, f2.ry, f2.depth, X);
+        unproject(F2, f2.rx, f2.ry, f2.depth, X);
         code = ORBX_TRI_OK_STEREO2;
     } else {
         return ORBX_TRI_LOW_PARALLAX;
@@ -281,7 +246,11 @@ __device__ __forceinline__ int triangulate_one(const orbx_frame_pose& F1,
     if (z2 <= 0.0f) return ORBX_TRI_BEHIND_2;
     if (!reproj_ok(F1, f1, st1, F1.mbf, z1, X)) return ORBX_TRI_REPROJ_1;
     if (!reproj_ok(F2, f2, st2, F1.mbf, z2, X)) return ORBX_TRI_REPROJ_2;   // :482: KF1's mbf
-    const float dist1 = dist_to(X, F1.Ow), dist2 = dist_to(X, F2.Ow);
+    // dist = (float)cv::norm(x3D - Ow)
+    const float n1[3] = {fs(X[0], F1.Ow[0]), fs(X[1], F1.Ow[1]), fs(X[2], F1.Ow[2])};
+    const float dist1 = norm3(n1);
+    const float n2[3] = {fs(X[0], F2.Ow[0]), fs(X[1], F2.Ow[1]), fs(X[2], F2.Ow[2])};
+    const float dist2 = norm3(n2);
     if (dist1 == 0.0f || dist2 == 0.0f) return ORBX_TRI_DIST_ZERO;
     const float ratio_dist = __fdiv_rn(dist2, dist1);
     const float ratio_octave = __fdiv_rn(F1.scale[f1.octave], F2.scale[f2.octave]);

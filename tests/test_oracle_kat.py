@@ -113,3 +113,17 @@ def test_glibc_logf_port_exhaustive(tmp_path):
                        timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "checked=2147483648 logf_mismatch=0" in r.stdout
+
+
+def test_x86_conversions_match_the_instructions(tmp_path):
+    """orbx_math.h's x86_trunc(float), x86_trunc(double) and cv_round(float) == cvttss2si,
+    cvttsd2si and cvtss2si: float bit patterns at an odd stride over all 2^32, every pattern
+    within 64 ulps of 0, +-0.5, +-2^23, +-2^31, inf and NaN, every half-integer below 2^20, and
+    for the double form the neighbourhoods of +-2^31 and -2^31 - 1 as well."""
+    exe = tmp_path / "xcc"
+    subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17",
+                    str(ROOT / "tests/native/x86_cvt_check.cpp"), "-o", str(exe), "-lm"],
+                   check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "trunc_mismatch=0 round_mismatch=0 trunc_f64_mismatch=0" in r.stdout
