@@ -8,6 +8,10 @@
  * of the map, one workgroup per frame, and writes the block orbx_is_in_frustum_batch_device,
  * the projection search, orbx_matches_to_features_batch_device and
  * orbx_pose_optimization_batch_device read, so a tracked frame never leaves the device.
+ *
+ * The records and descriptors that walk reads are local mapping's results:
+ * MapPoint::UpdateNormalAndDepth and MapPoint::ComputeDistinctiveDescriptors
+ * (src/MapPoint.cc:252-392), restated over the same snapshot by orbx_refresh_map_points* below.
  */
 #ifndef ORBX_LOCALMAP_H
 #define ORBX_LOCALMAP_H
@@ -157,6 +161,87 @@ orbx_status orbx_local_map_search_inputs_batch_device(
     const orbx_map_view* map, const uint8_t* d_mp_desc, int32_t nframes, const int32_t* d_local_mp,
     const int32_t* d_n_local_mp, int32_t cap_mp, const int32_t* d_mp_of_feat, int32_t feat_stride,
     const int32_t* d_nfeat, uint8_t* d_qdesc, uint8_t* d_claimed, void* stream);
+
+/* ---- MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:346-392) and
+ * MapPoint::ComputeDistinctiveDescriptors (:252-313) over the view: what local mapping writes
+ * after every change of a point's observations, and what the calls above read (mp_rec, d_mp_desc).
+ *
+ * The arrays the view lacks.  Device pointers for the *_device form, host pointers otherwise.
+ *   mp_obs_feat[n_obs]  parallel to mp_obs: the size_t of mObservations, the feature index in
+ *                       that keyframe
+ *   mp_ref_kf[n_mp]     mpRefKF as a slot
+ *   kf_pose[n_kf]       the keyframe's pose; Ow, nlevels and scale[] are read
+ *   kf_keys, kf_desc    mvKeysUn and mDescriptors (32 bytes per feature, 4-byte aligned), both
+ *                       indexed kf_mp_off[slot] + feature: an orbx_kf_db whose keyframe k is slot k
+ *                       passes its keys / desc as they are */
+typedef struct orbx_map_refresh_inputs {
+    const int32_t* mp_obs_feat;
+    const int32_t* mp_ref_kf;
+    const orbx_frame_pose* kf_pose;
+    const orbx_keypoint* kf_keys;
+    const uint8_t* kf_desc;
+} orbx_map_refresh_inputs;
+
+/* what */
+#define ORBX_REFRESH_NORMAL_DEPTH 1u
+#define ORBX_REFRESH_DESCRIPTOR 2u
+/* the longest observation row a call can take: ORBX_MAX_OBSERVATIONS of orbx_match.h */
+#define ORBX_REFRESH_MAX_OBS 256
+
+/* d_info[i] */
+#define ORBX_REFRESH_SKIPPED_BAD (1u << 0) /* mp_bad[id] (:354, :261): nothing written */
+#define ORBX_REFRESH_NO_OBS (1u << 1)      /* an empty row (:361, :266): nothing written */
+#define ORBX_REFRESH_DESC_KEPT (1u << 2)   /* every observing keyframe is bad (:279): the descriptor stays */
+#define ORBX_REFRESH_CAP_OBS (1u << 8)     /* refused: the row is longer than max_obs */
+#define ORBX_REFRESH_BAD_INDEX (1u << 10)  /* refused: an index read from the caller's arrays is out of range */
+#define ORBX_REFRESH_REFUSED_ANY (5u << 8)
+
+/* Refreshes the MapPoints d_ids[0..n), one wave each, in one launch on the caller's stream;
+ * allocates nothing (graph-capturable).  Of the view n_kf, n_mp, n_kfmp, n_obs, kf_order, kf_bad,
+ * kf_mp_off, mp_bad, mp_obs_off and mp_obs are read; its other pointers may be NULL.  An id may
+ * repeat: the call reads nothing that it writes.
+ *
+ * Per point: mp_bad[id] -> SKIPPED_BAD; an empty row -> NO_OBS; otherwise the row is walked in
+ * ascending kf_order of its keyframes, the order std::map<KeyFrame*, size_t> iterates it in (the
+ * kernel sorts it; rows of mp_obs stay in any order).
+ *   ORBX_REFRESH_NORMAL_DEPTH  d_mp_rec[id].normal / min_dist / max_dist (pos is read there and
+ *       never written; d_mp_rec may equal map->mp_rec).  Every keyframe of the row counts, bad or
+ *       not: normali = pos - Ow_i, normal += normali * (float)(1.0 / cv::norm(normali)) (the norm
+ *       kept in double; product and sum rounded separately), normal * (float)(1.0 / n) at the end
+ *       (a copy for n == 1).  max_dist = (float)cv::norm(pos - Ow_ref) * scale_ref[level],
+ *       min_dist = max_dist / scale_ref[nlevels_ref - 1], level the octave of the reference
+ *       keyframe's feature -- of its feature 0 when the reference keyframe is not in the row, as
+ *       std::map::operator[] on the copy yields.
+ *   ORBX_REFRESH_DESCRIPTOR    d_mp_desc[id*32 ..): of the descriptors of the row's keyframes that
+ *       are not bad, in that order, the first whose median distance vDists[(N-1)/2] to all of
+ *       them is least.  None left: nothing is written and DESC_KEPT is set.
+ *
+ * Refusals are per point, in d_info[i] alone; nothing of a refused point is written.  CAP_OBS: the
+ * row is longer than max_obs.  BAD_INDEX, whatever `what` asks for: an id outside [0, n_mp); a row
+ * whose offsets decrease or leave mp_obs; a slot (mp_ref_kf's too) or a kf_order rank outside
+ * [0, n_kf); two entries of a row with the same slot or rank; a feature index outside its
+ * keyframe's kf_mp_off row (index 0 of an empty reference keyframe too) or a kf_mp_off row that
+ * leaves [0, n_kfmp]; the reference keyframe's nlevels outside [1, 16] or its feature's octave
+ * outside [0, nlevels).  Every index is checked before it is used as an address.
+ *
+ * max_obs, in [1, ORBX_REFRESH_MAX_OBS], sizes the LDS of a wave and so the waves per workgroup.
+ * ORBX_ERR_INVALID: a NULL map, inputs or required pointer, a negative count, `what` without a
+ * bit or with an unknown one, max_obs out of range, kf_desc or d_mp_desc not 4-byte aligned.
+ * ORBX_ERR_UNSUPPORTED: n_kf > ORBX_LOCALMAP_MAX_KF.  n == 0: ORBX_OK, nothing launched.
+ * Without a GPU: ORBX_ERR_DEVICE. */
+orbx_status orbx_refresh_map_points_batch_device(const orbx_map_view* map,
+                                                 const orbx_map_refresh_inputs* in,
+                                                 const int32_t* d_ids, int32_t n, uint32_t what,
+                                                 int32_t max_obs, orbx_map_point* d_mp_rec,
+                                                 uint8_t* d_mp_desc, uint32_t* d_info, void* stream);
+
+/* Host arrays: mp_rec [n_mp] and mp_desc [n_mp*32] in/out, info [n] out; everything is copied to
+ * the device for the call.  The argument checks run before the device is touched (as above; a NULL
+ * array is accepted where its count is 0); without a GPU: ORBX_ERR_DEVICE. */
+orbx_status orbx_refresh_map_points(const orbx_map_view* map, const orbx_map_refresh_inputs* in,
+                                    const int32_t* ids, int32_t n, uint32_t what, int32_t max_obs,
+                                    orbx_map_point* mp_rec, uint8_t* mp_desc, uint32_t* info,
+                                    int device);
 
 #ifdef __cplusplus
 }

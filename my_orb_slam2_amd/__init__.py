@@ -18,6 +18,8 @@ Host-side mirror of the reference's operator interface for this path:
   ``pnp_correspondences_batch_device`` / ``pnp_apply_batch_device`` around it
 * ``LocalMapView`` / ``update_local_map`` / ``MonoTrackBatch.track_local_map`` —
   Tracking::UpdateLocalMap over a CSR snapshot of the map (src/Tracking.cc:1288-1442)
+* ``refresh_map_points`` / ``LocalMapView.set_refresh_inputs`` — MapPoint::UpdateNormalAndDepth and
+  MapPoint::ComputeDistinctiveDescriptors over the same snapshot (src/MapPoint.cc:252-392)
 * ``Vocabulary`` — ORBVocabulary / DBoW2 transform (Frame::ComputeBoW, src/Frame.cc:420-427)
 * ``KeyFrameDatabase`` — ORB_SLAM2::KeyFrameDatabase candidate detection (src/KeyFrameDatabase.cc)
 * ``MonoTrackBatch`` / ``RGBDTrackBatch`` — the batched monocular and RGB-D Frame front-ends
@@ -45,7 +47,8 @@ from .pnp import (PnPsolver, pnp_iterate, pnp_job, pnp_limits, pnp_ransac_parame
 from .sim3 import (OptimizeSim3, Sim3Solver, sim3_iterate, sim3_job, sim3_limits, sim3_optimize,
                    sim3_ransac_iterations, sim3_sample_triples, sim3opt_job, sim3opt_limits)
 from .localmap import (LocalMapView, local_map_search_inputs, map_arrays_from_lists,
-                       update_local_map, update_local_map_host)
+                       refresh_map_points, refresh_map_points_host, update_local_map,
+                       update_local_map_host)
 from .rectify import (Rectifier, RectifiedStereoBatch, init_undistort_rectify_map,
                       load_stereo_settings, remap_fixed_point, remap_stereo_batch_device)
 
@@ -62,4 +65,4 @@ __all__ = ["ORBextractor", "ORBmatcher", "compute_stereo_matches", "compute_ster
            "sim3_optimize", "sim3opt_job", "sim3opt_limits", "PnPsolver", "pnp_iterate", "pnp_job",
            "pnp_limits", "pnp_ransac_parameters", "pnp_sample_quads", "pnp_window", "LocalMapView",
            "local_map_search_inputs", "map_arrays_from_lists", "update_local_map",
-           "update_local_map_host"]
+           "update_local_map_host", "refresh_map_points", "refresh_map_points_host"]

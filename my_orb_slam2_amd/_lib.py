@@ -81,6 +81,12 @@ class MapViewC(ctypes.Structure):
                                                 "mp_rec")])
 
 
+class MapRefreshC(ctypes.Structure):
+    """orbx_map_refresh_inputs (include/orbx_localmap.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mp_obs_feat", "mp_ref_kf", "kf_pose", "kf_keys",
+                                               "kf_desc")]
+
+
 # name -> (restype, argtypes); the exported C ABI (include/orbx.h)
 _vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SIGNATURES = {
@@ -257,6 +263,11 @@ SIGNATURES = {
     "orbx_update_local_map_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "orbx_update_local_map": (_i, [ctypes.POINTER(MapViewC), _vp, _i, _vp, _i, _i, _vp, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "orbx_refresh_map_points_batch_device": (_i, [ctypes.POINTER(MapViewC),
+                                                  ctypes.POINTER(MapRefreshC), _vp, _i,
+                                                  ctypes.c_uint32, _i, _vp, _vp, _vp, _vp]),
+    "orbx_refresh_map_points": (_i, [ctypes.POINTER(MapViewC), ctypes.POINTER(MapRefreshC), _vp, _i,
+                                     ctypes.c_uint32, _i, _vp, _vp, _vp, _i]),
 }
 
 _lib = None

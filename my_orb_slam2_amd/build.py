@@ -29,7 +29,7 @@ SOURCES = ["orbx_pyramid.hip", "orbx_extract.hip", "orbx_stereo.hip", "orbx_matc
 HEADERS = ["orbx_internal.h", "orbx_device.h", "orbx_math.h", "orbx_hypot.h", "orbx_kernels.h",
            "orbx_host.h", "orbx_stage.h", "orbx_layout.h", "orbx_extractor.h", "orbx_lm.h",
            "orbx_match_kernels.h", "orbx_matcher.h", "orbx_ransac.h", "orbx_fast_pretest.h",
-           "orbx_pattern.inc", "orbx_cv.h",
+           "orbx_pattern.inc", "orbx_cv.h", "orbx_distinctive.h",
            "../../include/orbx.h", "../../include/orbx_match.h", "../../include/orbx_vocab.h",
            "../../include/orbx_frame.h", "../../include/orbx_kfdb.h",
            "../../include/orbx_localmap.h"]
@@ -316,6 +316,19 @@ def build_localmap_ref(force: bool = False, verbose: bool = False) -> pathlib.Pa
     """g++ on the standard library only: no liborbx and no GPU (the CPU reference of
     orbx_update_local_map*)."""
     return _build_native(LOCALMAP_REF_SRC, LOCALMAP_REF_BIN, [], [], flags=("-Wextra",),
+                         force=force, verbose=verbose)
+
+
+# UpdateNormalAndDepth / ComputeDistinctiveDescriptors restated over stand-in objects and the cv
+# stand-in
+MPREFRESH_REF_SRC = NATIVE / "mprefresh_ref.cpp"
+MPREFRESH_REF_BIN = NATIVE / "mprefresh_ref"
+
+
+def build_mprefresh_ref(force: bool = False, verbose: bool = False) -> pathlib.Path:
+    """g++ on the cv stand-in and the standard library only: no liborbx and no GPU (the CPU
+    reference of orbx_refresh_map_points*)."""
+    return _build_native(MPREFRESH_REF_SRC, MPREFRESH_REF_BIN, _headers(CV_STANDIN), [CV_STANDIN],
                          force=force, verbose=verbose)
 
 

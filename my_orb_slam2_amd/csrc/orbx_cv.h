@@ -1,6 +1,6 @@
 // orbx_cv.h — the small arithmetic forms of OpenCV 3.2 that the geometry kernels restate, once
 // (orbx_frame.hip, orbx_triangulate.hip, orbx_sim3.hip, orbx_sim3opt.hip, orbx_poseopt.hip,
-// orbx_pnp.hip), and the exactly rounded one-line wrappers they and orbx_lm.h / orbx_hypot.h are
+// orbx_pnp.hip, orbx_localmap.hip), and the exactly rounded one-line wrappers they and orbx_lm.h / orbx_hypot.h are
 // written with.  Device code.  Every form is restated from the library's sources and PARITY
 // UNPINNED [unverified-OpenCV]: one found wrong against the real library is fixed
 // here.  The x86 integer conversions (x86_trunc, cv_round) are orbx_math.h's, which host code
@@ -67,13 +67,14 @@ __device__ __forceinline__ void gemm3t(const float* R, const float* c, float* ou
 
 // ---- cv::norm, Mat::dot, Mat::convertTo ---------------------------------------------------------
 // (float)cv::norm(a), NORM_L2 on CV_32F: squares accumulated in double (normL2Sqr<float,
-// double>), sqrt, stored in a float
-__device__ __forceinline__ float norm3(const float* a) {
+// double>), sqrt, stored in a float; norm3d is the double cv::norm returns
+__device__ __forceinline__ double norm3d(const float* a) {
     double ss = 0.0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) ss = da(ss, dm((double)a[k], (double)a[k]));
-    return (float)sq(ss);
+    return sq(ss);
 }
+__device__ __forceinline__ float norm3(const float* a) { return (float)norm3d(a); }
 
 // a.dot(b) of two CV_32F 3-vectors: Mat::dot in double (dotProd_<float, double>; below four
 // elements there is no 4-at-a-time step)
@@ -90,6 +91,15 @@ __device__ __forceinline__ float cvt_scale(float x, double alpha) {
     if (fabs(ds(alpha, 1.0)) < 2.220446049250313e-16) return x;
     return fa(fm(x, (float)alpha), 0.0f);
 }
+
+// b + a / s for CV_32F a, b and a double s: MatOp_AddEx::add folds the scaled operand into
+// cv::scaleAdd(a, 1. / s, b) (matop.cpp), whose CV_32F kernel takes alpha as a float and computes
+// a * alpha + b with the product and the sum rounded on their own (scaleAdd_32f, matmul.cpp).
+// scale_add_alpha is (float)(1. / s); one element is scale_add_sum(scale_add_term(a, alpha), b),
+// in two steps for k_refresh_map_points, which takes the products of a sum's terms in parallel.
+__device__ __forceinline__ float scale_add_alpha(double s) { return (float)dv(1.0, s); }
+__device__ __forceinline__ float scale_add_term(float a, float alpha) { return fm(a, alpha); }
+__device__ __forceinline__ float scale_add_sum(float term, float b) { return fa(term, b); }
 
 // ---- the pinhole, PredictScale, UnprojectStereo, the camera centre -------------------------------
 // One image coordinate from a camera-frame coordinate X and invz = 1 / z.  Frame's loops write

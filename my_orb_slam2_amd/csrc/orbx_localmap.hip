@@ -19,6 +19,9 @@
 //              listed keyframe holds is first seen there: the extras, in feature order.
 // Every index read from the caller's arrays is range-checked before it addresses anything; nothing
 // of a refused frame is written but its info word, so every output is written after the last check.
+//
+// k_refresh_map_points (further down): MapPoint::UpdateNormalAndDepth and
+// ComputeDistinctiveDescriptors over the same snapshot, one wave per MapPoint.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -26,6 +29,10 @@
 #include <cstring>
 
 #include "../../include/orbx_localmap.h"
+#include "../../include/orbx_match.h"
+#include "orbx_cv.h"
+#include "orbx_device.h"
+#include "orbx_distinctive.h"
 #include "orbx_host.h"
 
 using namespace orbx;
@@ -535,6 +542,225 @@ __global__ __launch_bounds__(256) void k_local_map_claimed(
     }
 }
 
+// ---- k_refresh_map_points: MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:346-392) and
+// MapPoint::ComputeDistinctiveDescriptors (:252-313), one wave per MapPoint ---------------------------
+//   order      the row's keys (kf_order rank << 8 | position in the row) are sorted by a bitonic
+//              network in LDS: the order std::map<KeyFrame*, size_t> iterates the observations in
+//   normal     lane per observation: normali = pos - Ow_i, its double norm, the scaleAdd products
+//              into LDS; lanes 0..2 add them in that order, one component each
+//   depth      the reference keyframe's feature (feature 0 when it is not in the row)
+//   descriptor the descriptors of the keyframes that are not bad, gathered in that order straight
+//              into LDS, then distinctive_best (orbx_distinctive.h)
+// The waves of a workgroup share nothing and meet at no barrier.  Every index is checked before it
+// addresses anything and every check precedes the first write.
+constexpr int RF_MAX_WAVES = 4;
+constexpr size_t RF_MAX_LDS = 64 * 1024;      // the default dynamic LDS limit: no attribute call
+static_assert(ORBX_REFRESH_MAX_OBS == ORBX_MAX_OBSERVATIONS, "one limit on the observation row");
+
+struct RefreshLaunch {
+    orbx_map_view m;
+    orbx_map_refresh_inputs in;
+    const int32_t* ids;
+    int32_t n;
+    uint32_t what;
+    int32_t max_obs;
+    orbx_map_point* rec;
+    uint32_t* desc;
+    uint32_t* info;
+};
+
+// One wave's dynamic LDS in 4-byte words from its base: the sort keys (a power of two), the normal
+// terms, the descriptors, 64 u16 distance rows of max_obs + 1.
+struct RefreshCarve {
+    int keys = 0, terms, desc, rows, row_stride, words;
+    __host__ __device__ explicit RefreshCarve(int max_obs) {
+        int p = 1;
+        while (p < max_obs) p <<= 1;
+        terms = p;
+        desc = terms + 3 * max_obs;
+        rows = desc + 8 * max_obs;
+        row_stride = max_obs + 1;
+        words = rows + 32 * row_stride;
+    }
+};
+
+// LDS written by some lanes of the wave, read by others
+__device__ __forceinline__ void rf_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(64 * RF_MAX_WAVES) void k_refresh_map_points(const RefreshLaunch a) {
+    extern __shared__ uint32_t rf_lds[];
+    const orbx_map_view& m = a.m;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = (int)blockIdx.x * (int)(blockDim.x >> 6) + wave;
+    if (i >= a.n) return;
+    const RefreshCarve carve(a.max_obs);
+    uint32_t* const base = rf_lds + (size_t)wave * carve.words;
+    uint32_t* const keys = base + carve.keys;
+    float* const terms = (float*)(base + carve.terms);
+    uint32_t* const dl = base + carve.desc;
+    uint16_t* const rows = (uint16_t*)(base + carve.rows);
+    const int n_kf = m.n_kf;
+
+#define RF_DONE(word)                      \
+    {                                      \
+        if (lane == 0) a.info[i] = (word); \
+        return;                            \
+    }
+    // everything up to the sort is the same in every lane but `bad`
+    const int id = a.ids[i];
+    if ((uint32_t)id >= (uint32_t)m.n_mp) RF_DONE(ORBX_REFRESH_BAD_INDEX)
+    if (m.mp_bad[id]) RF_DONE(ORBX_REFRESH_SKIPPED_BAD)                     // :354, :261
+    int b, e;
+    if (!lm_row(m.mp_obs_off, id, m.n_obs, b, e)) RF_DONE(ORBX_REFRESH_BAD_INDEX)
+    const int N = e - b;
+    if (N == 0) RF_DONE(ORBX_REFRESH_NO_OBS)                                // :361, :266
+    if (N > a.max_obs) RF_DONE(ORBX_REFRESH_CAP_OBS)
+
+    // ---- the row's keys, every entry checked ------------------------------------------------------
+    int P = 1;
+    while (P < N) P <<= 1;
+    bool bad = false;
+    for (int t = lane; t < P; t += 64) {
+        uint32_t key = 0xffffffffu;
+        if (t < N) {
+            const int s = m.mp_obs[b + t];
+            if ((uint32_t)s >= (uint32_t)n_kf) {
+                bad = true;
+            } else {
+                const int r = m.kf_order[s];
+                if ((uint32_t)r >= (uint32_t)n_kf) bad = true;
+                else key = (uint32_t)r << 8 | (uint32_t)t;
+                int fb, fe;
+                if (!lm_row(m.kf_mp_off, s, m.n_kfmp, fb, fe) ||
+                    (uint32_t)a.in.mp_obs_feat[b + t] >= (uint32_t)(fe - fb))
+                    bad = true;
+            }
+        }
+        keys[t] = key;
+    }
+    if (__ballot(bad)) RF_DONE(ORBX_REFRESH_BAD_INDEX)
+    rf_wave_sync();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = lane; t < P; t += 64) {
+                const int u = t ^ j;
+                if (u > t) {
+                    const uint32_t x = keys[t], y = keys[u];
+                    if ((x > y) == ((t & k) == 0)) keys[t] = y, keys[u] = x;
+                }
+            }
+            rf_wave_sync();
+        }
+
+    // ---- no keyframe twice; the reference keyframe's feature ----------------------------------------
+    const int ref = a.in.mp_ref_kf[id];
+    if ((uint32_t)ref >= (uint32_t)n_kf) RF_DONE(ORBX_REFRESH_BAD_INDEX)
+    int mine = -1;
+    for (int t = lane; t < N; t += 64) {
+        const uint32_t key = keys[t];
+        if (t + 1 < N && (keys[t + 1] >> 8) == (key >> 8)) bad = true;
+        const int o = b + (int)(key & 255u);
+        if (m.mp_obs[o] == ref) mine = a.in.mp_obs_feat[o];
+    }
+    const uint64_t holds = __ballot(mine >= 0);
+    // observations[pRefKF] on the copy (:377): a keyframe that is not there gets index 0
+    const int ref_feat = holds ? __shfl(mine, __ffsll((unsigned long long)holds) - 1) : 0;
+    int rb, re;
+    if (!lm_row(m.kf_mp_off, ref, m.n_kfmp, rb, re) || ref_feat >= re - rb) bad = true;
+    const int nlevels = a.in.kf_pose[ref].nlevels;
+    if (nlevels < 1 || nlevels > 16) bad = true;
+    int level = 0;
+    if (!bad) {
+        level = a.in.kf_keys[rb + ref_feat].octave;
+        if (level < 0 || level >= nlevels) bad = true;
+    }
+    if (__ballot(bad)) RF_DONE(ORBX_REFRESH_BAD_INDEX)
+
+    // ---- UpdateNormalAndDepth (:364-390): bad keyframes count -----------------------------------------
+    if (a.what & ORBX_REFRESH_NORMAL_DEPTH) {
+        const float pos[3] = {a.rec[id].pos[0], a.rec[id].pos[1], a.rec[id].pos[2]};
+        for (int t = lane; t < N; t += 64) {
+            const float* Ow = a.in.kf_pose[m.mp_obs[b + (int)(keys[t] & 255u)]].Ow;
+            const float d[3] = {fs(pos[0], Ow[0]), fs(pos[1], Ow[1]), fs(pos[2], Ow[2])};
+            const float alpha = scale_add_alpha(norm3d(d));
+#pragma unroll
+            for (int k = 0; k < 3; ++k) terms[3 * t + k] = scale_add_term(d[k], alpha);
+        }
+        rf_wave_sync();
+        const orbx_frame_pose& R = a.in.kf_pose[ref];
+        const float pc[3] = {fs(pos[0], R.Ow[0]), fs(pos[1], R.Ow[1]), fs(pos[2], R.Ow[2])};
+        const float max_dist = fm(norm3(pc), R.scale[level]);
+        const float min_dist = fdiv(max_dist, R.scale[nlevels - 1]);
+        if (lane < 3) {
+            float acc = 0.0f;
+            for (int t = 0; t < N; ++t) acc = scale_add_sum(terms[3 * t + lane], acc);
+            a.rec[id].normal[lane] = cvt_scale(acc, dv(1.0, (double)N));
+        }
+        if (lane == 0) {
+            a.rec[id].min_dist = min_dist;
+            a.rec[id].max_dist = max_dist;
+        }
+    }
+
+    // ---- ComputeDistinctiveDescriptors (:271-317): bad keyframes are skipped --------------------------
+    uint32_t word = 0;
+    if (a.what & ORBX_REFRESH_DESCRIPTOR) {
+        int M = 0;
+        for (int t0 = 0; t0 < N; t0 += 64) {
+            const int t = t0 + lane;
+            bool good = false;
+            long long src = 0;
+            if (t < N) {
+                const int o = b + (int)(keys[t] & 255u);
+                const int s = m.mp_obs[o];
+                good = !m.kf_bad[s];
+                src = (long long)m.kf_mp_off[s] + a.in.mp_obs_feat[o];
+            }
+            const uint64_t mask = __ballot(good);
+            if (good) {
+                const int j = M + lanes_below(mask);
+                const uint32_t* sp = (const uint32_t*)a.in.kf_desc + 8 * src;
+#pragma unroll
+                for (int w = 0; w < 8; ++w) dl[8 * j + w] = sp[w];
+            }
+            M += __popcll(mask);
+        }
+        rf_wave_sync();
+        if (M == 0) {
+            word = ORBX_REFRESH_DESC_KEPT;                                  // :279
+        } else {
+            const int best = distinctive_best(dl, rows, carve.row_stride, M);
+            if (lane < 8) a.desc[(size_t)id * 8 + lane] = dl[best * 8 + lane];
+        }
+    }
+    if (lane == 0) a.info[i] = word;
+#undef RF_DONE
+}
+
+// The launch geometry of a max_obs: as many waves per workgroup as RF_MAX_LDS holds, RF_MAX_WAVES
+// at the most.
+struct RefreshGeometry { int waves; size_t lds; };
+RefreshGeometry refresh_geometry(int max_obs) {
+    const size_t per = 4 * (size_t)RefreshCarve(max_obs).words;
+    int waves = (int)(RF_MAX_LDS / per);
+    waves = waves < 1 ? 1 : waves > RF_MAX_WAVES ? RF_MAX_WAVES : waves;
+    return {waves, per * (size_t)waves};
+}
+
+orbx_status rf_check_counts(const orbx_map_view* map, const orbx_map_refresh_inputs* in, int32_t n,
+                            uint32_t what, int32_t max_obs) {
+    if (!map || !in || n < 0 || map->n_kf < 0 || map->n_mp < 0 || map->n_kfmp < 0 ||
+        map->n_obs < 0 || !what || (what & ~(ORBX_REFRESH_NORMAL_DEPTH | ORBX_REFRESH_DESCRIPTOR)) ||
+        max_obs < 1 || max_obs > ORBX_REFRESH_MAX_OBS)
+        return ORBX_ERR_INVALID;
+    if (map->n_kf > ORBX_LOCALMAP_MAX_KF) return ORBX_ERR_UNSUPPORTED;
+    return ORBX_OK;
+}
+
 // The checks both forms share, on the counts alone.
 orbx_status lm_check_counts(const orbx_map_view* map, int32_t nframes, int32_t feat_stride,
                             int32_t cap_kf, int32_t cap_mp) {
@@ -668,6 +894,72 @@ orbx_status orbx_update_local_map(const orbx_map_view* map, const int32_t* feat_
         c.dev<int32_t>(p_lmp), c.dev<int32_t>(p_nlmp), c.dev<orbx_map_point>(p_mps),
         c.dev<uint8_t>(p_skip), c.dev<int32_t>(p_mpf), c.dev<uint32_t>(p_info),
         c.dev<uint8_t>(p_scr), scratch_bytes ? scratch_bytes : 4, c.st()));
+}
+
+orbx_status orbx_refresh_map_points_batch_device(const orbx_map_view* map,
+                                                 const orbx_map_refresh_inputs* in,
+                                                 const int32_t* d_ids, int32_t n, uint32_t what,
+                                                 int32_t max_obs, orbx_map_point* d_mp_rec,
+                                                 uint8_t* d_mp_desc, uint32_t* d_info, void* stream) {
+    const orbx_status counts = rf_check_counts(map, in, n, what, max_obs);
+    if (counts != ORBX_OK) return counts;
+    if (n == 0) return ORBX_OK;
+    if (!map->kf_order || !map->kf_bad || !map->kf_mp_off || !map->mp_bad || !map->mp_obs_off ||
+        !map->mp_obs || !in->mp_obs_feat || !in->mp_ref_kf || !in->kf_pose || !in->kf_keys ||
+        !in->kf_desc || !d_ids || !d_mp_rec || !d_mp_desc || !d_info ||
+        ((uintptr_t)in->kf_desc & 3) || ((uintptr_t)d_mp_desc & 3))
+        return ORBX_ERR_INVALID;
+    int ndev = 0;
+    if (!HIPOK(hipGetDeviceCount(&ndev)) || ndev < 1) return ORBX_ERR_DEVICE;
+    const RefreshLaunch L{*map, *in, d_ids, n, what, max_obs, d_mp_rec, (uint32_t*)d_mp_desc, d_info};
+    const RefreshGeometry g = refresh_geometry(max_obs);
+    hipLaunchKernelGGL(k_refresh_map_points, dim3((unsigned)((n + g.waves - 1) / g.waves)),
+                       dim3(64 * g.waves), g.lds, (hipStream_t)stream, L);
+    return HIPOK(hipGetLastError()) ? ORBX_OK : ORBX_ERR_DEVICE;
+}
+
+orbx_status orbx_refresh_map_points(const orbx_map_view* map, const orbx_map_refresh_inputs* in,
+                                    const int32_t* ids, int32_t n, uint32_t what, int32_t max_obs,
+                                    orbx_map_point* mp_rec, uint8_t* mp_desc, uint32_t* info,
+                                    int device) {
+    const orbx_status counts = rf_check_counts(map, in, n, what, max_obs);
+    if (counts != ORBX_OK) return counts;
+    const orbx_map_view& m = *map;
+    if ((n > 0 && (!ids || !info)) || !m.kf_mp_off || !m.mp_obs_off ||
+        (m.n_kf > 0 && (!m.kf_order || !m.kf_bad || !in->kf_pose)) ||
+        (m.n_mp > 0 && (!m.mp_bad || !in->mp_ref_kf || !mp_rec || !mp_desc)) ||
+        (m.n_obs > 0 && (!m.mp_obs || !in->mp_obs_feat)) ||
+        (m.n_kfmp > 0 && (!in->kf_keys || !in->kf_desc)))
+        return ORBX_ERR_INVALID;
+    if (n == 0) return ORBX_OK;
+    HostCall c(device);
+    if (!c.ok()) return ORBX_ERR_DEVICE;
+    StagePlan& p = c.plan();
+    const size_t kf = (size_t)m.n_kf, mp = (size_t)m.n_mp, obs = (size_t)m.n_obs,
+                 feat = (size_t)m.n_kfmp;
+    // an absent array of no entries still needs an address: 4 bytes of zeros
+    auto arr = [&](const void* src, size_t bytes) { return p.in(bytes ? src : nullptr, bytes ? bytes : 4); };
+    const size_t p_order = arr(m.kf_order, 4 * kf), p_kbad = arr(m.kf_bad, kf),
+                 p_mpo = p.in(m.kf_mp_off, 4 * (kf + 1)), p_mbad = arr(m.mp_bad, mp),
+                 p_obso = p.in(m.mp_obs_off, 4 * (mp + 1)), p_obs = arr(m.mp_obs, 4 * obs),
+                 p_ofeat = arr(in->mp_obs_feat, 4 * obs), p_ref = arr(in->mp_ref_kf, 4 * mp),
+                 p_pose = arr(in->kf_pose, sizeof(orbx_frame_pose) * kf),
+                 p_keys = arr(in->kf_keys, sizeof(orbx_keypoint) * feat),
+                 p_kdesc = arr(in->kf_desc, 32 * feat), p_ids = p.in(ids, 4 * (size_t)n);
+    auto io = [&](void* q, size_t bytes) { return bytes ? p.inout(q, bytes) : p.in(nullptr, 4); };
+    const size_t p_rec = io(mp_rec, sizeof(orbx_map_point) * mp), p_desc = io(mp_desc, 32 * mp),
+                 p_info = p.inout(info, 4 * (size_t)n);
+    if (!c.upload()) return c.finish(ORBX_ERR_DEVICE);
+    orbx_map_view d = m;
+    d.kf_order = c.dev<int32_t>(p_order), d.kf_bad = c.dev<uint8_t>(p_kbad);
+    d.kf_mp_off = c.dev<int32_t>(p_mpo), d.mp_bad = c.dev<uint8_t>(p_mbad);
+    d.mp_obs_off = c.dev<int32_t>(p_obso), d.mp_obs = c.dev<int32_t>(p_obs);
+    const orbx_map_refresh_inputs di{c.dev<int32_t>(p_ofeat), c.dev<int32_t>(p_ref),
+                                     c.dev<orbx_frame_pose>(p_pose), c.dev<orbx_keypoint>(p_keys),
+                                     c.dev<uint8_t>(p_kdesc)};
+    return c.finish(orbx_refresh_map_points_batch_device(
+        &d, &di, c.dev<int32_t>(p_ids), n, what, max_obs, c.dev<orbx_map_point>(p_rec),
+        c.dev<uint8_t>(p_desc), c.dev<uint32_t>(p_info), c.st()));
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@
 #include <climits>
 
 #include "orbx_device.h"
+#include "orbx_distinctive.h"
 #include "orbx_kernels.h"
 #include "orbx_match_kernels.h"
 #include "orbx_math.h"
@@ -35,22 +36,11 @@ namespace {
 constexpr int TH_HIGH = 100, TH_LOW = 50, HISTO = 30;
 constexpr uint32_t INF = 0xFFFFFFFFu;
 
-struct Desc {
-    uint32_t w[8];
-};
-
+// Desc, hamming and wave_min_u32 are orbx_distinctive.h's
 __device__ __forceinline__ Desc load_desc(const uint8_t* base, long long i) {
     const uint4* p = (const uint4*)(base + 32 * i);
     const uint4 a = p[0], b = p[1];
     return Desc{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w}};
-}
-
-// ORBmatcher::DescriptorDistance (:1715-1731): popcount of the XOR, 8 words, as a chain
-// of accumulating v_bcnt_u32_b32 (the compiler otherwise sums 8 counts with 3 v_add3).
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t x, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(acc));
-    return r;
 }
 
 // median of three (one v_med3_u32; a 2-input v_min / v_max costs the same issue slot)
@@ -58,27 +48,6 @@ __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
     uint32_t r;
     asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-}
-
-__device__ __forceinline__ int hamming(const Desc& a, const Desc& b) {
-    uint32_t d = __popc(a.w[0] ^ b.w[0]);
-#pragma unroll
-    for (int k = 1; k < 8; ++k) d = bcnt_acc(a.w[k] ^ b.w[k], d);
-    return (int)d;
-}
-
-// Wave-wide unsigned min, uniform result: DPP within rows of 16, then 4 readlanes.
-// Must be called with all 64 lanes active.
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0xB1, 0xF, 0xF, true));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x4E, 0xF, 0xF, true));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x124, 0xF, 0xF, true));
-    v = min(v, (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x128, 0xF, 0xF, true));
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32);
-    const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
-    return min(min(a, b), min(c, d));
 }
 
 // Rotation bin of the matchers (e.g. :269-275): float difference, +360 when negative,
@@ -1006,10 +975,8 @@ __global__ __launch_bounds__(256) void k_proj_finish(ProjLaunch g) {
 // ---------------------------------------------------------------------------------------
 // MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:252-313)
 // ---------------------------------------------------------------------------------------
-// One wave per map point: its N descriptors are staged in LDS, lane i computes row i of the
-// distance matrix into LDS (u16), finds the row's median vDists[(N-1)/2] by a binary search
-// over distance values (9 counting passes), and a wave-min over (median << 16 | i) keeps the
-// first row with the least median.
+// One wave per map point: its N descriptors are staged in LDS and distinctive_best
+// (orbx_distinctive.h) picks the first row with the least median.
 __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ desc,
                                                     const int32_t* __restrict__ off, int np,
                                                     int32_t* __restrict__ best, int* err) {
@@ -1029,33 +996,8 @@ __global__ __launch_bounds__(64) void k_distinctive(const uint8_t* __restrict__ 
     for (int t = lane; t < N * 8; t += 64)
         dl[t] = ((const uint32_t*)(desc + 32 * (size_t)o0))[t];
     __syncthreads();
-    const int k = (N - 1) >> 1;   // vDists[0.5*(N-1)]
-    uint32_t bestkey = INF;
-    uint16_t* row = rows + lane * (MAXN + 1);
-    for (int i0 = 0; i0 < N; i0 += 64) {
-        const int i = i0 + lane;
-        const bool has = i < N;
-        const int ic = has ? i : N - 1;
-        Desc di;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) di.w[w] = dl[ic * 8 + w];
-        for (int j = 0; j < N; ++j) {
-            Desc dj;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) dj.w[w] = dl[j * 8 + w];
-            row[j] = (uint16_t)hamming(di, dj);
-        }
-        int lo = 0, hi = 256;   // smallest v with #(row <= v) >= k + 1
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            int cnt = 0;
-            for (int j = 0; j < N; ++j) cnt += row[j] <= mid;
-            if (cnt >= k + 1) hi = mid; else lo = mid + 1;
-        }
-        const uint32_t key = has ? ((uint32_t)lo << 16 | (uint32_t)i) : INF;
-        bestkey = min(bestkey, wave_min_u32(key));
-    }
-    if (lane == 0) best[p] = (int)(bestkey & 0xFFFFu);
+    const int b = distinctive_best(dl, rows, MAXN + 1, N);
+    if (lane == 0) best[p] = b;
 }
 
 }  // namespace

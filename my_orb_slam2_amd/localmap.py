@@ -13,8 +13,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import MapViewC, check, load, ptr
-from .features import MAP_POINT_DTYPE
+from ._lib import KEYPOINT_DTYPE, MapRefreshC, MapViewC, check, load, ptr
+from .features import FRAME_POSE_DTYPE, MAP_POINT_DTYPE
 
 # d_info bits (include/orbx_localmap.h)
 LOCALMAP_KEPT = 1 << 0
@@ -31,6 +31,21 @@ _ARRAYS = (("kf_order", np.int32), ("kf_bad", np.uint8), ("kf_parent", np.int32)
            ("kf_child", np.int32), ("kf_mp_off", np.int32), ("kf_mp", np.int32),
            ("mp_bad", np.uint8), ("mp_obs_off", np.int32), ("mp_obs", np.int32),
            ("mp_rec", MAP_POINT_DTYPE))
+# the arrays of orbx_map_refresh_inputs
+_REFRESH_ARRAYS = (("mp_obs_feat", np.int32), ("mp_ref_kf", np.int32), ("kf_pose", FRAME_POSE_DTYPE),
+                   ("kf_keys", KEYPOINT_DTYPE), ("kf_desc", np.uint8))
+# what (include/orbx_localmap.h)
+REFRESH_NORMAL_DEPTH = 1
+REFRESH_DESCRIPTOR = 2
+REFRESH_MAX_OBS = 256
+# d_info of refresh_map_points
+REFRESH_SKIPPED_BAD = 1 << 0
+REFRESH_NO_OBS = 1 << 1
+REFRESH_DESC_KEPT = 1 << 2
+REFRESH_CAP_OBS = 1 << 8
+REFRESH_BAD_INDEX = 1 << 10
+REFRESH_REFUSED_ANY = 5 << 8
+
 _COUNTS = (("n_kf", "kf_order"), ("n_mp", "mp_bad"), ("n_cov", "kf_cov"), ("n_child", "kf_child"),
            ("n_kfmp", "kf_mp"), ("n_obs", "mp_obs"))
 
@@ -116,6 +131,7 @@ class LocalMapView:
         self.c = c
         self.n_kf, self.n_mp = n["n_kf"], n["n_mp"]
         self._scratch = None
+        self.refresh_t, self.refresh_c = None, None      # set_refresh_inputs
 
     @classmethod
     def from_lists(cls, kf_order, kf_bad, kf_parent, kf_cov, kf_child, kf_mp, mp_bad, mp_obs,
@@ -134,6 +150,33 @@ class LocalMapView:
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.dev)
         return self._scratch
+
+
+    def set_refresh_inputs(self, arrays: dict):
+        """The arrays ``refresh_map_points`` reads next to the view (orbx_map_refresh_inputs):
+        mp_obs_feat [n_obs] and mp_ref_kf [n_mp] int32, kf_pose [n_kf] FRAME_POSE_DTYPE, kf_keys
+        [n_kfmp] KEYPOINT_DTYPE, kf_desc [n_kfmp, 32] uint8 -- numpy arrays (uploaded) or device
+        tensors (used as they are: int32 / bytes).  Returns self."""
+        import torch
+        n_obs, n_kfmp = len(self.t["mp_obs"]), len(self.t["kf_mp"])
+        want = {"mp_obs_feat": 4 * n_obs, "mp_ref_kf": 4 * self.n_mp,
+                "kf_pose": FRAME_POSE_DTYPE.itemsize * self.n_kf,
+                "kf_keys": KEYPOINT_DTYPE.itemsize * n_kfmp, "kf_desc": 32 * n_kfmp}
+        c, held = MapRefreshC(), {}
+        for name, dt in _REFRESH_ARRAYS:
+            a = arrays[name]
+            if isinstance(a, np.ndarray):
+                raw = np.ascontiguousarray(a, dt).reshape(-1).view(np.uint8)
+                a = torch.from_numpy(raw.copy()).to(self.dev)
+            elif not a.is_contiguous():
+                raise ValueError(f"{name}: a contiguous tensor is expected")
+            if a.numel() * a.element_size() != want[name]:
+                raise ValueError(f"{name} holds {a.numel() * a.element_size()} bytes, expected "
+                                 f"{want[name]}")
+            held[name] = a
+            setattr(c, name, a.data_ptr() if a.numel() else self._pad.data_ptr())
+        self.refresh_t, self.refresh_c = held, c
+        return self
 
 
 def update_local_map(view: LocalMapView, nframes: int, d_feat_mp, feat_stride: int, d_nfeat,
@@ -165,6 +208,53 @@ def local_map_search_inputs(view: LocalMapView, d_mp_desc, nframes: int, d_local
               ctypes.byref(view.c), ptr(d_mp_desc), int(nframes), ptr(d_local_mp),
               ptr(d_n_local_mp), int(cap_mp), ptr(d_mp_of_feat), int(feat_stride), ptr(d_nfeat),
               ptr(d_qdesc), ptr(d_claimed), ctypes.c_void_p(stream)))
+
+
+def refresh_map_points(view: LocalMapView, d_ids, what: int, max_obs: int, d_mp_desc, d_info,
+                       d_mp_rec=None, n: int | None = None, stream: int = 0):
+    """orbx_refresh_map_points_batch_device on device tensors: MapPoint::UpdateNormalAndDepth
+    (REFRESH_NORMAL_DEPTH) and / or ComputeDistinctiveDescriptors (REFRESH_DESCRIPTOR) of the
+    MapPoints d_ids [n] int32, in place: normal / min_dist / max_dist of d_mp_rec (the view's own
+    mp_rec when None), d_mp_desc [n_mp, 32], and the REFRESH_* words d_info [n].  max_obs: no row
+    of the ids is longer (a longer one is refused with REFRESH_CAP_OBS).  The view holds the extra
+    arrays (``LocalMapView.set_refresh_inputs``)."""
+    if view.refresh_c is None:
+        raise ValueError("LocalMapView.set_refresh_inputs has not been called")
+    rec = view.t["mp_rec"] if d_mp_rec is None else d_mp_rec
+    check("orbx_refresh_map_points_batch_device", load().orbx_refresh_map_points_batch_device(
+        ctypes.byref(view.c), ctypes.byref(view.refresh_c), ptr(d_ids),
+        int(len(d_ids) if n is None else n), int(what), int(max_obs), ptr(rec), ptr(d_mp_desc),
+        ptr(d_info), ctypes.c_void_p(stream)))
+
+
+def refresh_map_points_host(arrays: dict, extra: dict, ids, what: int, max_obs: int, mp_desc,
+                            device: int = 0) -> dict:
+    """orbx_refresh_map_points: host arrays (``arrays`` as ``map_arrays_from_lists`` gives them,
+    ``extra`` the arrays of ``LocalMapView.set_refresh_inputs``, mp_desc [n_mp, 32]).  Returns
+    info [n], and copies of mp_rec and mp_desc as the call left them."""
+    keep = {n: np.ascontiguousarray(arrays[n], dt) for n, dt in _ARRAYS}
+    ex = {n: np.ascontiguousarray(extra[n], dt) for n, dt in _REFRESH_ARRAYS}
+    c, r = MapViewC(), MapRefreshC()
+    for k, v in _counts(keep).items():
+        setattr(c, k, v)
+    for n, _ in _ARRAYS:
+        setattr(c, n, keep[n].ctypes.data if len(keep[n]) else None)
+    for n, _ in _REFRESH_ARRAYS:
+        setattr(r, n, ex[n].ctypes.data if ex[n].size else None)
+    if (len(ex["mp_obs_feat"]), len(ex["mp_ref_kf"]), len(ex["kf_pose"]), len(ex["kf_keys"]),
+            ex["kf_desc"].size) != (c.n_obs, c.n_mp, c.n_kf, c.n_kfmp, 32 * c.n_kfmp):
+        raise ValueError("the refresh inputs do not fit the view's counts")
+    ids = np.ascontiguousarray(ids, np.int32)
+    rec = keep["mp_rec"].copy()
+    desc = np.ascontiguousarray(mp_desc, np.uint8).copy()
+    if desc.size != 32 * c.n_mp:
+        raise ValueError("mp_desc holds 32 bytes per MapPoint")
+    info = np.zeros(len(ids), np.uint32)
+    check("orbx_refresh_map_points", load().orbx_refresh_map_points(
+        ctypes.byref(c), ctypes.byref(r), ptr(ids) if len(ids) else None, len(ids), int(what),
+        int(max_obs), ptr(rec) if len(rec) else None, ptr(desc) if desc.size else None,
+        ptr(info) if len(ids) else None, int(device)))
+    return dict(info=info, mp_rec=rec, mp_desc=desc)
 
 
 def update_local_map_host(arrays: dict, feat_mp, cap_kf: int, cap_mp: int, local_kf=(),
