@@ -18,6 +18,7 @@
 #include "orbx_internal.h"
 #include "orbx_math.h"
 #include "orbx_kernels.h"
+#include "orbx_layout.h"
 #include "orbx_fast_pretest.h"
 
 namespace orbx {
@@ -442,6 +443,19 @@ struct NodeArrays {
     int32_t *cnt, *seq;
 };
 
+// The kernel's LDS regions but the candidate arrays, at OctreeCarve's offsets (orbx_layout.h).
+// octree_level reuses some of them under other names; each reuse and its lifetime:
+//   cpos[4 i], [4 i + 1]  node i's split lines, from a round's node loop to the end of its
+//              quadrant pass (the node pass writes the children's positions there next)
+//   stage      = cpos as u64 [NCAP], all of it: the bucket sort's output, inside phase 2's sort
+//              (between the quadrant pass and the node pass, while cpos is idle)
+//   wc         = pre, NT ints of it ([NT / 64][64] keys per wave and bucket), inside the bucket
+//              sort, which is why that sort needs NCAP >= NT; the cut's scan writes pre next,
+//              behind a barrier
+//   best       = cc: a node's best keypoint, then its orientation bucket and rank, after the last
+//              round (the child counts are done with)
+//   sp_hist, sp_start  = pre, pre2: the orientation buckets' sizes and first positions, also after
+//              the last round (used only while the buckets number NCAP at most)
 struct OctreeSmem {
     NodeArrays A, B;
     int32_t* cc;      // child counts: [NCAP][4] u32, or [NCAP][2] u16 pairs (see octree_level)
@@ -470,10 +484,8 @@ __device__ __forceinline__ void child_rect(int q, int x0, int y0, int x1, int y1
     cy1 = (q & 2) ? y1 : sy;
 }
 
-// Chunked exclusive scan over n items (n may exceed 256).  f(i) gives the value; g(i, excl)
-// consumes the exclusive prefix.  Returns the total.  All threads must call.
-// Exclusive scan of f over [0, n), gcb(i, prefix) per element.  Up to NT elements: one block
-// scan, element i on thread i.  Beyond: each thread scans a contiguous run of ceil(n / NT)
+// Exclusive scan of f over [0, n), gcb(i, prefix) per element; returns the total.  All threads
+// must call.  Up to NT elements: one block scan, element i on thread i.  Beyond: each thread scans a contiguous run of ceil(n / NT)
 // elements (f evaluated twice per element, so f must not read what gcb writes), one block scan
 // of the runs' sums, and a closing barrier (a thread's gcb writes are not the elements a
 // thread-strided loop after the scan reads): 3 barriers for any n, where a scan per NT-chunk
@@ -695,6 +707,15 @@ __device__ void octree_level(const Geometry* __restrict__ g, const LevelGeom& L,
                                        ((uint64_t)(uint32_t)cur.seq[i] << 16) | (uint64_t)i;
                 });
             __syncthreads();
+            // nV <= S <= ncap always: nV counts nodes of the list, and the list never outgrows
+            // the plan's out_cap = max(nfeat + 3, 4 n_ini, 4) <= ncap (the first round makes at
+            // most 4 n_ini nodes; a later phase-1 round runs only while S + 3 nToExpand <= N and
+            // adds at most that; a phase-2 round starts below N and stops at the first split that
+            // reaches it, at most N + 2).  So the selection is in effect ncap >= NT ? bucket :
+            // rank, the rank sort sees nV < NT (one of its four keys per thread is live), and the
+            // bitonic branch cannot run.  The test and the dead code stay as written: without
+            // them the kernel came out slower than the rule for this change allows
+            // (profiles/octree_passes_ab.txt).
             if (nV <= sm.ncap && sm.ncap >= NT) {
                 // bucket sort, descending: keys go to buckets by size (min(cnt, 63), larger
                 // sizes first), a stable counting sort.  In phase 2 no root is expandable (phase 1's first
@@ -971,32 +992,19 @@ __global__ __launch_bounds__(NT) void k_octree(const Geometry* __restrict__ g,
     const int lrel = lin / gridDim.y, b = lin - lrel * gridDim.y, tid = threadIdx.x;
     const int level = level_base + lrel;
     const LevelGeom& L = g->lv[level];
-    // carve LDS
-    uint8_t* p = smem;
-    auto take = [&](size_t bytes) { uint8_t* r = p; p += (bytes + 15) & ~(size_t)15; return r; };
-    OctreeSmem sm;
-    int NP2 = 1;
-    while (NP2 < NCAP) NP2 <<= 1;
-    sm.tmp = (int*)take(224 * sizeof(int));
-    sm.ncap = NCAP;
-    sm.sortb = (uint64_t*)take((size_t)NP2 * 8);
-    sm.A.x0 = (int16_t*)take(NCAP * 2); sm.A.y0 = (int16_t*)take(NCAP * 2);
-    sm.A.x1 = (int16_t*)take(NCAP * 2); sm.A.y1 = (int16_t*)take(NCAP * 2);
-    sm.A.cnt = (int32_t*)take(NCAP * 4); sm.A.seq = (int32_t*)take(NCAP * 4);
-    sm.B.x0 = (int16_t*)take(NCAP * 2); sm.B.y0 = (int16_t*)take(NCAP * 2);
-    sm.B.x1 = (int16_t*)take(NCAP * 2); sm.B.y1 = (int16_t*)take(NCAP * 2);
-    sm.B.cnt = (int32_t*)take(NCAP * 4); sm.B.seq = (int32_t*)take(NCAP * 4);
-    sm.cpos = (int16_t*)take((size_t)NCAP * 8);
-    sm.npos = (int16_t*)take(NCAP * 2);
-    sm.pord = (int16_t*)take(NCAP * 2);
-    sm.pre = (int32_t*)take(NCAP * 4);
-    sm.pre2 = (int32_t*)take(NCAP * 4);
-    // the child counts last but the candidate arrays: the LDS path's counts ([NCAP][2] packed
-    // or [NCAP][4]), then its candidates; the global-scratch path's [NCAP][4] counts run on
-    // over the (unused) candidate arrays (octree_lds_bytes sizes both)
-    sm.cc = (int32_t*)take((size_t)NCAP * (packed ? 8 : 16));
-    uint32_t* l_kdata = (uint32_t*)take((size_t)KCAP * 4);
-    int16_t* l_knode = (int16_t*)take((size_t)KCAP * 2);
+    // LDS regions at OctreeCarve's offsets (orbx_layout.h)
+    const OctreeCarve cv(NCAP, KCAP, packed != 0);
+    auto nodes = [&](const uint32_t* o) {
+        return NodeArrays{(int16_t*)(smem + o[OctreeCarve::X0]), (int16_t*)(smem + o[OctreeCarve::Y0]),
+                          (int16_t*)(smem + o[OctreeCarve::X1]), (int16_t*)(smem + o[OctreeCarve::Y1]),
+                          (int32_t*)(smem + o[OctreeCarve::CNT]), (int32_t*)(smem + o[OctreeCarve::SEQ])};
+    };
+    OctreeSmem sm{nodes(cv.node[0]), nodes(cv.node[1]), (int32_t*)(smem + cv.cc),
+                  (int16_t*)(smem + cv.cpos), (int16_t*)(smem + cv.npos), (int16_t*)(smem + cv.pord),
+                  (int32_t*)(smem + cv.pre), (int32_t*)(smem + cv.pre2), (uint64_t*)(smem + cv.sortb),
+                  (int*)(smem + cv.tmp), NCAP};
+    uint32_t* l_kdata = (uint32_t*)(smem + cv.kdata);
+    int16_t* l_knode = (int16_t*)(smem + cv.knode);
 
     // count the level's candidates
     const int* cc = ccnt + (size_t)b * g->n_cells + L.cell_begin;
@@ -1493,19 +1501,6 @@ hipError_t launch_extract(const ExtractLaunch& a, hipStream_t st) {
         return err;
     }
     return hipGetLastError();
-}
-
-size_t octree_lds_bytes(int ncap, int kcap, bool packed) {
-    auto r = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    int np2 = 1;
-    while (np2 < ncap) np2 <<= 1;
-    size_t s = r(224 * 4) + r((size_t)np2 * 8);
-    s += 2 * (4 * r((size_t)ncap * 2) + 2 * r((size_t)ncap * 4));
-    s += r((size_t)ncap * 8) + 2 * r((size_t)ncap * 2) + 2 * r((size_t)ncap * 4);
-    // the LDS path's packed counts + candidates, or the global path's wide counts
-    const size_t lds_path = r((size_t)ncap * (packed ? 8 : 16)) + r((size_t)kcap * 4) + r((size_t)kcap * 2);
-    const size_t glb_path = r((size_t)ncap * 16);
-    return s + (lds_path > glb_path ? lds_path : glb_path);
 }
 
 }  // namespace orbx

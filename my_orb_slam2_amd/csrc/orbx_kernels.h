@@ -171,7 +171,6 @@ hipError_t launch_extract(const ExtractLaunch& a, hipStream_t st);
 hipError_t launch_levels(const ExtractLaunch& a, hipStream_t st, int l_begin, int l_end);
 hipError_t launch_pyr_chain(const ExtractLaunch& a, hipStream_t st);
 size_t fast_lds_bytes(const Geometry& g);
-size_t octree_lds_bytes(int ncap, int kcap, bool packed);
 int octree_threads(int batch, int nlevels);   // k_octree threads per list of a call
 bool orient_spatial(int batch);               // k_orient_desc in the spatial order (operm)
 hipError_t launch_stereo(const StereoLaunch& a, hipStream_t st);

@@ -491,14 +491,14 @@ orbx_status build_geometry(const orbx_extractor_params& prm, int W, int H, Extra
     p.ncap = (int)align_up((size_t)std::max(G.max_out_cap, 16), 16);
     auto kcap_within = [&](bool packed, size_t kb) {
         int kc = std::min(std::max(G.max_ncand_level, 64), 8192);
-        while (kc > 64 && octree_lds_bytes(p.ncap, kc, packed) > kb * 1024) kc -= 64;
+        while (kc > 64 && OctreeCarve(p.ncap, kc, packed).bytes > kb * 1024) kc -= 64;
         return kc;
     };
     p.kcap = kcap_within(true, OCT_LDS_KB);
-    p.octree_lds = octree_lds_bytes(p.ncap, p.kcap, true);
+    p.octree_lds = OctreeCarve(p.ncap, p.kcap, true).bytes;
     // small batches: the same node arrays, candidates in LDS up to OCT_LDS_SMALL_KB
     p.kcap_small = std::max(kcap_within(false, OCT_LDS_SMALL_KB), p.kcap);
-    p.octree_lds_small = std::max(octree_lds_bytes(p.ncap, p.kcap_small, false), p.octree_lds);
+    p.octree_lds_small = std::max(OctreeCarve(p.ncap, p.kcap_small, false).bytes, p.octree_lds);
     G.stereo_ob = G.nlevels;
     p.stereo_lds = stereo_lds_bytes(G.kp_cap, G.lv[0].h, G.stereo_ob);
     if (p.stereo_lds > 160 * 1024) {   // row buckets only (octaves tested per candidate)

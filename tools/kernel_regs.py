@@ -13,7 +13,8 @@ import tempfile
 sys.path.insert(0, str(pathlib.Path(__file__).resolve().parent))
 import isa_dump  # noqa: E402
 
-FIELDS = (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".vgpr_spill_count")
+FIELDS = (".vgpr_count", ".sgpr_count", ".group_segment_fixed_size", ".vgpr_spill_count",
+          ".sgpr_spill_count", ".private_segment_fixed_size")
 
 
 def main() -> None:
